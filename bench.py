@@ -12,6 +12,13 @@ aperture halos when those are narrower), diffraction sum of the rank's
 output-trace block.  Strong scaling: the radargram is fixed, output blocks are
 balanced by in-aperture pair count.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  --full
+adds everything else the benchmark measures and checks (CPU baselines, in-run
+parity against the C oracle, the one-shot and first-call figures, counter
+passes, the config-2 / config-5 / float64 sub-records).  --dump-outputs DIR
+writes what the last timed step computed (DIR/migrated.npy, a fixed seeded
+sample of output traces) so that two builds can be compared output for output.
+
 Rank 0 prints ONE JSON line (see DESIGN.md section 6 for the field meanings).
 No torch anywhere: the control plane is impdar_amd.parallel.Rendezvous, all
 device work goes through the C ABI.
@@ -39,6 +46,9 @@ FP32_VECTOR_PEAK_TF = 157.3
 FP64_VECTOR_PEAK_TF = 78.6   # v_fma_f64: 4 cycles per wave instruction, measured (profiles/r04_valu_rates.txt): 64 x 2 / 4 x 1024 SIMDs x 2.4 GHz
 FP16_MFMA_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: BF16/FP16 MFMA ~2.5 PF dense
 PARITY_BAR = 1e-4         # relative L2 of the fast (float32) kernel against the float64 oracle, DESIGN.md section 2
+DUMP_TRACES = 1024        # --dump-outputs: output traces in the sample (fewer when snum makes them pass DUMP_BYTES)
+DUMP_BYTES = 60 << 20
+DUMP_SEED = 0
 
 
 def log(*a):
@@ -46,7 +56,21 @@ def log(*a):
 
 
 def host_threads():
-    return max(1, min(64, os.cpu_count() or 1))
+    """The cores this process may use (its affinity mask, and OMP_NUM_THREADS when set), at most 64."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    omp = os.environ.get('OMP_NUM_THREADS', '')
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, min(64, n))
+
+
+def dump_columns(snum, tnum, itemsize):
+    """The output traces --dump-outputs writes: a fixed, seeded sample, sorted, the same for every run of the same sizes."""
+    k = int(min(tnum, DUMP_TRACES, max(1, DUMP_BYTES // (snum * itemsize))))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(tnum, size=k, replace=False)).astype(np.int64)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -851,10 +875,18 @@ def main():
                     help='strong (default): the BASELINE radargram is fixed; weak: --tnum traces PER GPU')
     ap.add_argument('--exchange', default='auto', choices=['auto', 'halo', 'allgather'])
     ap.add_argument('--data', default='synthetic', choices=['synthetic', 'noise'])
-    ap.add_argument('--no-cpu', action='store_true', help='skip the host-CPU legs (and the parity check that needs them)')
-    ap.add_argument('--no-pmc', action='store_true', help='skip the rocprofv3 counter passes (roofline.traffic = null)')
-    ap.add_argument('--no-paths', action='store_true', help='skip the config-2 / config-5 sub-records')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the PCIe-inclusive one-shot figure')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run everything else the benchmark measures and checks: CPU baselines and '
+                         'in-run parity against the C oracle, the single-radargram figure, the one-shot and first-call figures, '
+                         'the rocprofv3 counter passes and the config-2 / config-5 / float64 sub-records (each can be '
+                         'switched off with its --no-* option); off by default')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last step computed to DIR/migrated.npy: the migrated image '
+                         '(float32, or float64 with --dtype f64) on a fixed, seeded sample of output traces, at most %d' % DUMP_TRACES)
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the host-CPU legs (and the parity check that needs them)')
+    ap.add_argument('--no-pmc', action='store_true', help='with --full: skip the rocprofv3 counter passes (roofline.traffic = null)')
+    ap.add_argument('--no-paths', action='store_true', help='with --full: skip the config-2 / config-5 sub-records')
+    ap.add_argument('--no-e2e', action='store_true', help='with --full: skip the PCIe-inclusive one-shot figure')
     ap.add_argument('--cpu-budget', type=float, default=15.0)
     ap.add_argument('--first-call', default=None, choices=['kirch', 'stolt', 'phsh'], help=argparse.SUPPRESS)
     ap.add_argument('--spot-oracle', nargs=2, default=None, metavar=('KIND', 'OUT'), help=argparse.SUPPRESS)
@@ -864,6 +896,8 @@ def main():
     ap.add_argument('--full-line', action='store_true', help='print the record with its prose notes (default: numbers only, so that the line fits the driver\'s 8 KB tail; the keys are explained in profiles/bench_record_keys.md)')
     ap.add_argument('--data-child', default='zeros', choices=['zeros', 'synthetic'], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.spot_oracle:
         spot_oracle_child(*args.spot_oracle)
         return
@@ -898,13 +932,14 @@ def main():
     # the FIRST call of a process (what `impproc migrate file.mat` is), measured in fresh child processes started
     # before this one touches the GPU
     first_calls = None
-    if rank == 0 and world == 1 and not args.no_e2e and not args.pmc_child and not os.environ.get('IMPDAR_BENCH_FORCE_DIST'):
+    full = args.full and not args.pmc_child
+    if rank == 0 and world == 1 and full and not args.no_e2e and not os.environ.get('IMPDAR_BENCH_FORCE_DIST'):
         t0 = time.time()
         first_calls = first_call_records()
         log('[bench] first-call children took %.1f s' % (time.time() - t0))
     # the CPU oracle of the 8192^2 phase-shift sub-records' spot wavenumbers: child processes beside everything below
     spot = None
-    if rank == 0 and world == 1 and not args.no_paths and not args.no_cpu and not args.pmc_child:
+    if rank == 0 and world == 1 and full and not args.no_paths and not args.no_cpu:
         spot = start_spot_oracles()
 
     from impdar_amd import _hip, parallel, synth
@@ -939,7 +974,7 @@ def main():
         local_data = np.zeros((snum, max(nloc, 1)), dtype=np_dtype)
     elif args.data == 'synthetic':
         # rank 0 builds the whole radargram when it needs it for the CPU legs / parity anyway
-        need_full = rank == 0 and not args.no_cpu and not args.pmc_child
+        need_full = rank == 0 and full and not args.no_cpu
         lo, hi = (0, tnum) if need_full else (jlo, jhi)
         blk = synth.diffractor_radargram(snum, tnum, vel=vel, dtype=np_dtype, trace_lo=lo, trace_hi=hi, chunk=128,
                                          threads=host_threads())
@@ -979,17 +1014,21 @@ def main():
         plan.destroy()
         return
 
+    # what the last timed step computed: this rank's output block (--full checks it, --dump-outputs writes a sample of it)
+    out_host = d_out.to_host()[:, :xhi - xlo] if (full or args.dump_outputs) else None
+    finite = bool(np.isfinite(out_host).all()) if full else None
+    dcols = dump_columns(snum, tnum, np.dtype(np_dtype).itemsize) if args.dump_outputs else np.zeros(0, np.int64)
+    dcols = dcols[(dcols >= xlo) & (dcols < xhi)]
+
     # one radargram on an idle device: nothing to hide the exchange behind (the timed loop pipelines it under the
     # previous radargram's diffraction sum)
-    fence()
-    t1 = time.perf_counter()
-    step()
-    fence()
-    single_ms = rdv.allreduce_max((time.perf_counter() - t1) * 1e3)
-    s_prep, s_gather, s_mig = plan.history_ms(0)
-
-    out_host = d_out.to_host()[:, :xhi - xlo]
-    finite = bool(np.isfinite(out_host).all())
+    if full:
+        fence()
+        t1 = time.perf_counter()
+        step()
+        fence()
+        single_ms = rdv.allreduce_max((time.perf_counter() - t1) * 1e3)
+        s_prep, s_gather, s_mig = plan.history_ms(0)
 
     # ---- what every rank did, gathered on rank 0: its block, the rows RCCL handed it, its own event times, four
     # columns of its timed output (rank 0 holds them to the C oracle below), and what RCCL itself says about the
@@ -1000,7 +1039,7 @@ def main():
         vals = [C.c_int(-1) for _ in range(4)]
         if _hip.load().impdar_comm_info(ctx, *[C.byref(v) for v in vals]) == 0:
             rccl = dict(ranks=vals[0].value, rank=vals[1].value, device=vals[2].value, version=vals[3].value)
-    pcols = np.unique(np.linspace(xlo, max(xhi - 1, xlo), 4).round().astype(np.int64)) if xhi > xlo else np.zeros(0, np.int64)
+    pcols = np.unique(np.linspace(xlo, max(xhi - 1, xlo), 4).round().astype(np.int64)) if (full and xhi > xlo) else np.zeros(0, np.int64)
     mine = dict(rank=rank, device=local % ndev, output_block=[int(xlo), int(xhi)], input_shard=[int(jlo), int(jhi)],
                 rows_received=int(sk.xplan['rows_received'][rank]) if world > 1 else 0,
                 prep_ms=float(np.mean(prep_ms)) if prep_ms else None,
@@ -1008,8 +1047,14 @@ def main():
                 migrate_ms=float(np.mean(kernel_ms)) if kernel_ms else None,
                 pairs=int(sk.pairs[rank]), rccl=rccl, finite=finite,
                 cols=[int(c) for c in pcols],
-                colvals=np.ascontiguousarray(out_host[:, pcols - xlo], dtype=np.float64) if len(pcols) else np.zeros((snum, 0)))
+                colvals=np.ascontiguousarray(out_host[:, pcols - xlo], dtype=np.float64) if len(pcols) else np.zeros((snum, 0)),
+                dump=np.ascontiguousarray(out_host[:, dcols - xlo]) if len(dcols) else np.zeros((snum, 0), np_dtype))
     everyone = rdv.allgather(mine)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'migrated.npy'),
+                np.ascontiguousarray(np.concatenate([e['dump'] for e in sorted(everyone, key=lambda e: e['output_block'][0])],
+                                                    axis=1), dtype=np_dtype))
 
     res = None
     if rank == 0:
@@ -1036,17 +1081,13 @@ def main():
                                     "rows_allgather": int(sk.xplan['rows_allgather'])},
                        "prep_ms": float(np.mean(prep_ms)) if prep_ms else None,
                        "exchange_ms": float(np.mean(gather_ms)) if gather_ms else None,
-                       "single_radargram": {"wall_ms": single_ms, "prep_ms": s_prep, "exchange_ms": s_gather,
-                                            "migrate_ms": s_mig,
-                                            "note": "one radargram on an idle device: prep + exchange are exposed here; "
-                                                    "the timed steps overlap them with the previous diffraction sum"},
                        "rccl": ({"ranks": everyone[0]['rccl']['ranks'], "version": everyone[0]['rccl']['version'],
                                  "ranks_seen_by_every_rank": [e['rccl']['ranks'] if e['rccl'] else None for e in everyone]}
                                 if everyone[0]['rccl'] else None),
                        "ranks": [{k: e[k] for k in ('rank', 'device', 'output_block', 'input_shard', 'rows_received',
                                                     'prep_ms', 'exchange_ms', 'migrate_ms', 'pairs', 'finite')}
                                  for e in everyone],
-                       "output_finite": bool(all(e['finite'] for e in everyone))},
+                       "output_finite": bool(all(e['finite'] for e in everyone)) if full else None},
             # the binding roof: every pair's sample is one 4-byte lane of a ds_read_b128, so the LDS read port
             # (256 B/clk/CU) bounds the diffraction sum; HBM only sees the compulsory image + output bytes
             "roofline": {"bound": "lds", "achieved": achieved, "peak": LDS_PEAK_GBS, "unit": "GB/s",
@@ -1060,11 +1101,16 @@ def main():
                                                      "peak. A multiple of the peak, not a fraction: the samples are "
                                                      "re-read from LDS, not from HBM"}},
         }
-        if not finite:
-            res["error"] = "non-finite values in the migrated output"
+        if full:
+            res["config"]["single_radargram"] = {
+                "wall_ms": single_ms, "prep_ms": s_prep, "exchange_ms": s_gather, "migrate_ms": s_mig,
+                "note": "one radargram on an idle device: prep + exchange are exposed here; the timed steps overlap "
+                        "them with the previous diffraction sum"}
+            if not res["config"]["output_finite"]:
+                res["error"] = "non-finite values in the migrated output"
 
     # ---- CPU legs + in-run parity of the timed output (rank 0)
-    if rank == 0 and not args.no_cpu and args.data == 'synthetic':
+    if rank == 0 and full and not args.no_cpu and args.data == 'synthetic':
         t0 = time.time()
         if world == 1:
             rec, cols, want = cpu_baseline(full_data, geo, vel, tnum, args.cpu_budget)
@@ -1102,7 +1148,7 @@ def main():
     d_in.free()
     d_out.free()
 
-    if rank == 0 and world == 1 and not os.environ.get('IMPDAR_BENCH_FORCE_DIST'):
+    if rank == 0 and world == 1 and full and not os.environ.get('IMPDAR_BENCH_FORCE_DIST'):
         # ---- PCIe-inclusive one-shot figure (never `value`): RadarData.migrate('kirch') on host arrays
         if not args.no_e2e and full_data is not None:
             import contextlib

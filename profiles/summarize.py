@@ -56,7 +56,7 @@ def main():
         w, k = int(b['warmup']), int(b['steps'])
         timed = d[w:w + k]
         with open(os.path.join(here, '%s_bench_kernel_launches.txt' % tag), 'w') as fo:
-            fo.write('%s: %d launches in this rocprofv3 --kernel-trace run of `python3 bench.py --no-pmc`, ms each, launch order\n'
+            fo.write('%s: %d launches in this rocprofv3 --kernel-trace run of `python3 bench.py --full --no-pmc`, ms each, launch order\n'
                      % (kname, len(d)))
             fo.write(' '.join('%.3f' % x for x in d) + '\n')
             fo.write('average of all launches (what --stats reports): %.4f ms\n' % (sum(d) / len(d)))

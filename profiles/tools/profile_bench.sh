@@ -9,10 +9,10 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R
 B="python3 bench.py --steps 3 --warmup 1 --no-cpu --no-pmc --no-paths --no-e2e"
-# the stats pass runs the default bench command (python3 bench.py: 20 steps, 3 warm-up, CPU baseline leg) so that
+# the stats pass runs the whole bench command (python3 bench.py --full: 20 steps, 3 warm-up, CPU baseline leg) so that
 # its average kernel duration is the one bench.py reports from HIP events in the JSON line of the same process
 # (kept as bench_under_rocprof.json); the counter passes only need a few launches
-rocprofv3 --kernel-trace --stats -d $O/stats/run -o x --output-format csv -- python3 bench.py --no-pmc > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/stats/run -o x --output-format csv -- python3 bench.py --full --no-pmc > $O/stats.log 2>&1
 grep '^{"metric"' $O/stats.log > $O/bench_under_rocprof.json
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pmc_fetch/run -o x --output-format csv -- $B > $O/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pmc_write/run -o x --output-format csv -- $B > $O/pmc_write.log 2>&1

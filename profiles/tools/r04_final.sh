@@ -1,7 +1,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out/r04_final
 O=gpurun_out/r04_final
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.log
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.log
 echo "bench rc=$?"
 (timeout 900 python tests/tools/fuzz_kirchhoff.py 400 71 2>&1 | tail -8) > $O/fuzz_k.txt
 (timeout 900 python tests/tools/fuzz_phaseshift.py 300 72 2>&1 | tail -8) > $O/fuzz_ps.txt
