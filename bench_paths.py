@@ -3,7 +3,8 @@
 BASELINE config 2 (4096x4096 float32), phase-shift at config 5 (8192x8192,
 constant v and 1-D v(z)), the v(x,z) finite-difference branch (256x512) and the band-pass / re-spacing steps in front of a
 migration at config-3 size (4096x10000 float32, resident in HBM, plus the
-three-step chain with and without residency), each through the product path on
+three-step chain with and without residency), the horizontal filters (hfilt, adaptive
+hfilt at windows 10 and 1000) at the same size, resident, each through the product path on
 one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
@@ -226,6 +227,64 @@ def main():
             print(json.dumps({"path": "chain vbp -> constant_space -> stolt, %s" % ("resident in HBM" if resident else "host buffers between steps"),
                               "config": "%dx%d float32 in, float64 out" % (snum, tnum), "host_seconds": best,
                               "traces_per_s": tnum / best}), flush=True)
+
+    if 'hfilt' not in args.skip:
+        # horizontal filters at the chain's size, resident: device time per call, bytes / time against HBM
+        from impdar_amd import hfilt as hf
+        snum, tnum = (int(v) for v in args.chain.split('x'))
+        ctx, lib = _hip.context(), _hip.load()
+        hrng = np.random.default_rng(5)
+        x = hrng.standard_normal((snum, tnum)).astype(np.float32)
+        x[40:60] += 1000.0
+        scale = hf.taper(np.arange(snum) * 1e-2)
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+
+        def hdev_ms(fn, reps=10):
+            fn()
+            lib.impdar_ctx_sync(ctx)
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            lib.impdar_ctx_sync(ctx)
+            return (time.perf_counter() - t0) / reps * 1e3
+
+        def hline(path, ms, algo, note, cb):
+            print(json.dumps({"path": path, "config": "%dx%d float32" % (snum, tnum), "device_ms": ms,
+                              "traces_per_s": tnum / ms * 1e3, "algorithmic_bytes": algo,
+                              "roofline": {"bound": "hbm", "achieved": algo / ms / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                           "frac": algo / ms / 1e6 / 8000.0, "note": note},
+                              "cpu_baseline": cb}), flush=True)
+
+        lo, hi = hf.hfilt_bounds(0, tnum, tnum)
+        ms = hdev_ms(lambda: hf.hfilt_dev(d_x, lo, hi, scale))
+        cb = None
+        if not args.no_cpu:
+            t0 = time.perf_counter()
+            avg = np.mean(x[:, lo:hi], axis=-1) * scale
+            _ = x - np.atleast_2d(avg).transpose().astype(x.dtype)
+            cb = {"seconds": time.perf_counter() - t0, "kind": "reference", "cores": 1,
+                  "sample": "the reference's NumPy expression on all %d traces" % tnum}
+        hline("hfilt (mean trace removed), resident", ms, 3 * snum * tnum * 4,
+              "row mean read + row read/write; the second read of a row is expected from cache", cb)
+        for window in (10, 1000):
+            wlo, whi = hf.ahfilt_windows(tnum, window)
+            ms = hdev_ms(lambda: hf.ahfilt_dev(d_x, wlo, whi, scale))
+            cb = None
+            if not args.no_cpu:
+                from scipy.signal import filtfilt
+                m = min(tnum, 200)
+                t0 = time.perf_counter()
+                out = np.zeros((snum, m), dtype=x.dtype)
+                for i in range(m):                             # the reference's per-trace loop, restated
+                    pk = x[:, wlo[i]:whi[i]].copy()
+                    out[:, i] = x[:, i] - filtfilt([.25] * 4, 1, np.mean(pk, axis=-1)) * scale
+                cb = {"seconds": (time.perf_counter() - t0) * tnum / m, "kind": "reference", "cores": 1,
+                      "sample": "per-trace loop on %d of %d traces, scaled to all" % (m, tnum)}
+            # pass 1: read x, write M; pass 2: read M and x, write x (fp64 prefix rows of pass 1 counted apart)
+            hline("ahfilt window %d (adaptive), resident" % window, ms, 5 * snum * tnum * 4,
+                  "two passes: windowed means from fp64 prefix rows (8 B/element more, largely cache-resident), "
+                  "then the 7-tap stencil, taper and subtraction", cb)
+        d_x.free()
 
 
 if __name__ == '__main__':

@@ -1,12 +1,14 @@
 #! /usr/bin/env python
-"""``impproc migrate`` (and the two steps usually run in front of it, ``vbp`` and ``interp``) on the MI355X
-engine.
+"""``impproc migrate`` (and the steps usually run in front of it, ``vbp``, ``hfilt``, ``ahfilt`` and ``interp``)
+on the MI355X engine.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
-vbp ``:113-125``, interp ``:222-251``, ``main`` ``:378-415``, ``mig`` ``:508-519``, ``vbp`` ``:438-440``,
-``interp`` ``:483-491``): same options, types and defaults, same output naming
-(``<name minus _raw>_<migrated|bandpassed|interp>.mat``, ``-o`` file or folder).  The reference's other
-processing sub-commands are out of scope.
+hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, interp ``:222-251``, ``main`` ``:378-415``, ``hfilt``
+``:418-420``, ``ahfilt`` ``:423-425``, ``mig`` ``:508-519``, ``vbp`` ``:438-440``, ``interp`` ``:483-491``):
+same options, types and defaults, same output naming
+(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|interp>.mat``, ``-o`` file or folder).  As in the
+reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default window of 1000 traces.
+The reference's other processing sub-commands are out of scope.
 
     python -m impdar_amd.bin.impproc migrate --mtype kirch line1_raw.mat
 """
@@ -42,6 +44,18 @@ def _get_args():
                                  'slabs) migration over this many MI355X of the node '
                                  '(default: $IMPDAR_NGPUS, else one)')
     _add_def_args(parser_mig)
+
+    parser_hfilt = subparsers.add_parser('hfilt', help='Horizontally filter the data by subtracting the average '
+                                                        'trace from a window')
+    parser_hfilt.set_defaults(func=hfilt, name='hfilted')
+    parser_hfilt.add_argument('start_trace', type=int, help='First trace of representative subset')
+    parser_hfilt.add_argument('end_trace', type=int, help='Last trace of representative subset')
+    _add_def_args(parser_hfilt)
+
+    parser_ahfilt = subparsers.add_parser('ahfilt', help='Horizontally filter the data adaptively')
+    parser_ahfilt.set_defaults(func=ahfilt, name='ahfilt')
+    parser_ahfilt.add_argument('win', type=int, help='Number of traces to include in the moving average')
+    _add_def_args(parser_ahfilt)
 
     parser_vbp = subparsers.add_parser('vbp', help='Vertically bandpass the data')
     parser_vbp.set_defaults(func=vbp, name='bandpassed')
@@ -106,6 +120,16 @@ def mig(dat, mtype='stolt', vel=1.69e8, vtaper=100, htaper=100, tmig=0, verbose=
         os.environ['IMPDAR_NGPUS'] = str(gpus)
     dat.migrate(mtype, vel=vel, vtaper=vtaper, htaper=htaper, tmig=tmig, verbose=verbose, vel_fn=vel_fn,
                 nxpad=nxpad, nearfield=nearfield)
+
+
+def hfilt(dat, start_trace=0, end_trace=-1, **kwargs):
+    """Subtract the average trace of a range of traces."""
+    dat.hfilt(ftype='hfilt', bounds=(start_trace, end_trace))
+
+
+def ahfilt(dat, window_size=1000, **kwargs):
+    """Adaptive horizontal filter.  The parsed ``win`` lands in ``kwargs``, as in the reference."""
+    dat.hfilt(ftype='adaptive', window_size=window_size)
 
 
 def vbp(dat, low_MHz=1, high_MHz=10000, **kwargs):

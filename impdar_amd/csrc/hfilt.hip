@@ -1,0 +1,335 @@
+// The two horizontal filters an impproc/impdar chain runs between the band pass and the migration, kept on the
+// device so that a radargram stays resident from the first filter to the migrated image:
+//
+//   * horizontalfilt(ntr1, ntr2)  (reference src/impdar/lib/RadarData/_RadarDataFiltering.py:93-135):
+//       every sample row loses mean(row[lo:hi]) * scale[t], the mean and the tapered mean each cast to the data's
+//       dtype first (float32 data: float32 mean, float32 subtraction);
+//   * adaptivehfilt(window_size)  (:19-90): trace i loses scale[t] * filtfilt([.25]*4, 1, mean(data[:, lo_i:hi_i], -1)).
+//       For that 4-tap box filtfilt is exactly the 7-tap stencil [1,2,3,4,3,2,1]/16 on the odd extension of the
+//       mean trace (M[-k] = 2 M[0] - M[k], M[snum-1+k] = 2 M[snum-1] - M[snum-1-k], k = 1..3): the 12-sample pad
+//       absorbs the steady-state initial conditions before they reach a kept sample.
+//
+// Data is (snum, tnum) row-major: a row holds one sample of every trace and is contiguous.  adaptivehfilt is two
+// passes whose cost does not depend on the window:
+//   ahfilt_rowmean_kernel  one workgroup per row (persistent over rows): an fp64 prefix sum of x - x[t, 0] along the
+//                          row (chunks of 1024 with a carry, so any tnum), then M[t, i] = x[t, 0] + (P[hi_i] -
+//                          P[lo_i]) / (hi_i - lo_i) for the host's window table, NaN for an empty window, stored in
+//                          the data's dtype (the reference's mean of float32 data is float32).  The pivot keeps the
+//                          difference of two long prefix sums from losing the digits of a row that holds a strong
+//                          flat band -- the very thing the filter is for.
+//   ahfilt_apply_kernel    one thread per trace walks a strip of rows with M[t-3..t+3] in registers, applies the
+//                          stencil and the taper and subtracts in fp64, storing in the data's dtype.
+// The file is compiled with -ffp-contract=off, like the rest of the library.
+#include "common.h"
+#include <mutex>
+
+#define HF_BLOCK 256
+#define HF_PER 4                          // consecutive elements per thread in one scan chunk
+#define HF_CHUNK (HF_BLOCK * HF_PER)
+#define HF_ROWS 64                        // rows per thread in ahfilt_apply_kernel
+#define HF_MAX_ROW_BLOCKS 2048            // resident workgroups of ahfilt_rowmean_kernel (each owns a prefix-sum row)
+
+// exclusive prefix of one value per thread across the workgroup (fixed order: the host and resident forms agree
+// bit for bit); `total` is the workgroup's sum
+__device__ __forceinline__ double hf_block_scan(double v, double *wsum, double &total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    double ex = __shfl_up(inc, 1, 64);
+    if (lane == 0) ex = 0.0;
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    double before = 0.0, tot = 0.0;
+#pragma unroll
+    for (int k = 0; k < HF_BLOCK / 64; ++k) {
+        const double s = wsum[k];
+        if (k < w) before += s;
+        tot += s;
+    }
+    __syncthreads();   // wsum is rewritten by the next chunk
+    total = tot;
+    return before + ex;
+}
+
+template <typename T>
+__global__ __launch_bounds__(HF_BLOCK) void ahfilt_rowmean_kernel(const T *__restrict__ x, T *__restrict__ M,
+                                                                  double *__restrict__ Pbuf, const int *__restrict__ lo,
+                                                                  const int *__restrict__ hi, int snum, int tnum)
+{
+    __shared__ double wsum[HF_BLOCK / 64];
+    double *P = Pbuf + (size_t)blockIdx.x * (tnum + 1);   // this workgroup's prefix-sum row, P[k] = sum(x[:k] - x[0])
+    for (int t = blockIdx.x; t < snum; t += gridDim.x) {
+        const T *xr = x + (size_t)t * tnum;
+        const double x0 = (double)xr[0];
+        double carry = 0.0;
+        if (threadIdx.x == 0) P[0] = 0.0;
+        for (int c0 = 0; c0 < tnum; c0 += HF_CHUNK) {
+            const int j = c0 + threadIdx.x * HF_PER;
+            double s[HF_PER];
+#pragma unroll
+            for (int u = 0; u < HF_PER; ++u) s[u] = j + u < tnum ? (double)xr[j + u] - x0 : 0.0;
+#pragma unroll
+            for (int u = 1; u < HF_PER; ++u) s[u] += s[u - 1];
+            double total;
+            const double ex = carry + hf_block_scan(s[HF_PER - 1], wsum, total);
+#pragma unroll
+            for (int u = 0; u < HF_PER; ++u)
+                if (j + u < tnum) P[j + u + 1] = ex + s[u];
+            carry += total;
+        }
+        __syncthreads();   // the whole prefix row is written and visible to the workgroup
+        T *Mr = M + (size_t)t * tnum;
+#pragma unroll 4
+        for (int i = threadIdx.x; i < tnum; i += HF_BLOCK) {
+            const int a = lo[i], b = hi[i];
+            const double m = b > a ? x0 + (P[b] - P[a]) / (double)(b - a) : __builtin_nan("");
+            Mr[i] = (T)m;
+        }
+        __syncthreads();   // P is rewritten for the next row
+    }
+}
+
+// row r of the odd extension of the mean traces, in the data's own arithmetic (scipy's odd_ext on a float32 mean
+// is a float32 expression), widened; r in [-3, snum + 2] and snum > 12
+template <typename T>
+__device__ __forceinline__ double hf_mext(const T *__restrict__ M, int r, int i, int snum, int tnum)
+{
+    if (r < 0) return (double)(T)((T)2 * M[i] - M[(size_t)(-r) * tnum + i]);
+    if (r >= snum) {
+        const int e = snum - 1;
+        return (double)(T)((T)2 * M[(size_t)e * tnum + i] - M[(size_t)(2 * e - r) * tnum + i]);
+    }
+    return (double)M[(size_t)r * tnum + i];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ahfilt_apply_kernel(T *__restrict__ x, const T *__restrict__ M,
+                                                           const double *__restrict__ scale, int snum, int tnum)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= tnum) return;
+    const int t0 = blockIdx.y * HF_ROWS;
+    const int t1 = t0 + HF_ROWS < snum ? t0 + HF_ROWS : snum;
+    double w[7];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) w[k] = hf_mext(M, t0 - 3 + k, i, snum, tnum);
+    for (int t = t0; t < t1; ++t) {
+        w[6] = hf_mext(M, t + 3, i, snum, tnum);
+        const double s = (w[0] + 2.0 * w[1] + 3.0 * w[2] + 4.0 * w[3] + 3.0 * w[4] + 2.0 * w[5] + w[6]) * 0.0625;
+        T *p = x + (size_t)t * tnum + i;
+        *p = (T)((double)*p - s * scale[t]);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) w[k] = w[k + 1];
+    }
+}
+
+// one workgroup per row: fp64 sum over [lo, hi), the mean and the tapered mean each cast to T, then the row loses it
+// in T's arithmetic (reference: data - (mean(data[:, lo:hi], -1) * scale).astype(data.dtype)[:, None])
+template <typename T>
+__global__ __launch_bounds__(HF_BLOCK) void hfilt_mean_kernel(T *__restrict__ x, int tnum, int lo, int hi,
+                                                              const double *__restrict__ scale)
+{
+    __shared__ double red[HF_BLOCK / 64];
+    const int t = blockIdx.x;
+    T *xr = x + (size_t)t * tnum;
+    double s = 0.0;
+#pragma unroll 4
+    for (int j = lo + threadIdx.x; j < hi; j += HF_BLOCK) s += (double)xr[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    const double sum = (red[0] + red[1]) + (red[2] + red[3]);
+    const T m = (T)(sum / (double)(hi - lo));
+    const T a = (T)((double)m * scale[t]);
+#pragma unroll 8
+    for (int j = threadIdx.x; j < tnum; j += HF_BLOCK) xr[j] = xr[j] - a;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+
+struct HfiltScratch {
+    impdar_ctx *owner = nullptr;
+    DevBuf data, M, P, tab;
+    // pinned staging of the small host tables: copied on the stream without draining it; the next call waits only for
+    // the previous table copy before it reuses the buffer
+    void *host = nullptr;
+    size_t host_bytes = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    void release()
+    {
+        data.release();
+        M.release();
+        P.release();
+        tab.release();
+        if (pending && ev) (void)hipEventSynchronize(ev);
+        if (host) (void)hipHostFree(host);
+        if (ev) (void)hipEventDestroy(ev);
+        host = nullptr;
+        host_bytes = 0;
+        ev = nullptr;
+        pending = false;
+    }
+};
+static HfiltScratch g_hf;
+static std::recursive_mutex g_hf_mu;   // one scratch set per process; re-entrant (the host forms call the resident ones)
+#define HFILT_LOCK() std::lock_guard<std::recursive_mutex> hfilt_lock_(g_hf_mu)
+
+static void hf_bind(impdar_ctx *ctx)
+{
+    if (g_hf.owner != ctx) {
+        g_hf.release();
+        g_hf.owner = ctx;
+    }
+}
+
+void impdar_hfilt_forget(impdar_ctx *ctx)
+{
+    HFILT_LOCK();
+    if (g_hf.owner == ctx) {
+        g_hf.release();
+        g_hf.owner = nullptr;
+    }
+}
+
+// the concatenation of `n` host blocks into the device table buffer, enqueued on the compute stream
+static int hf_upload_tables(impdar_ctx *ctx, const void *const *src, const size_t *bytes, int n)
+{
+    size_t total = 0;
+    for (int k = 0; k < n; ++k) total += (bytes[k] + 15) & ~(size_t)15;
+    if (g_hf.pending) IMPDAR_HIP_CHECK(hipEventSynchronize(g_hf.ev));
+    g_hf.pending = false;
+    if (!g_hf.ev) IMPDAR_HIP_CHECK(hipEventCreateWithFlags(&g_hf.ev, hipEventDisableTiming));
+    if (g_hf.host_bytes < total) {
+        if (g_hf.host) IMPDAR_HIP_CHECK(hipHostFree(g_hf.host));
+        g_hf.host = nullptr;
+        g_hf.host_bytes = 0;
+        IMPDAR_HIP_CHECK(hipHostMalloc(&g_hf.host, total, hipHostMallocDefault));
+        g_hf.host_bytes = total;
+    }
+    IMPDAR_HIP_CHECK(g_hf.tab.ensure(total));
+    size_t off = 0;
+    for (int k = 0; k < n; ++k) {
+        memcpy((char *)g_hf.host + off, src[k], bytes[k]);
+        off += (bytes[k] + 15) & ~(size_t)15;
+    }
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(g_hf.tab.p, g_hf.host, total, hipMemcpyHostToDevice, ctx->stream));
+    IMPDAR_HIP_CHECK(hipEventRecord(g_hf.ev, ctx->stream));
+    g_hf.pending = true;
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_hfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, int lo, int hi,
+                                const double *scale)
+{
+    HFILT_LOCK();
+    IMPDAR_ARG_CHECK(ctx && d_data && scale, "impdar_hfilt: null argument");
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfilt: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
+    IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    hf_bind(ctx);
+    const void *src[1] = {scale};
+    const size_t bytes[1] = {(size_t)snum * sizeof(double)};
+    int rc = hf_upload_tables(ctx, src, bytes, 1);
+    if (rc) return rc;
+    if (dtype == IMPDAR_F32)
+        hipLaunchKernelGGL(hfilt_mean_kernel<float>, dim3(snum), dim3(HF_BLOCK), 0, ctx->stream, (float *)d_data, tnum, lo,
+                           hi, g_hf.tab.as<double>());
+    else
+        hipLaunchKernelGGL(hfilt_mean_kernel<double>, dim3(snum), dim3(HF_BLOCK), 0, ctx->stream, (double *)d_data, tnum,
+                           lo, hi, g_hf.tab.as<double>());
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return impdar_ctx_mark_produced(ctx);
+}
+
+extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo,
+                                 const int *hi, const double *scale)
+{
+    HFILT_LOCK();
+    IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && scale, "impdar_ahfilt: null argument");
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_ahfilt: dtype must be float32 or float64");
+    // scipy.signal.filtfilt's own guard and message (padlen = 3 * 4 taps)
+    IMPDAR_ARG_CHECK(snum > 12, "The length of the input vector x must be greater than padlen, which is %d.", 12);
+    IMPDAR_ARG_CHECK(tnum >= 1, "impdar_ahfilt: empty radargram");
+    for (int i = 0; i < tnum; ++i)
+        IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] <= tnum,
+                         "impdar_ahfilt: window [%d, %d) of trace %d not inside [0, %d]", lo[i], hi[i], i, tnum);
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    hf_bind(ctx);
+    const size_t es = impdar_dtype_size(dtype);
+    const int nblk = snum < HF_MAX_ROW_BLOCKS ? snum : HF_MAX_ROW_BLOCKS;
+    IMPDAR_HIP_CHECK(g_hf.M.ensure((size_t)snum * tnum * es));
+    IMPDAR_HIP_CHECK(g_hf.P.ensure((size_t)nblk * (tnum + 1) * sizeof(double)));
+    const size_t db = (size_t)snum * sizeof(double), ib = (size_t)tnum * sizeof(int);
+    const void *src[3] = {scale, lo, hi};
+    const size_t bytes[3] = {db, ib, ib};
+    int rc = hf_upload_tables(ctx, src, bytes, 3);
+    if (rc) return rc;
+    const double *d_scale = g_hf.tab.as<double>();
+    const int *d_lo = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15));
+    const int *d_hi = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15) + ((ib + 15) & ~(size_t)15));
+    const dim3 grid2((tnum + 255) / 256, (snum + HF_ROWS - 1) / HF_ROWS);
+    if (dtype == IMPDAR_F32) {
+        hipLaunchKernelGGL(ahfilt_rowmean_kernel<float>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream, (const float *)d_data,
+                           g_hf.M.as<float>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
+        hipLaunchKernelGGL(ahfilt_apply_kernel<float>, grid2, dim3(256), 0, ctx->stream, (float *)d_data,
+                           (const float *)g_hf.M.as<float>(), d_scale, snum, tnum);
+    } else {
+        hipLaunchKernelGGL(ahfilt_rowmean_kernel<double>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream,
+                           (const double *)d_data, g_hf.M.as<double>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
+        hipLaunchKernelGGL(ahfilt_apply_kernel<double>, grid2, dim3(256), 0, ctx->stream, (double *)d_data,
+                           (const double *)g_hf.M.as<double>(), d_scale, snum, tnum);
+    }
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return impdar_ctx_mark_produced(ctx);
+}
+
+// ---- host-buffer forms: upload, run, download ------------------------------------------------------------
+
+static int hf_stage_in(impdar_ctx *ctx, const void *host, size_t bytes)
+{
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    hf_bind(ctx);
+    IMPDAR_HIP_CHECK(g_hf.data.ensure(bytes));
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(g_hf.data.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_hfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, int lo, int hi,
+                            const double *scale)
+{
+    HFILT_LOCK();
+    IMPDAR_ARG_CHECK(ctx && data && scale, "impdar_hfilt: null argument");
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfilt: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
+    IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
+    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
+    int rc = hf_stage_in(ctx, data, bytes);
+    if (rc) return rc;
+    rc = impdar_hfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
+    return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
+}
+
+extern "C" int impdar_ahfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                             const double *scale)
+{
+    HFILT_LOCK();
+    IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_ahfilt: null argument");
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_ahfilt: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum > 12, "The length of the input vector x must be greater than padlen, which is %d.", 12);
+    IMPDAR_ARG_CHECK(tnum >= 1, "impdar_ahfilt: empty radargram");
+    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
+    int rc = hf_stage_in(ctx, data, bytes);
+    if (rc) return rc;
+    rc = impdar_ahfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
+    return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
+}

@@ -1,10 +1,64 @@
 """``RadarData.migrate``: the string dispatch into the migration library
 (reference ``src/impdar/lib/RadarData/_RadarDataFiltering.py:590-637``: same
 mtype names, per-mtype keyword forwarding, defaults, ValueError for unknown
-names, ``flags.mig`` recorded afterwards), and ``RadarData.vertical_band_pass``
-(``:469-549``), the filter an impproc chain runs in front of a migration."""
+names, ``flags.mig`` recorded afterwards), ``RadarData.vertical_band_pass``
+(``:469-549``) and the horizontal filters ``hfilt`` / ``horizontalfilt`` / ``adaptivehfilt`` (``:19-135``,
+``:443-466``), the filters an impproc chain runs in front of a migration."""
+import numpy as np
+
 from .. import migrationlib
+from ... import hfilt as _hf
 from ... import preproc
+
+
+def _shape(self):
+    dev = getattr(self, '_dev', None)
+    return dev.shape if dev is not None else np.shape(self.data)
+
+
+def adaptivehfilt(self, window_size, *args, **kwargs):
+    """Subtract from every trace the mean of the ``window_size`` traces around it, smoothed vertically
+    (``filtfilt([.25] * 4, 1, .)``) and tapered with travel time; the reference's windows, including their
+    edge branches and empty windows (NaN traces).  The filtering runs on the MI355X whatever the window."""
+    print('Adaptive filtering')
+    snum, tnum = _shape(self)
+    lo, hi = _hf.ahfilt_windows(tnum, window_size)
+    scale = _hf.taper(self.travel_time)
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        _hf.ahfilt_dev(dev, lo, hi, scale)
+    else:
+        self.data = _hf.ahfilt_host(self.data, lo, hi, scale)
+    print('Adaptive filtering complete')
+    self.flags.hfilt[0] = 1
+    self.flags.hfilt[1] = 4
+
+
+def horizontalfilt(self, ntr1, ntr2, *args, **kwargs):
+    """Subtract the tapered mean of traces ``ntr1`` to ``ntr2`` (clamped as the reference clamps them) from
+    every trace, in the data's own dtype."""
+    snum, tnum = _shape(self)
+    htr1, htrn = _hf.hfilt_bounds(ntr1, ntr2, tnum)
+    print('Subtracting mean trace found between {:d} and {:d}'.format(htr1, htrn))
+    scale = _hf.taper(self.travel_time)
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        _hf.hfilt_dev(dev, htr1, htrn, scale)
+    else:
+        self.data = _hf.hfilt_host(self.data, htr1, htrn, scale)
+    print('Horizontal filter complete.')
+    self.flags.hfilt = np.ones((2,))
+
+
+def hfilt(self, ftype='hfilt', bounds=None, window_size=None):
+    """Horizontally filter the data: ``ftype`` 'hfilt' (``bounds`` = (first, last) trace of the mean) or
+    'adaptive' (``window_size`` traces in the moving mean)."""
+    if ftype == 'hfilt':
+        self.horizontalfilt(bounds[0], bounds[1])
+    elif ftype == 'adaptive':
+        self.adaptivehfilt(window_size=window_size)
+    else:
+        raise ValueError('Unrecognized filter type')
 
 
 def vertical_band_pass(self, low, high, order=5, filttype='butter', cheb_rp=5, fir_window='hamming',

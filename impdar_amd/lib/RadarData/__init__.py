@@ -17,6 +17,7 @@ import numpy as np
 from ..ImpdarError import ImpdarError
 from ..RadarFlags import RadarFlags
 from ._RadarDataFiltering import migrate as _migrate, vertical_band_pass as _vertical_band_pass
+from ._RadarDataFiltering import adaptivehfilt as _adaptivehfilt, hfilt as _hfilt, horizontalfilt as _horizontalfilt
 from ._RadarDataProcessing import constant_space as _constant_space
 from ... import resident as _resident
 
@@ -31,6 +32,9 @@ class RadarData(object):
 
     migrate = _migrate
     vertical_band_pass = _vertical_band_pass
+    hfilt = _hfilt
+    horizontalfilt = _horizontalfilt
+    adaptivehfilt = _adaptivehfilt
     constant_space = _constant_space
     to_device = _resident.to_device
     from_device = _resident.from_device

@@ -4,11 +4,13 @@ Mirrors the part of the reference's ``src/impdar/lib/process.py`` that leads up 
 reference's order (``:72-197``): ``vbp=(low, high)`` -> ``dat.vertical_band_pass`` (``:151-154``),
 ``interp=(spacing, gps_fn)`` -> ``gpslib.interp`` = ``dat.constant_space`` when no GPS file is given
 (``:178-180``), ``migrate=X`` -> ``dat.migrate(mtype='stolt')`` whatever ``X`` is (``:190-193`` -- the string
-given on the command line is ignored by the reference, and so it is here).  When more than one of the steps
-is requested on a float radargram it is uploaded once and stays in HBM until the last step is done.
+given on the command line is ignored by the reference, and so it is here), and ``ahfilt=W`` ->
+``dat.hfilt(ftype='adaptive', window_size=W)`` after the band pass (``:160-162``).  When more than one of the
+steps is requested on a float radargram it is uploaded once and stays in HBM until the last step is done.
 ``process_and_exit`` loads, processes and saves with the reference's file naming (``:30-70``, ``:274-295``).
-The other steps of that driver (crop, nmo, horizontal filters, restack, denoise, reverse) are out of scope
-and rejected.
+The other steps of that driver (crop, nmo, the ``hfilt=(first, last)`` mean-trace filter, restack, denoise,
+reverse) are rejected; ``RadarData.hfilt(ftype='hfilt')`` runs on its own, but accepting it here would change
+what ``process`` has always answered to it.
 """
 import os
 
@@ -16,11 +18,24 @@ import numpy as np
 
 from .load import load
 
-_OUT_OF_SCOPE = ('rev', 'hfilt', 'ahfilt', 'nmo', 'crop', 'hcrop', 'restack', 'denoise')
+_OUT_OF_SCOPE = ('rev', 'hfilt', 'nmo', 'crop', 'hcrop', 'restack', 'denoise')
 
 
-def process(RadarDataList, interp=None, vbp=None, migrate=None, **kwargs):
-    """Returns True if something was done (reference ``process.py:72-197``)."""
+def _window(ahfilt):
+    """``-ahfilt W`` arrives from argparse as a 1-element list (``nargs=1``); the reference hands that list on
+    to ``window_size // 2`` and fails.  An int or a 1-element list is accepted here."""
+    if isinstance(ahfilt, (list, tuple, np.ndarray)):
+        if len(ahfilt) != 1:
+            raise ValueError('ahfilt must be one window size (number of traces)')
+        ahfilt = ahfilt[0]
+    if isinstance(ahfilt, (bool, np.bool_)) or int(ahfilt) != ahfilt:
+        raise TypeError('ahfilt must be an integer number of traces')
+    return int(ahfilt)
+
+
+def process(RadarDataList, interp=None, vbp=None, ahfilt=None, migrate=None, **kwargs):
+    """Returns True if something was done (reference ``process.py:72-197``).  ``hfilt=(first, last)`` stays
+    rejected (run ``RadarData.hfilt`` or ``impproc hfilt`` for it)."""
     for name in _OUT_OF_SCOPE:
         if kwargs.get(name) not in (None, False):
             raise NotImplementedError('processing step %r is not part of the MI355X migration engine; '
@@ -37,7 +52,11 @@ def process(RadarDataList, interp=None, vbp=None, migrate=None, **kwargs):
         if interp[1] is not None:
             raise NotImplementedError('kinematic GPS control (a gps filename for interp) is not part of the '
                                       'MI355X migration engine')
-    steps = sum(x is not None for x in (vbp, interp, migrate))
+    if ahfilt is False or (isinstance(ahfilt, (int, np.integer)) and ahfilt == 0):
+        ahfilt = None                 # the reference's `if ahfilt:`
+    if ahfilt is not None:
+        ahfilt = _window(ahfilt)
+    steps = sum(x is not None for x in (vbp, ahfilt, interp, migrate))
     if steps == 0:
         return False
     for dat in RadarDataList:
@@ -47,6 +66,8 @@ def process(RadarDataList, interp=None, vbp=None, migrate=None, **kwargs):
         try:
             if vbp is not None:
                 dat.vertical_band_pass(*vbp)
+            if ahfilt is not None:
+                dat.hfilt(ftype='adaptive', window_size=ahfilt)
             if interp is not None:
                 dat.constant_space(float(interp[0]))
             if migrate is not None:

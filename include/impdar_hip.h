@@ -276,6 +276,27 @@ int impdar_trace_lerp_dev(impdar_ctx *ctx, const void *d_data, int dtype, int sn
                           const int *lo, const int *hi, const double *den, const double *t,
                           int n_new, double *d_out);
 
+/* impdar_hfilt: RadarData.horizontalfilt (_RadarDataFiltering.py:93-135),
+ * in place: row t loses (T)((T)mean(data[t, lo:hi]) * scale[t]) in the
+ * data's own arithmetic (T = float32 or float64; the mean is summed in
+ * fp64).  lo/hi are the clamped trace bounds, 0 <= lo < hi <= tnum; scale:
+ * snum host doubles (the taper exp(-tt*0.05) / exp(-tt[0]*0.05)).
+ * impdar_ahfilt: RadarData.adaptivehfilt (:19-90), in place: trace i loses
+ * scale[t] * filtfilt([.25]*4, 1, mean(data[:, lo[i]:hi[i]], -1)), the
+ * difference taken in fp64 and stored in the data's dtype; the mean of an
+ * empty window (lo[i] == hi[i]) is NaN.  lo, hi: tnum host ints with
+ * 0 <= lo[i] <= hi[i] <= tnum; scale: snum host doubles.  Fails with
+ * scipy's message when snum <= 12 (filtfilt's padlen).  Run time does not
+ * depend on the window sizes. */
+int impdar_hfilt(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tnum,
+                 int lo, int hi, const double *scale);
+int impdar_hfilt_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum,
+                     int lo, int hi, const double *scale);
+int impdar_ahfilt(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tnum,
+                  const int *lo, const int *hi, const double *scale);
+int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum,
+                      const int *lo, const int *hi, const double *scale);
+
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
 
