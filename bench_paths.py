@@ -4,8 +4,8 @@ BASELINE config 2 (4096x4096 float32), phase-shift at config 5 (8192x8192,
 constant v and 1-D v(z)), the v(x,z) finite-difference branch (256x512) and the band-pass / re-spacing steps in front of a
 migration at config-3 size (4096x10000 float32, resident in HBM, plus the
 three-step chain with and without residency), the horizontal filters (hfilt, adaptive
-hfilt at windows 10 and 1000) at the same size, resident, each through the product path on
-one MI355X.
+hfilt at windows 10 and 1000) and denoise (Wiener and median at several windows) at the same size, resident,
+each through the product path on one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
 ``cpu_baseline``: the NumPy oracle (a port of the reference's algorithm in
@@ -284,6 +284,65 @@ def main():
             hline("ahfilt window %d (adaptive), resident" % window, ms, 5 * snum * tnum * 4,
                   "two passes: windowed means from fp64 prefix rows (8 B/element more, largely cache-resident), "
                   "then the 7-tap stencil, taper and subtraction", cb)
+        d_x.free()
+
+    if 'denoise' not in args.skip:
+        # Wiener and median denoise at the chain's size, float32 resident: device time per call
+        from impdar_amd import denoise as dn
+        snum, tnum = (int(v) for v in args.chain.split('x'))
+        ctx, lib = _hip.context(), _hip.load()
+        drng = np.random.default_rng(6)
+        x = drng.standard_normal((snum, tnum)).astype(np.float32)
+        x[40:60] += 1000.0
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+
+        def ddev_ms(fn, reps=5):
+            fn().free()
+            lib.impdar_ctx_sync(ctx)
+            outs = []
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                outs.append(fn())
+            lib.impdar_ctx_sync(ctx)
+            ms = (time.perf_counter() - t0) / reps * 1e3
+            for o in outs:
+                o.free()
+            return ms
+
+        def dline(path, ms, algo, bound, note, cb):
+            rl = {"bound": bound, "note": note}
+            if algo:
+                rl.update({"achieved": algo / ms / 1e6, "peak": 8000.0, "unit": "GB/s", "frac": algo / ms / 1e6 / 8000.0})
+            print(json.dumps({"path": path, "config": "%dx%d float32" % (snum, tnum), "device_ms": ms,
+                              "traces_per_s": tnum / ms * 1e3, "algorithmic_bytes": algo, "roofline": rl,
+                              "cpu_baseline": cb}), flush=True)
+
+        def cpu_line(fn, what):
+            if args.no_cpu:
+                return None
+            m = min(tnum, 200)
+            t0 = time.perf_counter()
+            fn(x[:, :m])
+            return {"seconds": (time.perf_counter() - t0) * tnum / m, "kind": "reference", "cores": 1,
+                    "sample": "%s on %d of %d traces, scaled to all" % (what, m, tnum)}
+
+        from scipy.ndimage import median_filter
+        from scipy.signal import wiener
+        for win in ((1, 10), (5, 5), (21, 201)):
+            ms = ddev_ms(lambda: dn.wiener_dev(d_x, win[0], win[1])[0])
+            cb = cpu_line(lambda a: wiener(a, mysize=win), 'scipy.signal.wiener')
+            # floor: pass 1 reads x, pass 2 reads x and writes float64 (16 B); the kept statistics add 20 B
+            # written and about 40 B read per element
+            dline("denoise wiener %dx%d, noise estimated, resident" % win, ms, 16 * snum * tnum, "hbm",
+                  "byte floor of both passes (4 + 4 + 8 B/element); the fp64 window statistics kept between the "
+                  "passes add about 60 B/element of traffic", cb)
+        for win in ((1, 10), (5, 5), (3, 21), (11, 101)):
+            small = win[0] * win[1] <= 64
+            ms = ddev_ms(lambda: dn.median_dev(d_x, win[0], win[1]), reps=5 if small else 2)
+            cb = cpu_line(lambda a: median_filter(a, size=win), 'scipy.ndimage.median_filter')
+            dline("denoise median %dx%d, resident" % win, ms, 8 * snum * tnum, "compute",
+                  ("register sorting network over the window gathered from an LDS tile" if small else
+                   "radix select, 8 passes of N = %d keys per output" % (win[0] * win[1])), cb)
         d_x.free()
 
 

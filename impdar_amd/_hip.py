@@ -86,6 +86,10 @@ SIGNATURES = {
     'impdar_hfilt_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _dp]),
     'impdar_ahfilt': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp]),
     'impdar_ahfilt_dev': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp]),
+    'impdar_wiener': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _i, _dp, _dp]),
+    'impdar_wiener_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _i, _p, _dp]),
+    'impdar_median': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    'impdar_median_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_comm_unique_id': (_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),

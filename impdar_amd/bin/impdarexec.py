@@ -1,7 +1,7 @@
 #! /usr/bin/env python
-"""``impdar proc [-vbp LOW HIGH] [-ahfilt WIN] [-interp SPACING GPS_FN] [-migrate X] files`` on the MI355X engine
-(reference ``src/impdar/bin/impdarexec.py:47-119,175-182`` -> ``process.process_and_exit``).  Only the ``proc``
-sub-command with these four steps is provided."""
+"""``impdar proc [-vbp LOW HIGH] [-ahfilt WIN] [-denoise V H] [-interp SPACING GPS_FN] [-migrate X] files`` on the
+MI355X engine (reference ``src/impdar/bin/impdarexec.py:47-119,175-182`` -> ``process.process_and_exit``).  Only
+the ``proc`` sub-command with these five steps is provided."""
 import argparse
 import sys
 
@@ -16,6 +16,8 @@ def _get_args():
     parser_proc.add_argument('-vbp', nargs=2, type=float,
                              help='Bandpass the data vertically at low (MHz) and high (MHz)')
     parser_proc.add_argument('-ahfilt', nargs=1, type=int, help='Adaptive horizontal filtering')
+    parser_proc.add_argument('-denoise', nargs=2, type=int,
+                             help='Denoising filter vertical and horizontal (scipy wiener for now)')
     parser_proc.add_argument('-interp', nargs=2, type=str,
                              help='Reinterpolate GPS. First argument is the new spacing, in meters. Second argument '
                                   'is the filename with new GPS data (not supported by this engine)')

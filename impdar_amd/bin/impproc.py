@@ -1,13 +1,15 @@
 #! /usr/bin/env python
-"""``impproc migrate`` (and the steps usually run in front of it, ``vbp``, ``hfilt``, ``ahfilt`` and ``interp``)
-on the MI355X engine.
+"""``impproc migrate`` (and the steps usually run in front of it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise`` and
+``interp``) on the MI355X engine.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
-hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, interp ``:222-251``, ``main`` ``:378-415``, ``hfilt``
-``:418-420``, ``ahfilt`` ``:423-425``, ``mig`` ``:508-519``, ``vbp`` ``:438-440``, ``interp`` ``:483-491``):
-same options, types and defaults, same output naming
-(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|interp>.mat``, ``-o`` file or folder).  As in the
-reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default window of 1000 traces.
+hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, interp ``:222-251``, denoise ``:275-293``, ``main``
+``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig`` ``:508-519``, ``vbp`` ``:438-440``,
+``interp`` ``:483-491``, ``denoise`` ``:503-505``): same options, types and defaults, same output naming
+(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|interp|denoise>.mat``, ``-o`` file or folder).  As in
+the reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default window of 1000
+traces.  ``impproc denoise V H`` accepts ``--filt weiner|wiener|median`` (default ``weiner``, the reference's
+spelling, which runs the Wiener filter; the reference's own default fails in its ``RadarData.denoise``).
 The reference's other processing sub-commands are out of scope.
 
     python -m impdar_amd.bin.impproc migrate --mtype kirch line1_raw.mat
@@ -56,6 +58,14 @@ def _get_args():
     parser_ahfilt.set_defaults(func=ahfilt, name='ahfilt')
     parser_ahfilt.add_argument('win', type=int, help='Number of traces to include in the moving average')
     _add_def_args(parser_ahfilt)
+
+    parser_denoise = subparsers.add_parser('denoise', help='Denoising filter for the data image')
+    parser_denoise.set_defaults(func=denoise, name='denoise')
+    parser_denoise.add_argument('vert_win', type=int, help='Size of filtering window in vertical (number of samples)')
+    parser_denoise.add_argument('hor_win', type=int, help='Size of filtering window in horizontal (number of traces)')
+    parser_denoise.add_argument('--filt', type=str, choices=['weiner', 'wiener', 'median'], default='weiner',
+                                help='Filter type (Wiener or median with specified dimensions)')
+    _add_def_args(parser_denoise)
 
     parser_vbp = subparsers.add_parser('vbp', help='Vertically bandpass the data')
     parser_vbp.set_defaults(func=vbp, name='bandpassed')
@@ -130,6 +140,11 @@ def hfilt(dat, start_trace=0, end_trace=-1, **kwargs):
 def ahfilt(dat, window_size=1000, **kwargs):
     """Adaptive horizontal filter.  The parsed ``win`` lands in ``kwargs``, as in the reference."""
     dat.hfilt(ftype='adaptive', window_size=window_size)
+
+
+def denoise(dat, vert_win=1, hor_win=10, noise=None, filt='wiener', **kwargs):
+    """Despeckle.  The reference's CLI spelling 'weiner' (its default) runs the Wiener filter."""
+    dat.denoise(vert_win=vert_win, hor_win=hor_win, noise=noise, ftype='wiener' if filt == 'weiner' else filt)
 
 
 def vbp(dat, low_MHz=1, high_MHz=10000, **kwargs):

@@ -2,11 +2,12 @@
 (reference ``src/impdar/lib/RadarData/_RadarDataFiltering.py:590-637``: same
 mtype names, per-mtype keyword forwarding, defaults, ValueError for unknown
 names, ``flags.mig`` recorded afterwards), ``RadarData.vertical_band_pass``
-(``:469-549``) and the horizontal filters ``hfilt`` / ``horizontalfilt`` / ``adaptivehfilt`` (``:19-135``,
-``:443-466``), the filters an impproc chain runs in front of a migration."""
+(``:469-549``), the horizontal filters ``hfilt`` / ``horizontalfilt`` / ``adaptivehfilt`` (``:19-135``,
+``:443-466``) and ``denoise`` (``:552-587``), the filters an impproc chain runs in front of a migration."""
 import numpy as np
 
 from .. import migrationlib
+from ... import denoise as _dn
 from ... import hfilt as _hf
 from ... import preproc
 
@@ -59,6 +60,41 @@ def hfilt(self, ftype='hfilt', bounds=None, window_size=None):
         self.adaptivehfilt(window_size=window_size)
     else:
         raise ValueError('Unrecognized filter type')
+
+
+def denoise(self, vert_win=1, hor_win=10, noise=None, ftype='wiener'):
+    """Denoising filter over a (``vert_win`` samples, ``hor_win`` traces) window, on the MI355X.
+
+    ``ftype='wiener'``: ``scipy.signal.wiener(data, mysize=(vert_win, hor_win), noise=noise)``; the data becomes
+    float64, as in the reference (a resident float32 radargram becomes a resident float64 one).  ``noise`` is the
+    noise power, by default the mean of the local variance.  ``ftype='median'``:
+    ``scipy.ndimage.median_filter(data, size=(vert_win, hor_win))``, in the data's own dtype.  Any other ftype
+    raises ``ValueError`` as the reference does.
+
+    Deliberate differences from the reference: integer data is widened to float64 before it is
+    squared (the reference's int16 squares wrap); with ``noise=None`` a flat window gives its mean instead of
+    raising, and ``ValueError('Could not compute variance, specify noise for denoise')`` is raised only when
+    every window is flat (estimated noise exactly 0); window sizes below 1 raise ``ValueError``; with ``noise``
+    given, an output is NaN exactly when its window holds a non-finite value (with ``noise=None`` every output
+    is, as in the reference).
+    """
+    if ftype not in ('wiener', 'median'):
+        raise ValueError(_dn.FTYPE_MESSAGE)
+    dev = getattr(self, '_dev', None)
+    if ftype == 'wiener':
+        if dev is not None:
+            new_dev, _ = _dn.wiener_dev(dev, vert_win, hor_win, noise=noise)
+        else:
+            self.data, _ = _dn.wiener_host(self.data, vert_win, hor_win, noise=noise)
+    else:
+        if dev is not None:
+            new_dev = _dn.median_dev(dev, vert_win, hor_win)
+        else:
+            self.data = _dn.median_host(self.data, vert_win, hor_win)
+    if dev is not None:
+        dev.free()
+        self._dev = new_dev
+        self.data = None
 
 
 def vertical_band_pass(self, low, high, order=5, filttype='butter', cheb_rp=5, fir_window='hamming',

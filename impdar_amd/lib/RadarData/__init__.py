@@ -18,6 +18,7 @@ from ..ImpdarError import ImpdarError
 from ..RadarFlags import RadarFlags
 from ._RadarDataFiltering import migrate as _migrate, vertical_band_pass as _vertical_band_pass
 from ._RadarDataFiltering import adaptivehfilt as _adaptivehfilt, hfilt as _hfilt, horizontalfilt as _horizontalfilt
+from ._RadarDataFiltering import denoise as _denoise
 from ._RadarDataProcessing import constant_space as _constant_space
 from ... import resident as _resident
 
@@ -35,6 +36,7 @@ class RadarData(object):
     hfilt = _hfilt
     horizontalfilt = _horizontalfilt
     adaptivehfilt = _adaptivehfilt
+    denoise = _denoise
     constant_space = _constant_space
     to_device = _resident.to_device
     from_device = _resident.from_device

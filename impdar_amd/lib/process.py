@@ -5,11 +5,13 @@ reference's order (``:72-197``): ``vbp=(low, high)`` -> ``dat.vertical_band_pass
 ``interp=(spacing, gps_fn)`` -> ``gpslib.interp`` = ``dat.constant_space`` when no GPS file is given
 (``:178-180``), ``migrate=X`` -> ``dat.migrate(mtype='stolt')`` whatever ``X`` is (``:190-193`` -- the string
 given on the command line is ignored by the reference, and so it is here), and ``ahfilt=W`` ->
-``dat.hfilt(ftype='adaptive', window_size=W)`` after the band pass (``:160-162``).  When more than one of the
-steps is requested on a float radargram it is uploaded once and stays in HBM until the last step is done.
+``dat.hfilt(ftype='adaptive', window_size=W)`` after the band pass (``:160-162``), and ``denoise=(V, H)`` ->
+``dat.denoise(V, H)`` (Wiener) after the horizontal filter and before the re-spacing (``:121-126``, ``:175-178``).
+When more than one of the steps is requested on a float radargram it is uploaded once and stays in HBM until the
+last step is done.
 ``process_and_exit`` loads, processes and saves with the reference's file naming (``:30-70``, ``:274-295``).
-The other steps of that driver (crop, nmo, the ``hfilt=(first, last)`` mean-trace filter, restack, denoise,
-reverse) are rejected; ``RadarData.hfilt(ftype='hfilt')`` runs on its own, but accepting it here would change
+The other steps of that driver (crop, nmo, the ``hfilt=(first, last)`` mean-trace filter, restack, reverse)
+are rejected; ``RadarData.hfilt(ftype='hfilt')`` runs on its own, but accepting it here would change
 what ``process`` has always answered to it.
 """
 import os
@@ -18,7 +20,7 @@ import numpy as np
 
 from .load import load
 
-_OUT_OF_SCOPE = ('rev', 'hfilt', 'nmo', 'crop', 'hcrop', 'restack', 'denoise')
+_OUT_OF_SCOPE = ('rev', 'hfilt', 'nmo', 'crop', 'hcrop', 'restack')
 
 
 def _window(ahfilt):
@@ -33,13 +35,20 @@ def _window(ahfilt):
     return int(ahfilt)
 
 
-def process(RadarDataList, interp=None, vbp=None, ahfilt=None, migrate=None, **kwargs):
+def process(RadarDataList, interp=None, vbp=None, ahfilt=None, denoise=None, migrate=None, **kwargs):
     """Returns True if something was done (reference ``process.py:72-197``).  ``hfilt=(first, last)`` stays
     rejected (run ``RadarData.hfilt`` or ``impproc hfilt`` for it)."""
     for name in _OUT_OF_SCOPE:
         if kwargs.get(name) not in (None, False):
             raise NotImplementedError('processing step %r is not part of the MI355X migration engine; '
                                       'run it with the reference ImpDAR first' % name)
+    if denoise is not None:
+        try:
+            ok = type(denoise[0]) is int and type(denoise[1]) is int     # the reference's check (:121-126)
+        except (TypeError, IndexError):
+            ok = False
+        if not ok:
+            raise ValueError('Denoise must be two integers giving vertical and horizontal window sizes')
     if vbp is not None:
         if not hasattr(vbp, '__iter__'):
             raise TypeError('vbp must be a tuple with first two elements [low] [high] MHz')
@@ -56,7 +65,7 @@ def process(RadarDataList, interp=None, vbp=None, ahfilt=None, migrate=None, **k
         ahfilt = None                 # the reference's `if ahfilt:`
     if ahfilt is not None:
         ahfilt = _window(ahfilt)
-    steps = sum(x is not None for x in (vbp, ahfilt, interp, migrate))
+    steps = sum(x is not None for x in (vbp, ahfilt, denoise, interp, migrate))
     if steps == 0:
         return False
     for dat in RadarDataList:
@@ -68,6 +77,8 @@ def process(RadarDataList, interp=None, vbp=None, ahfilt=None, migrate=None, **k
                 dat.vertical_band_pass(*vbp)
             if ahfilt is not None:
                 dat.hfilt(ftype='adaptive', window_size=ahfilt)
+            if denoise is not None:
+                dat.denoise(*denoise)
             if interp is not None:
                 dat.constant_space(float(interp[0]))
             if migrate is not None:

@@ -297,6 +297,31 @@ int impdar_ahfilt(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tn
 int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum,
                       const int *lo, const int *hi, const double *scale);
 
+/* impdar_wiener: RadarData.denoise(ftype='wiener') (_RadarDataFiltering.py:552-587) =
+ * scipy.signal.wiener(data, mysize=(vert_win, hor_win), noise): box means and
+ * variances over the window (zero padding, always divided by the full
+ * vert_win * hor_win; output i covers inputs i - w/2 .. i + (w-1)/2), noise =
+ * mean(lVar) when noise_given == 0, out = lVar < noise ? lMean
+ * : (x - lMean) * (1 - noise / lVar) + lMean.  Input float32 or float64 (float32
+ * squares rounded to float32, as the reference squares in the data's dtype);
+ * output: snum x tnum float64 (host buffer / device array).  *noise_used (may be
+ * null) receives the noise applied.  An output whose window holds a non-finite
+ * value is NaN (with an estimated noise every output is).  Fails with
+ * IMPDAR_ERR_ARG ("Could not compute variance, specify noise for denoise") when
+ * the estimated noise is exactly 0.  Bitwise repeatable; run time does not
+ * depend on the window size.
+ * impdar_median: scipy.ndimage.median_filter(data, size=(vert_win, hor_win)),
+ * mode 'reflect', rank N/2 of N = vert_win * hor_win, into a separate buffer of
+ * the input's dtype (float32 or float64).  Windows >= 1 in both axes, any size. */
+int impdar_wiener(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int vert_win, int hor_win,
+                  double noise, int noise_given, double *out, double *noise_used);
+int impdar_wiener_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int vert_win, int hor_win,
+                      double noise, int noise_given, double *d_out, double *noise_used);
+int impdar_median(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int vert_win, int hor_win,
+                  void *out);
+int impdar_median_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int vert_win, int hor_win,
+                      void *d_out);
+
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
 
