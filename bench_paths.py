@@ -4,7 +4,8 @@ BASELINE config 2 (4096x4096 float32), phase-shift at config 5 (8192x8192,
 constant v and 1-D v(z)), the v(x,z) finite-difference branch (256x512) and the band-pass / re-spacing steps in front of a
 migration at config-3 size (4096x10000 float32, resident in HBM, plus the
 three-step chain with and without residency), the horizontal filters (hfilt, adaptive
-hfilt at windows 10 and 1000) and denoise (Wiener and median at several windows) at the same size, resident,
+hfilt at windows 10 and 1000), denoise (Wiener and median at several windows) and the horizontal frequency
+filters (hbp, lp, hp; float64, as constant_space hands them on) at the same size, resident,
 each through the product path on one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
@@ -343,6 +344,54 @@ def main():
             dline("denoise median %dx%d, resident" % win, ms, 8 * snum * tnum, "compute",
                   ("register sorting network over the window gathered from an LDS tile" if small else
                    "radix select, 8 passes of N = %d keys per output" % (win[0] * win[1])), cb)
+        d_x.free()
+
+
+    if 'hpass' not in args.skip:
+        # horizontal band pass / low pass / high pass at the chain's size, float64 resident (what constant_space
+        # hands on): device time per call
+        from impdar_amd import hpass as hp
+        snum, tnum = (int(v) for v in args.chain.split('x'))
+        ctx, lib = _hip.context(), _hip.load()
+        prng = np.random.default_rng(7)
+        x = prng.standard_normal((snum, tnum))
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+
+        def pdev_ms(fn, reps=10):
+            fn()
+            lib.impdar_ctx_sync(ctx)
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            lib.impdar_ctx_sync(ctx)
+            return (time.perf_counter() - t0) / reps * 1e3
+
+        with contextlib.redirect_stdout(io.StringIO()):
+            cases = [("horizontal_band_pass 5-100 m (butter 5 band, 11 coefficients)", hp.band_pass_design(5., 100., 1.0, tnum)),
+                     ("lowpass 20 m (butter 3, 4 coefficients)", hp.pass_design('low', 20., 1.0, tnum, 1e-8)),
+                     ("highpass 20 m (butter 5, 6 coefficients)", hp.pass_design('high', 20., 1.0, tnum, 1e-8))]
+        for label, spec in cases:
+            ms = pdev_ms(lambda: hp.filtfilt_dev(d_x, spec))
+            pad = 3 * len(spec[0])
+            steps = 2 * tnum + 3 * pad
+            # read x, write and read the fp64 forward pass (tnum + 2 pad per row), write out: about 32 B/element
+            algo = snum * (tnum * 8 + 2 * (tnum + 2 * pad) * 8 + tnum * 8)
+            cb = None
+            if not args.no_cpu:
+                from scipy.signal import filtfilt
+                m = min(snum, 64)
+                t0 = time.perf_counter()
+                filtfilt(spec[0], spec[1], x[:m], axis=1)
+                cb = {"seconds": (time.perf_counter() - t0) * snum / m, "kind": "reference", "cores": 1,
+                      "sample": "scipy.signal.filtfilt (what the reference calls) on %d of %d rows, scaled to all" % (m, snum)}
+            print(json.dumps({"path": label + ", resident", "config": "%dx%d float64" % (snum, tnum), "device_ms": ms,
+                              "traces_per_s": tnum / ms * 1e3, "algorithmic_bytes": algo, "ns_per_step": ms * 1e6 / steps,
+                              "roofline": {"bound": "serial recurrence", "achieved": algo / ms / 1e6, "peak": 8000.0,
+                                           "unit": "GB/s", "frac": algo / ms / 1e6 / 8000.0,
+                                           "note": "serial fp64 recurrence along each row, %d dependent steps per row; "
+                                                   "%d rows: bound by the step latency of one wavefront, not HBM"
+                                                   % (steps, snum)},
+                              "cpu_baseline": cb}), flush=True)
         d_x.free()
 
 

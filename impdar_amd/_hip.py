@@ -90,6 +90,8 @@ SIGNATURES = {
     'impdar_wiener_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _i, _p, _dp]),
     'impdar_median': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_median_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    'impdar_hfiltfilt': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _i, _dp, _dp]),
+    'impdar_hfiltfilt_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _i, _dp, _p]),
     'impdar_comm_unique_id': (_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),

@@ -1,14 +1,15 @@
 #! /usr/bin/env python
-"""``impproc migrate`` (and the steps usually run in front of it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise`` and
-``interp``) on the MI355X engine.
+"""``impproc migrate`` (and the steps usually run in front of it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise``,
+``interp``, ``hbp`` and ``lp``) on the MI355X engine.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
-hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, interp ``:222-251``, denoise ``:275-293``, ``main``
-``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig`` ``:508-519``, ``vbp`` ``:438-440``,
-``interp`` ``:483-491``, ``denoise`` ``:503-505``): same options, types and defaults, same output naming
-(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|interp|denoise>.mat``, ``-o`` file or folder).  As in
-the reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default window of 1000
-traces.  ``impproc denoise V H`` accepts ``--filt weiner|wiener|median`` (default ``weiner``, the reference's
+hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
+denoise ``:275-293``, ``main`` ``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig``
+``:508-519``, ``vbp`` ``:438-440``, ``hbp`` ``:443-445``, ``lp`` ``:448-450``, ``interp`` ``:483-491``,
+``denoise`` ``:503-505``): same options, types and defaults, same output naming
+(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|denoise>.mat``, ``-o`` file or
+folder).  As in the reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default
+window of 1000 traces.  ``impproc denoise V H`` accepts ``--filt weiner|wiener|median`` (default ``weiner``, the reference's
 spelling, which runs the Wiener filter; the reference's own default fails in its ``RadarData.denoise``).
 The reference's other processing sub-commands are out of scope.
 
@@ -72,6 +73,17 @@ def _get_args():
     parser_vbp.add_argument('low_MHz', type=float, help='Lowest frequency passed (in MHz)')
     parser_vbp.add_argument('high_MHz', type=float, help='Highest frequency passed (in MHz)')
     _add_def_args(parser_vbp)
+
+    parser_hbp = subparsers.add_parser('hbp', help='Horizontally bandpass the data')
+    parser_hbp.set_defaults(func=hbp, name='hbp')
+    parser_hbp.add_argument('low', type=float, help='Lowest frequency passed (in wavelength)')
+    parser_hbp.add_argument('high', type=float, help='Highest frequency passed (in wavelength)')
+    _add_def_args(parser_hbp)
+
+    parser_lp = subparsers.add_parser('lp', help='Horizontally lowpass the data')
+    parser_lp.set_defaults(func=lp, name='lp')
+    parser_lp.add_argument('low', type=float, help='Lowest frequency passed (in wavelength)')
+    _add_def_args(parser_lp)
 
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
@@ -150,6 +162,16 @@ def denoise(dat, vert_win=1, hor_win=10, noise=None, filt='wiener', **kwargs):
 def vbp(dat, low_MHz=1, high_MHz=10000, **kwargs):
     """Vertically bandpass the data."""
     dat.vertical_band_pass(low_MHz, high_MHz)
+
+
+def hbp(dat, low=1, high=10, **kwargs):
+    """Horizontally band pass the data."""
+    dat.horizontal_band_pass(low, high)
+
+
+def lp(dat, low=1, **kwargs):
+    """Low pass filter the data."""
+    dat.lowpass(low)
 
 
 def interp(dats, spacing, gps_fn=None, offset=0.0, minmove=1.0e-2, extrapolate=False, **kwargs):

@@ -3,12 +3,14 @@
 mtype names, per-mtype keyword forwarding, defaults, ValueError for unknown
 names, ``flags.mig`` recorded afterwards), ``RadarData.vertical_band_pass``
 (``:469-549``), the horizontal filters ``hfilt`` / ``horizontalfilt`` / ``adaptivehfilt`` (``:19-135``,
-``:443-466``) and ``denoise`` (``:552-587``), the filters an impproc chain runs in front of a migration."""
+``:443-466``), ``denoise`` (``:552-587``) and the horizontal frequency filters ``horizontal_band_pass`` /
+``highpass`` / ``lowpass`` (``:138-350``), the filters an impproc chain runs in front of a migration."""
 import numpy as np
 
 from .. import migrationlib
 from ... import denoise as _dn
 from ... import hfilt as _hf
+from ... import hpass as _hp
 from ... import preproc
 
 
@@ -95,6 +97,48 @@ def denoise(self, vert_win=1, hor_win=10, noise=None, ftype='wiener'):
         dev.free()
         self._dev = new_dev
         self.data = None
+
+
+def _hpass_apply(self, spec):
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        new_dev = _hp.filtfilt_dev(dev, spec)
+        if new_dev is not dev:
+            dev.free()
+            self._dev = new_dev
+            self.data = None
+    else:
+        self.data = _hp.filtfilt_host(self.data, spec)
+    self.flags.hfilt = np.ones((2,))
+    self.flags.hfilt[1] = 3
+
+
+def horizontal_band_pass(self, low, high):
+    """Band-pass every sample row along the traces between the wavelengths ``low`` and ``high`` (m):
+    ``filtfilt(butter(5, corners, 'bandpass'), data, axis=1)`` on the MI355X, float64 out.  Needs constantly
+    spaced (``constant_space``), not elevation-corrected data; the reference's checks, messages and corner
+    frequencies.  A resident float32 radargram becomes a resident float64 one.  Integer data is widened to
+    float64 before the odd extension (the reference's int16 extension wraps)."""
+    tracespace = _hp.trace_spacing(self.flags)
+    _hpass_apply(self, _hp.band_pass_design(low, high, tracespace, self.tnum))
+    print('Highpass filter complete.')
+
+
+def highpass(self, wavelength):
+    """High pass along the traces for ``wavelength`` (m): ``filtfilt(butter(5, c, 'high'), data)`` with the
+    reference's corner ``c = (100 / nsamp) MHz / (0.5 / dt)``, on the MI355X, float64 out (see
+    :func:`horizontal_band_pass` for the checks, residency and integer data)."""
+    tracespace = _hp.trace_spacing(self.flags)
+    _hpass_apply(self, _hp.pass_design('high', wavelength, tracespace, self.tnum, self.dt))
+    print('Highpass filter complete.')
+
+
+def lowpass(self, wavelength):
+    """Low pass along the traces for ``wavelength`` (m): ``filtfilt(butter(3, c, 'low'), data)``, corner as in
+    :func:`highpass`."""
+    tracespace = _hp.trace_spacing(self.flags)
+    _hpass_apply(self, _hp.pass_design('low', wavelength, tracespace, self.tnum, self.dt))
+    print('Lowpass filter complete.')
 
 
 def vertical_band_pass(self, low, high, order=5, filttype='butter', cheb_rp=5, fir_window='hamming',

@@ -19,6 +19,7 @@ from ..RadarFlags import RadarFlags
 from ._RadarDataFiltering import migrate as _migrate, vertical_band_pass as _vertical_band_pass
 from ._RadarDataFiltering import adaptivehfilt as _adaptivehfilt, hfilt as _hfilt, horizontalfilt as _horizontalfilt
 from ._RadarDataFiltering import denoise as _denoise
+from ._RadarDataFiltering import highpass as _highpass, horizontal_band_pass as _horizontal_band_pass, lowpass as _lowpass
 from ._RadarDataProcessing import constant_space as _constant_space
 from ... import resident as _resident
 
@@ -37,6 +38,9 @@ class RadarData(object):
     horizontalfilt = _horizontalfilt
     adaptivehfilt = _adaptivehfilt
     denoise = _denoise
+    horizontal_band_pass = _horizontal_band_pass
+    highpass = _highpass
+    lowpass = _lowpass
     constant_space = _constant_space
     to_device = _resident.to_device
     from_device = _resident.from_device

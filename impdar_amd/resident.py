@@ -1,10 +1,11 @@
 """Keeping a radargram in HBM across the steps of a processing chain.
 
-``dat.to_device()`` uploads ``dat.data`` once; ``vertical_band_pass``, ``hfilt``, ``denoise``, ``constant_space``
-and ``migrate('kirch' | 'stolt' | 'phsh')`` then work on the resident array through the ``*_dev`` entry points
-of the C ABI (no PCIe traffic between steps), and ``dat.from_device()`` brings the result back.  ``denoise``
-and ``constant_space`` replace the resident array with a new one (Wiener's is float64 whatever the input, as
-the reference's result is).  While resident,
+``dat.to_device()`` uploads ``dat.data`` once; ``vertical_band_pass``, ``hfilt``, ``denoise``, ``constant_space``,
+``horizontal_band_pass`` / ``highpass`` / ``lowpass`` and ``migrate('kirch' | 'stolt' | 'phsh')`` then work on
+the resident array through the ``*_dev`` entry points of the C ABI (no PCIe traffic between steps), and
+``dat.from_device()`` brings the result back.  ``denoise``, ``constant_space`` and the horizontal frequency
+filters may replace the resident array with a new one (their results are float64 whatever the input, as the
+reference's are).  While resident,
 ``dat.data`` is None.  What has no resident form ('tk', the 2-D v(x, z) branch of 'phsh', SeisUnix)
 round-trips through the host.
 """

@@ -322,6 +322,23 @@ int impdar_median(impdar_ctx *ctx, const void *data, int dtype, int snum, int tn
 int impdar_median_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int vert_win, int hor_win,
                       void *d_out);
 
+/* impdar_hfiltfilt: scipy.signal.filtfilt(b, a, data, axis=1) along the trace axis
+ * of a (snum, tnum) radargram: the reference's horizontal_band_pass, highpass and
+ * lowpass (_RadarDataFiltering.py:138-350).  ncoef = len(b) = len(a), 2..17; zi
+ * (ncoef - 1 values) = scipy.signal.lfilter_zi(b, a).  Odd extension by
+ * padlen = 3 * ncoef samples computed in the input's arithmetic, initial state
+ * zi * x0, forward pass, backward pass from zi * y0, all in fp64 in SciPy's
+ * operation order.  Input float32 or float64; output snum x tnum float64 (host
+ * buffer / device array), which may be the input itself when it is float64.  Each
+ * row is filtered on its own (a NaN stays in its row).  Fails with IMPDAR_ERR_ARG
+ * ("The length of the input vector x must be greater than padlen, which is N.")
+ * when tnum <= padlen.  The fp64 forward pass, snum x (tnum + 2 * padlen), is
+ * scratch the context keeps for the next call. */
+int impdar_hfiltfilt(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *b,
+                     const double *a, int ncoef, const double *zi, double *out);
+int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const double *b,
+                         const double *a, int ncoef, const double *zi, double *d_out);
+
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
 
