@@ -67,10 +67,11 @@ def lfilter_zi(b, a):
 
 
 def lfilter_tdf2(b, a, x, z):
-    """Transposed direct form II along axis 0 of x (float64), all traces at once; returns y.  ``z`` is
-    (ncoef-1, tnum) and is updated in place.  Operation order of SciPy's C loop."""
-    b = np.asarray(b, dtype=np.float64) / a[0]
-    a = np.asarray(a, dtype=np.float64) / a[0]
+    """Transposed direct form II along axis 0 of x, all traces at once, in the precision of x (float64, or
+    np.longdouble for conditioning checks); returns y.  ``z`` is (ncoef-1, tnum) and is updated in place.
+    Operation order of SciPy's C loop; the coefficients are normalised by a[0] in float64, as SciPy does."""
+    b = (np.asarray(b, dtype=np.float64) / a[0]).astype(x.dtype)
+    a = (np.asarray(a, dtype=np.float64) / a[0]).astype(x.dtype)
     nc = len(b)
     y = np.empty_like(x)
     for i in range(x.shape[0]):
@@ -83,8 +84,10 @@ def lfilter_tdf2(b, a, x, z):
     return y
 
 
-def filtfilt(b, a, x):
-    """scipy.signal.filtfilt(b, a, x, axis=0) (padtype 'odd', padlen 3*ntaps, method 'pad'); float64 out."""
+def filtfilt(b, a, x, dtype=np.float64):
+    """scipy.signal.filtfilt(b, a, x, axis=0) (padtype 'odd', padlen 3*ntaps, method 'pad'); float64 out.
+    ``dtype=np.longdouble`` runs both passes in that precision from the same odd extension (in the data's
+    dtype) and the same float64 ``lfilter_zi``, and returns that dtype."""
     b = np.atleast_1d(np.asarray(b, dtype=np.float64))
     a = np.atleast_1d(np.asarray(a, dtype=np.float64))
     ntaps = max(len(a), len(b))
@@ -99,8 +102,8 @@ def filtfilt(b, a, x):
     right = 2 * x[-1:] - x[-2:-(edge + 2):-1]
     ext = np.concatenate((left, x, right), axis=0)
     zi = lfilter_zi(b, a)
-    x0 = ext[0].astype(np.float64)
-    y = lfilter_tdf2(b, a, ext.astype(np.float64), zi[:, None] * x0[None, :])
+    x0 = ext[0].astype(dtype)
+    y = lfilter_tdf2(b, a, ext.astype(dtype), zi[:, None] * x0[None, :])
     y0 = y[-1]
     y = lfilter_tdf2(b, a, y[::-1].copy(), zi[:, None] * y0[None, :])
     return y[::-1][edge:-edge]
