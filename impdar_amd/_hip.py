@@ -3,6 +3,7 @@
 There is deliberately no CPU fallback: if the library is missing or no GPU
 is visible the migration entry points raise.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -209,6 +210,19 @@ def dtype_code(dt):
     raise TypeError('device kernels take float32 or float64 data, got %s' % dt)
 
 
+def work_array(data, what, copy):
+    """float32 / float64 C-contiguous (snum, tnum) array for a host-buffer entry point (integers and bools
+    widened to float64).  ``what`` opens the ``TypeError`` for complex data, subject and verb; ``copy`` asks for
+    a fresh array whatever the input, because the C call works in place."""
+    data = np.asarray(data)
+    if data.ndim != 2:
+        raise ValueError('data must be (snum, tnum)')
+    if np.iscomplexobj(data):
+        raise TypeError('%s not supported by the MI355X engine' % what)
+    dtype = data.dtype if data.dtype in (np.float32, np.float64) else np.float64
+    return np.array(data, dtype=dtype, order='C') if copy else np.ascontiguousarray(data, dtype=dtype)
+
+
 class DeviceArray(object):
     """A (rows, cols) row-major array resident in HBM."""
 
@@ -251,3 +265,15 @@ class DeviceArray(object):
             self.free()
         except Exception:
             pass
+
+
+@contextlib.contextmanager
+def new_device_array(ctx, shape, dtype):
+    """A fresh :class:`DeviceArray` for the result of a ``*_dev`` call: freed if the body raises, else the
+    caller's."""
+    d = DeviceArray(ctx, shape, dtype)
+    try:
+        yield d
+    except Exception:
+        d.free()
+        raise

@@ -153,3 +153,39 @@ struct DevBuf {
     }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+
+// What a processing step (preproc.hip, hfilt.hip, denoise.hip, hpass.hip) keeps between calls: its buffers -- `Bufs`,
+// with a release() that frees every one of them -- and the context they belong to.  One set per process and step:
+// entry points of different contexts / threads take turns, each holding lock() from its first line to its return
+// (re-entrant because the host-buffer forms call the resident ones).
+template <class Bufs> struct StepScratch : Bufs {
+    impdar_ctx *owner = nullptr;
+    std::recursive_mutex mu;
+    std::unique_lock<std::recursive_mutex> lock() { return std::unique_lock<std::recursive_mutex>(mu); }
+    // buffers live on the owner's device: a call on another context starts from none
+    void bind(impdar_ctx *ctx)
+    {
+        if (owner != ctx) {
+            Bufs::release();
+            owner = ctx;
+        }
+    }
+    // the context is going away (impdar_ctx_destroy)
+    void forget(impdar_ctx *ctx)
+    {
+        const auto held = lock();
+        if (owner == ctx) {
+            Bufs::release();
+            owner = nullptr;
+        }
+    }
+    // a host-buffer entry point's upload of the caller's array into `buf` (one of Bufs), on the compute stream
+    int stage_in(impdar_ctx *ctx, DevBuf &buf, const void *host, size_t bytes)
+    {
+        IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+        bind(ctx);
+        IMPDAR_HIP_CHECK(buf.ensure(bytes));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return IMPDAR_OK;
+    }
+};

@@ -37,7 +37,6 @@
 // The file is compiled with -ffp-contract=off, like the rest of the library.
 #include "common.h"
 #include <cmath>
-#include <mutex>
 
 #define WN_BLOCK 256
 #define WN_RS 64                          // output rows per strip of wn_vsum_kernel (one pivot per strip)
@@ -420,8 +419,7 @@ __global__ __launch_bounds__(256) void med_radix_kernel(const T *__restrict__ x,
 
 // ------------------------------------------------------------------------------------------------ host side
 
-struct DenoiseScratch {
-    impdar_ctx *owner = nullptr;
+struct DenoiseBufs {
     DevBuf in, out, v1, v2, vc, rowsum, noise;
     void release()
     {
@@ -434,26 +432,9 @@ struct DenoiseScratch {
         noise.release();
     }
 };
-static DenoiseScratch g_dn;
-static std::recursive_mutex g_dn_mu;   // one scratch set per process; re-entrant (the host forms call the resident ones)
-#define DENOISE_LOCK() std::lock_guard<std::recursive_mutex> denoise_lock_(g_dn_mu)
+static StepScratch<DenoiseBufs> g_dn;
 
-static void dn_bind(impdar_ctx *ctx)
-{
-    if (g_dn.owner != ctx) {
-        g_dn.release();
-        g_dn.owner = ctx;
-    }
-}
-
-void impdar_denoise_forget(impdar_ctx *ctx)
-{
-    DENOISE_LOCK();
-    if (g_dn.owner == ctx) {
-        g_dn.release();
-        g_dn.owner = nullptr;
-    }
-}
+void impdar_denoise_forget(impdar_ctx *ctx) { g_dn.forget(ctx); }
 
 #define DN_CHECK_ARGS(name)                                                                                          \
     IMPDAR_ARG_CHECK(ctx && d_data && d_out, name ": null argument");                                               \
@@ -501,10 +482,10 @@ static int wn_run(impdar_ctx *ctx, const T *d_x, int snum, int tnum, int m, int 
 extern "C" int impdar_wiener_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int vert_win,
                                  int hor_win, double noise, int noise_given, double *d_out, double *noise_used)
 {
-    DENOISE_LOCK();
+    const auto lock = g_dn.lock();
     DN_CHECK_ARGS("impdar_wiener");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    dn_bind(ctx);
+    g_dn.bind(ctx);
     if (dtype == IMPDAR_F32)
         return wn_run(ctx, (const float *)d_data, snum, tnum, vert_win, hor_win, noise, noise_given, d_out, noise_used);
     return wn_run(ctx, (const double *)d_data, snum, tnum, vert_win, hor_win, noise, noise_given, d_out, noise_used);
@@ -529,7 +510,7 @@ static void md_launch(impdar_ctx *ctx, const T *d_x, T *d_out, int snum, int tnu
 extern "C" int impdar_median_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int vert_win,
                                  int hor_win, void *d_out)
 {
-    DENOISE_LOCK();
+    const auto lock = g_dn.lock();
     DN_CHECK_ARGS("impdar_median");
     IMPDAR_ARG_CHECK(d_out != d_data, "impdar_median: the output must be a separate buffer");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
@@ -543,26 +524,17 @@ extern "C" int impdar_median_dev(impdar_ctx *ctx, const void *d_data, int dtype,
 
 // ---- host-buffer forms: upload, run, download ------------------------------------------------------------
 
-static int dn_stage_in(impdar_ctx *ctx, const void *host, size_t bytes, size_t out_bytes)
-{
-    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    dn_bind(ctx);
-    IMPDAR_HIP_CHECK(g_dn.in.ensure(bytes));
-    IMPDAR_HIP_CHECK(g_dn.out.ensure(out_bytes));
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(g_dn.in.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return IMPDAR_OK;
-}
-
 extern "C" int impdar_wiener(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int vert_win,
                              int hor_win, double noise, int noise_given, double *out, double *noise_used)
 {
-    DENOISE_LOCK();
+    const auto lock = g_dn.lock();
     const void *d_data = data;
     double *d_out = out;
     DN_CHECK_ARGS("impdar_wiener");
     const size_t ne = (size_t)snum * tnum;
-    int rc = dn_stage_in(ctx, data, ne * impdar_dtype_size(dtype), ne * sizeof(double));
+    int rc = g_dn.stage_in(ctx, g_dn.in, data, ne * impdar_dtype_size(dtype));
     if (rc) return rc;
+    IMPDAR_HIP_CHECK(g_dn.out.ensure(ne * sizeof(double)));
     rc = impdar_wiener_dev(ctx, g_dn.in.p, dtype, snum, tnum, vert_win, hor_win, noise, noise_given,
                            g_dn.out.as<double>(), noise_used);
     if (rc) return rc;
@@ -572,13 +544,14 @@ extern "C" int impdar_wiener(impdar_ctx *ctx, const void *data, int dtype, int s
 extern "C" int impdar_median(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int vert_win,
                              int hor_win, void *out)
 {
-    DENOISE_LOCK();
+    const auto lock = g_dn.lock();
     const void *d_data = data;
     void *d_out = out;
     DN_CHECK_ARGS("impdar_median");
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = dn_stage_in(ctx, data, bytes, bytes);
+    int rc = g_dn.stage_in(ctx, g_dn.in, data, bytes);
     if (rc) return rc;
+    IMPDAR_HIP_CHECK(g_dn.out.ensure(bytes));
     rc = impdar_median_dev(ctx, g_dn.in.p, dtype, snum, tnum, vert_win, hor_win, g_dn.out.p);
     if (rc) return rc;
     return impdar_download(ctx, out, g_dn.out.p, bytes, ctx->stream);

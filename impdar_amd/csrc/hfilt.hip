@@ -21,7 +21,6 @@
 //                          stencil and the taper and subtracts in fp64, storing in the data's dtype.
 // The file is compiled with -ffp-contract=off, like the rest of the library.
 #include "common.h"
-#include <mutex>
 
 #define HF_BLOCK 256
 #define HF_PER 4                          // consecutive elements per thread in one scan chunk
@@ -153,8 +152,7 @@ __global__ __launch_bounds__(HF_BLOCK) void hfilt_mean_kernel(T *__restrict__ x,
 
 // ------------------------------------------------------------------------------------------------ host side
 
-struct HfiltScratch {
-    impdar_ctx *owner = nullptr;
+struct HfiltBufs {
     DevBuf data, M, P, tab;
     // pinned staging of the small host tables: copied on the stream without draining it; the next call waits only for
     // the previous table copy before it reuses the buffer
@@ -177,26 +175,9 @@ struct HfiltScratch {
         pending = false;
     }
 };
-static HfiltScratch g_hf;
-static std::recursive_mutex g_hf_mu;   // one scratch set per process; re-entrant (the host forms call the resident ones)
-#define HFILT_LOCK() std::lock_guard<std::recursive_mutex> hfilt_lock_(g_hf_mu)
+static StepScratch<HfiltBufs> g_hf;
 
-static void hf_bind(impdar_ctx *ctx)
-{
-    if (g_hf.owner != ctx) {
-        g_hf.release();
-        g_hf.owner = ctx;
-    }
-}
-
-void impdar_hfilt_forget(impdar_ctx *ctx)
-{
-    HFILT_LOCK();
-    if (g_hf.owner == ctx) {
-        g_hf.release();
-        g_hf.owner = nullptr;
-    }
-}
+void impdar_hfilt_forget(impdar_ctx *ctx) { g_hf.forget(ctx); }
 
 // the concatenation of `n` host blocks into the device table buffer, enqueued on the compute stream
 static int hf_upload_tables(impdar_ctx *ctx, const void *const *src, const size_t *bytes, int n)
@@ -228,13 +209,13 @@ static int hf_upload_tables(impdar_ctx *ctx, const void *const *src, const size_
 extern "C" int impdar_hfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, int lo, int hi,
                                 const double *scale)
 {
-    HFILT_LOCK();
+    const auto lock = g_hf.lock();
     IMPDAR_ARG_CHECK(ctx && d_data && scale, "impdar_hfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
     IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    hf_bind(ctx);
+    g_hf.bind(ctx);
     const void *src[1] = {scale};
     const size_t bytes[1] = {(size_t)snum * sizeof(double)};
     int rc = hf_upload_tables(ctx, src, bytes, 1);
@@ -252,7 +233,7 @@ extern "C" int impdar_hfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int sn
 extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo,
                                  const int *hi, const double *scale)
 {
-    HFILT_LOCK();
+    const auto lock = g_hf.lock();
     IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && scale, "impdar_ahfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_ahfilt: dtype must be float32 or float64");
     // scipy.signal.filtfilt's own guard and message (padlen = 3 * 4 taps)
@@ -262,7 +243,7 @@ extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int s
         IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] <= tnum,
                          "impdar_ahfilt: window [%d, %d) of trace %d not inside [0, %d]", lo[i], hi[i], i, tnum);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    hf_bind(ctx);
+    g_hf.bind(ctx);
     const size_t es = impdar_dtype_size(dtype);
     const int nblk = snum < HF_MAX_ROW_BLOCKS ? snum : HF_MAX_ROW_BLOCKS;
     IMPDAR_HIP_CHECK(g_hf.M.ensure((size_t)snum * tnum * es));
@@ -293,25 +274,16 @@ extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int s
 
 // ---- host-buffer forms: upload, run, download ------------------------------------------------------------
 
-static int hf_stage_in(impdar_ctx *ctx, const void *host, size_t bytes)
-{
-    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    hf_bind(ctx);
-    IMPDAR_HIP_CHECK(g_hf.data.ensure(bytes));
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(g_hf.data.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return IMPDAR_OK;
-}
-
 extern "C" int impdar_hfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, int lo, int hi,
                             const double *scale)
 {
-    HFILT_LOCK();
+    const auto lock = g_hf.lock();
     IMPDAR_ARG_CHECK(ctx && data && scale, "impdar_hfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
     IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = hf_stage_in(ctx, data, bytes);
+    int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
     if (rc) return rc;
     rc = impdar_hfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
     if (rc) return rc;
@@ -321,13 +293,13 @@ extern "C" int impdar_hfilt(impdar_ctx *ctx, void *data, int dtype, int snum, in
 extern "C" int impdar_ahfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
                              const double *scale)
 {
-    HFILT_LOCK();
+    const auto lock = g_hf.lock();
     IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_ahfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_ahfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum > 12, "The length of the input vector x must be greater than padlen, which is %d.", 12);
     IMPDAR_ARG_CHECK(tnum >= 1, "impdar_ahfilt: empty radargram");
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = hf_stage_in(ctx, data, bytes);
+    int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
     if (rc) return rc;
     rc = impdar_ahfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
     if (rc) return rc;

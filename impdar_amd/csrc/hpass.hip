@@ -9,10 +9,11 @@
 //   y = z[0] + b[0]*x;  z[n] = z[n+1] + x*b[n+1] - y*a[n+1];  z[last] = x*b[last] - y*a[last].
 // A transfer-function filter with low corners goes through large transient growth of its state, so neither a
 // chunked evaluation with carried state nor second-order sections reproduce filtfilt(b, a): the
-// parallelism comes from the rows only.  As in the vertical band pass (preproc.hip), the delays of one row are
-// spread over the lanes of the row's group and neighbours are fetched with DPP moves before anything is updated;
-// a wavefront walks 64 / G rows side by side.  G = 4 lanes (one quad) when the filter has at most 4 delays, else 8
-// (two DPP hops for the broadcast of z[0], but half the delays per lane): measured in DESIGN.md 4.7.
+// parallelism comes from the rows only.  The delays of one row are spread over the lanes of the row's group and
+// neighbours are fetched with DPP moves before anything is updated (FiltLane of filtfilt_core.h, the recurrence
+// this file shares with the vertical band pass); a wavefront walks 64 / G rows side by side.  G = 4 lanes (one
+// quad) when the filter has at most 4 delays, else 8 (two DPP hops for the broadcast of z[0], but half the
+// delays per lane): measured in DESIGN.md 4.7.
 //
 // Memory side: the samples of a row are contiguous, so the wavefront reads a (rows x HP_CH) tile with plain
 // element loads, 64 consecutive elements per instruction (two or more full row segments), and stages it
@@ -20,101 +21,14 @@
 // sample from LDS (all lanes of a row read the same address: a broadcast).  The outputs stay in registers,
 // packed as lane q holding step G * k + q, and are stored at the top of the next chunk, in front of the
 // next prefetch, so a whole chunk of filtering separates every store and load from the wait that retires it.
-#include "common.h"
-#include <mutex>
+#include "filtfilt_core.h"
 
 #define HP_MAX_COEF 17   // 16 delays: K = 2 per lane at 8 lanes per row
 #define HP_CH 32         // samples per chunk
 
-struct HpCoefs {
-    double b[HP_MAX_COEF];
-    double a[HP_MAX_COEF];
-    double zi[HP_MAX_COEF];
-};
-
-template <int CTRL> __device__ __forceinline__ double hp_dpp(double v)
-{
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-// value of lane 0 of the row's group of G lanes
-template <int G> __device__ __forceinline__ double hp_bcast0(double v)
-{
-    if constexpr (G == 4) {
-        return hp_dpp<0x00>(v);   // quad_perm [0,0,0,0]
-    } else {
-        static_assert(G == 8, "4 or 8 lanes per row");
-        // quad broadcast, then banks 1 and 3 of each 16-lane row take it from four lanes down (row_shr:4)
-        const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x00, 0xf, 0xf, true);
-        const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x00, 0xf, 0xf, true);
-        const int lo2 = __builtin_amdgcn_update_dpp(lo, lo, 0x114, 0xf, 0xa, false);
-        const int hi2 = __builtin_amdgcn_update_dpp(hi, hi, 0x114, 0xf, 0xa, false);
-        return __hiloint2double(hi2, lo2);
-    }
-}
-
-// value of the next lane of the group (the last lane's result is discarded by the caller)
-template <int G> __device__ __forceinline__ double hp_next(double v)
-{
-    if constexpr (G == 4) return hp_dpp<0xF9>(v);   // quad_perm [1,2,3,3]
-    else return hp_dpp<0x101>(v);                    // row_shl:1
-}
-
-// lane q of a row's group keeps the K delays z[qK .. qK+K-1] (padded with zero coefficients) and their coefficients
-template <int G, int K> struct HpLane {
-    double z[K], B[K], A[K];
-    double b0;
-    bool last;
-    __device__ __forceinline__ void init(const HpCoefs &c, int q, int nc, double x0)
-    {
-        b0 = c.b[0];
-        last = q == G - 1;
-        // uniform indices only: a lane-indexed read of the kernel argument becomes a vector memory load, and the
-        // wait bookkeeping of the compiler then drains every prefetch at the top of each chunk
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            B[k] = A[k] = z[k] = 0.0;
-#pragma unroll
-            for (int l = 0; l < G; ++l) {
-                const int n = l * K + k;   // delay index; its coefficients are b[n+1], a[n+1]
-                if (n + 1 < HP_MAX_COEF && q == l && n + 1 < nc) {
-                    B[k] = c.b[n + 1];
-                    A[k] = c.a[n + 1];
-                    z[k] = c.zi[n] * x0;
-                }
-            }
-        }
-    }
-    __device__ __forceinline__ double step(double xn)
-    {
-        const double y = hp_bcast0<G>(z[0]) + b0 * xn;
-        double zn = hp_next<G>(z[0]);
-        if (last) zn = 0.0;
-#pragma unroll
-        for (int k = 0; k < K - 1; ++k) z[k] = z[k + 1] + xn * B[k] - y * A[k];
-        z[K - 1] = zn + xn * B[K - 1] - y * A[K - 1];
-        return y;
-    }
-};
-
-// sample i of the odd extension of one row (scipy.signal._arraytools.odd_ext), in the data's own arithmetic;
-// i past the end is clamped (those outputs are never stored)
-template <typename T> __device__ __forceinline__ T hp_ext(const T *__restrict__ xr, int i, int tnum, int pad)
-{
-    const int L = tnum + 2 * pad;
-    i = i < L ? i : L - 1;
-    if (i < pad) return (T)((T)2 * xr[0] - xr[pad - i]);
-    i -= pad;
-    if (i < tnum) return xr[i];
-    i -= tnum;
-    return (T)((T)2 * xr[tnum - 1] - xr[tnum - 2 - i]);
-}
-
 // HP_CH steps on the samples of an LDS tile row (read forward or backward); lane q keeps step G*k + q in held[k]
 template <int G, int K, bool REV>
-__device__ __forceinline__ void hp_chunk_steps(HpLane<G, K> &f, const double *tr, double (&held)[HP_CH / G], int q)
+__device__ __forceinline__ void hp_chunk_steps(FiltLane<G, K> &f, const double *tr, double (&held)[HP_CH / G], int q)
 {
 #pragma unroll
     for (int s = 0; s < HP_CH; ++s) {
@@ -132,7 +46,7 @@ template <int G> struct HpTile {
 // forward pass over the extended rows; Y is (snum, tnum + 2*pad) fp64
 template <typename T, int G, int K>
 __global__ __launch_bounds__(64) void hp_forward_kernel(const T *__restrict__ x, double *__restrict__ Y, int snum,
-                                                        int tnum, int pad, int nc, HpCoefs c)
+                                                        int tnum, int pad, int nc, FiltCoefs<HP_MAX_COEF> c)
 {
     using P = HpTile<G>;
     __shared__ double tile[2][P::RPW * P::LD];
@@ -150,14 +64,14 @@ __global__ __launch_bounds__(64) void hp_forward_kernel(const T *__restrict__ x,
     const int lcol = lane % HP_CH;
     T nx[P::NE];
 #pragma unroll
-    for (int e = 0; e < P::NE; ++e) nx[e] = hp_ext(src[e], lcol, tnum, pad);
+    for (int e = 0; e < P::NE; ++e) nx[e] = filt_odd_ext(src[e], lcol, tnum, pad, 1);
 #pragma unroll
     for (int e = 0; e < P::NE; ++e) tile[0][((e * 64 + lane) / HP_CH) * P::LD + lcol] = (double)nx[e];
     __syncthreads();
     const int row = row0 + g;
     const bool live = row < snum;
     double *yr = Y + (size_t)(live ? row : 0) * ldy;
-    HpLane<G, K> f;
+    FiltLane<G, K> f;
     f.init(c, q, nc, tile[0][g * P::LD]);
     double held[HP_CH / G];
 #pragma unroll
@@ -178,7 +92,7 @@ __global__ __launch_bounds__(64) void hp_forward_kernel(const T *__restrict__ x,
                 for (int e = 0; e < P::NE; ++e) nx[e] = src[e][n0 - pad + lcol];
             } else {
 #pragma unroll
-                for (int e = 0; e < P::NE; ++e) nx[e] = hp_ext(src[e], n0 + lcol, tnum, pad);
+                for (int e = 0; e < P::NE; ++e) nx[e] = filt_odd_ext(src[e], n0 + lcol, tnum, pad, 1);
             }
         }
         hp_chunk_steps<G, K, false>(f, &tile[buf][g * P::LD], held, q);
@@ -202,7 +116,7 @@ __global__ __launch_bounds__(64) void hp_forward_kernel(const T *__restrict__ x,
 // [pad, pad + tnum) to `out` (snum x tnum float64; may be the input of the forward pass)
 template <int G, int K>
 __global__ __launch_bounds__(64) void hp_backward_kernel(const double *__restrict__ Y, double *__restrict__ out,
-                                                         int snum, int tnum, int pad, int nc, HpCoefs c)
+                                                         int snum, int tnum, int pad, int nc, FiltCoefs<HP_MAX_COEF> c)
 {
     using P = HpTile<G>;
     __shared__ double tile[2][P::RPW * P::LD];
@@ -227,7 +141,7 @@ __global__ __launch_bounds__(64) void hp_backward_kernel(const double *__restric
     const int row = row0 + g;
     const bool live = row < snum;
     double *orow = out + (size_t)(live ? row : 0) * tnum;
-    HpLane<G, K> f;
+    FiltLane<G, K> f;
     f.init(c, q, nc, tile[0][g * P::LD + HP_CH - 1]);
     double held[HP_CH / G];
 #pragma unroll
@@ -266,8 +180,7 @@ __global__ __launch_bounds__(64) void hp_backward_kernel(const double *__restric
 
 // ------------------------------------------------------------------------------------------------ host side
 
-struct HpassScratch {
-    impdar_ctx *owner = nullptr;
+struct HpassBufs {
     DevBuf y, in, out;   // the fp64 forward pass (reused across calls); staging of the host-buffer form
     void release()
     {
@@ -276,30 +189,13 @@ struct HpassScratch {
         out.release();
     }
 };
-static HpassScratch g_hp;
-static std::recursive_mutex g_hp_mu;   // one scratch set per process; re-entrant (the host form calls the resident one)
-#define HPASS_LOCK() std::lock_guard<std::recursive_mutex> hpass_lock_(g_hp_mu)
+static StepScratch<HpassBufs> g_hp;
 
-static void hp_bind(impdar_ctx *ctx)
-{
-    if (g_hp.owner != ctx) {
-        g_hp.release();
-        g_hp.owner = ctx;
-    }
-}
-
-void impdar_hpass_forget(impdar_ctx *ctx)
-{
-    HPASS_LOCK();
-    if (g_hp.owner == ctx) {
-        g_hp.release();
-        g_hp.owner = nullptr;
-    }
-}
+void impdar_hpass_forget(impdar_ctx *ctx) { g_hp.forget(ctx); }
 
 template <typename T, int G, int K>
 static void hp_launch(impdar_ctx *ctx, const T *x, double *Y, double *out, int snum, int tnum, int pad, int nc,
-                      const HpCoefs &c)
+                      const FiltCoefs<HP_MAX_COEF> &c)
 {
     const int nb = (snum + HpTile<G>::RPW - 1) / HpTile<G>::RPW;
     hipLaunchKernelGGL((hp_forward_kernel<T, G, K>), dim3(nb), dim3(64), 0, ctx->stream, x, Y, snum, tnum, pad, nc, c);
@@ -308,7 +204,7 @@ static void hp_launch(impdar_ctx *ctx, const T *x, double *Y, double *out, int s
 
 template <typename T>
 static void hp_dispatch(impdar_ctx *ctx, const T *x, double *Y, double *out, int snum, int tnum, int pad, int nc,
-                        const HpCoefs &c)
+                        const FiltCoefs<HP_MAX_COEF> &c)
 {
     static_assert(HP_MAX_COEF - 1 <= 2 * 8, "at most 2 delays per lane at 8 lanes per row");
     const int nd = nc - 1;   // delays
@@ -320,7 +216,7 @@ static void hp_dispatch(impdar_ctx *ctx, const T *x, double *Y, double *out, int
 extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const double *b,
                                     const double *a, int ncoef, const double *zi, double *d_out)
 {
-    HPASS_LOCK();
+    const auto lock = g_hp.lock();
     IMPDAR_ARG_CHECK(ctx && d_data && b && a && zi && d_out, "impdar_hfiltfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfiltfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(ncoef >= 2 && ncoef <= HP_MAX_COEF, "impdar_hfiltfilt: %d filter coefficients (2..%d supported)",
@@ -333,14 +229,8 @@ extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dty
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F64 || d_out != d_data, "impdar_hfiltfilt: float32 input needs a separate output");
     IMPDAR_ARG_CHECK((long long)snum * (tnum + 2 * pad) < (1LL << 40), "impdar_hfiltfilt: radargram too large");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    HpCoefs c;
-    memset(&c, 0, sizeof(c));
-    for (int n = 0; n < ncoef; ++n) {   // SciPy normalises by a[0] once, up front
-        c.b[n] = b[n] / a[0];
-        c.a[n] = a[n] / a[0];
-    }
-    for (int n = 0; n < ncoef - 1; ++n) c.zi[n] = zi[n];
-    hp_bind(ctx);
+    const FiltCoefs<HP_MAX_COEF> c = filt_coefs<HP_MAX_COEF>(b, a, zi, ncoef);
+    g_hp.bind(ctx);
     IMPDAR_HIP_CHECK(g_hp.y.ensure((size_t)snum * (tnum + 2 * pad) * sizeof(double)));
     if (dtype == IMPDAR_F32)
         hp_dispatch(ctx, (const float *)d_data, g_hp.y.as<double>(), d_out, snum, tnum, pad, ncoef, c);
@@ -353,21 +243,19 @@ extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dty
 extern "C" int impdar_hfiltfilt(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *b,
                                 const double *a, int ncoef, const double *zi, double *out)
 {
-    HPASS_LOCK();
+    const auto lock = g_hp.lock();
     IMPDAR_ARG_CHECK(ctx && data && out, "impdar_hfiltfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfiltfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfiltfilt: empty radargram");
     const size_t ne = (size_t)snum * tnum;
-    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    hp_bind(ctx);
-    IMPDAR_HIP_CHECK(g_hp.in.ensure(ne * impdar_dtype_size(dtype)));
+    int rc = g_hp.stage_in(ctx, g_hp.in, data, ne * impdar_dtype_size(dtype));
+    if (rc) return rc;
     double *d_out = g_hp.in.as<double>();   // float64 runs in place
     if (dtype == IMPDAR_F32) {
         IMPDAR_HIP_CHECK(g_hp.out.ensure(ne * sizeof(double)));
         d_out = g_hp.out.as<double>();
     }
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(g_hp.in.p, data, ne * impdar_dtype_size(dtype), hipMemcpyHostToDevice, ctx->stream));
-    const int rc = impdar_hfiltfilt_dev(ctx, g_hp.in.p, dtype, snum, tnum, b, a, ncoef, zi, d_out);
+    rc = impdar_hfiltfilt_dev(ctx, g_hp.in.p, dtype, snum, tnum, b, a, ncoef, zi, d_out);
     if (rc) return rc;
     return impdar_download(ctx, out, d_out, ne * sizeof(double), ctx->stream);
 }

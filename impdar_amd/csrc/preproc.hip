@@ -9,91 +9,18 @@
 //       linear interpolation of every sample row onto equally spaced distances (scipy interp1d, slope form).
 //
 // All three are HBM-streaming kernels; the arithmetic is fp64 in SciPy's operation order whatever the data
-// type (the file is compiled with -ffp-contract=off).  The IIR recurrence is a serial chain along time: a
-// wavefront runs 16 traces, four lanes each (rows of the (snum, tnum) array are contiguous across traces, so
-// every access is a coalesced row segment), with the loads of the next 32 samples in flight while 32 are filtered.
-#include "common.h"
-#include <mutex>
+// type (the file is compiled with -ffp-contract=off).  The IIR recurrence (filtfilt_core.h, shared with the
+// horizontal frequency filters) is a serial chain along time: a wavefront runs 16 traces, four lanes each (rows
+// of the (snum, tnum) array are contiguous across traces, so every access is a coalesced row segment), with the
+// loads of the next 32 samples in flight while 32 are filtered.
+#include "filtfilt_core.h"
 
 #define FF_MAX_COEF 33
 
-struct FiltCoefs {
-    double b[FF_MAX_COEF];
-    double a[FF_MAX_COEF];
-    double zi[FF_MAX_COEF];
-};
-
-// sample i of the odd extension of trace j (scipy.signal._arraytools.odd_ext): computed in the data's own
-// arithmetic (2*x[0] - x[edge-i] is a float32 expression for float32 data), then widened
-template <typename T>
-__device__ __forceinline__ double ff_ext(const T *__restrict__ x, int i, int j, int snum, int ld, int edge)
-{
-    if (i < edge) {
-        const T e = x[j], v = x[(size_t)(edge - i) * ld + j];
-        return (double)(T)((T)2 * e - v);
-    }
-    i -= edge;
-    if (i < snum) return (double)x[(size_t)i * ld + j];
-    i -= snum;
-    const T e = x[(size_t)(snum - 1) * ld + j], v = x[(size_t)(snum - 2 - i) * ld + j];
-    return (double)(T)((T)2 * e - v);
-}
-
-// The recurrence of one trace is spread over the four lanes of a quad: lane q keeps the K delays
-// z[qK .. qK+K-1] (K = ceil((NC-1)/4), padded with zero coefficients) and their coefficients in registers.
-// fp64 issues at half rate and a trace-per-lane mapping leaves 85 % of the SIMDs idle at 10000 traces (157
-// wavefronts for 1024 SIMDs), so the ~4(NC-1) fp64 operations of a step are the whole cost: split four ways
-// they take a third of the issue slots per wavefront on four times as many SIMDs.  Every delay is still
-// updated by exactly SciPy's expression (_lfilter.c.in),
-//   y = z[0] + b[0]*x;  z[n] = z[n+1] + x*b[n+1] - y*a[n+1];  z[last] = x*b[last] - y*a[last],
-// from the old value of its neighbour, fetched across lanes with quad DPP moves before anything is updated.
-__device__ __forceinline__ double ff_quad_bcast0(double v)
-{
-#ifdef FF_DIAG_NODPP   // timing ablation only
-    return v;
-#endif
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x00, 0xf, 0xf, true);   // quad_perm [0,0,0,0]
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x00, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double ff_quad_next(double v)
-{
-#ifdef FF_DIAG_NODPP
-    return v * 0.5;
-#endif
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0xF9, 0xf, 0xf, true);   // quad_perm [1,2,3,3]
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0xF9, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-template <int K> struct FfLane {
-    double z[K], B[K], A[K];
-    double b0;
-    bool last;   // lane 3 of the quad: nothing follows its last delay
-    __device__ __forceinline__ void init(const FiltCoefs &c, int q, int nc, double x0)
-    {
-        b0 = c.b[0];
-        last = q == 3;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int n = q * K + k;   // delay index; its coefficients are b[n+1], a[n+1]
-            const bool real = n + 1 < nc;
-            B[k] = real ? c.b[n + 1] : 0.0;
-            A[k] = real ? c.a[n + 1] : 0.0;
-            z[k] = (n < nc - 1) ? c.zi[n] * x0 : 0.0;
-        }
-    }
-    __device__ __forceinline__ double step(double xn)
-    {
-        const double y = ff_quad_bcast0(z[0]) + b0 * xn;
-        double zn = ff_quad_next(z[0]);
-        if (last) zn = 0.0;
-#pragma unroll
-        for (int k = 0; k < K - 1; ++k) z[k] = z[k + 1] + xn * B[k] - y * A[k];
-        z[K - 1] = zn + xn * B[K - 1] - y * A[K - 1];
-        return y;
-    }
-};
+// The recurrence of one trace is spread over the four lanes of a quad (FiltLane<4, K> of filtfilt_core.h, K =
+// ceil((NC-1)/4)).  fp64 issues at half rate and a trace-per-lane mapping leaves 85 % of the SIMDs idle at 10000
+// traces (157 wavefronts for 1024 SIMDs), so the ~4(NC-1) fp64 operations of a step are the whole cost: split four
+// ways they take a third of the issue slots per wavefront on four times as many SIMDs.
 
 #define FF_TRACES 16   // traces per 64-lane wavefront
 #define FF_CH 32       // samples per chunk (64 needs more than 256 VGPRs for the 21- and 33-coefficient kernels)
@@ -130,40 +57,16 @@ template <typename T> __device__ __forceinline__ void ff_wait_chunk(T (&r)[FF_PK
     asm volatile("s_waitcnt vmcnt(0)" : FF_TIE8(r) : : "memory");
 }
 
-// value of lane L (0..3) of the quad
-template <int L> __device__ __forceinline__ float ff_quad_pick(float v)
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), L * 0x55, 0xf, 0xf, true));
-}
-template <int L> __device__ __forceinline__ double ff_quad_pick(double v)
-{
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), L * 0x55, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), L * 0x55, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-// sample i of the odd extension in the data's own type (see ff_ext); i may lie past the end (clamped)
-template <typename T> __device__ __forceinline__ T ff_ext_t(const T *__restrict__ x, int i, int j, int snum, int ld, int edge)
-{
-    const int L = snum + 2 * edge;
-    i = i < L ? i : L - 1;
-    if (i < edge) return (T)((T)2 * x[j] - x[(size_t)(edge - i) * ld + j]);
-    i -= edge;
-    if (i < snum) return x[(size_t)i * ld + j];
-    i -= snum;
-    return (T)((T)2 * x[(size_t)(snum - 1) * ld + j] - x[(size_t)(snum - 2 - i) * ld + j]);
-}
-
 // FF_CH steps on the packed samples in `cur`; the packed outputs go to `held` (converted to TO)
 template <typename TI, typename TO, int K>
-__device__ __forceinline__ void ff_chunk_steps(FfLane<K> &f, const TI (&cur)[FF_PK], TO (&held)[FF_PK], int q)
+__device__ __forceinline__ void ff_chunk_steps(FiltLane<4, K> &f, const TI (&cur)[FF_PK], TO (&held)[FF_PK], int q)
 {
 #pragma unroll
     for (int k = 0; k < FF_PK; ++k) {
-        const double y0 = f.step((double)ff_quad_pick<0>(cur[k]));
-        const double y1 = f.step((double)ff_quad_pick<1>(cur[k]));
-        const double y2 = f.step((double)ff_quad_pick<2>(cur[k]));
-        const double y3 = f.step((double)ff_quad_pick<3>(cur[k]));
+        const double y0 = f.step((double)quad_pick<0>(cur[k]));
+        const double y1 = f.step((double)quad_pick<1>(cur[k]));
+        const double y2 = f.step((double)quad_pick<2>(cur[k]));
+        const double y3 = f.step((double)quad_pick<3>(cur[k]));
         const double lo = (q & 1) ? y1 : y0, hi = (q & 1) ? y3 : y2;
         held[k] = (TO)((q & 2) ? hi : lo);
     }
@@ -172,19 +75,20 @@ __device__ __forceinline__ void ff_chunk_steps(FfLane<K> &f, const TI (&cur)[FF_
 // forward pass over the extended trace; Y is (snum + 2*edge, tnum) fp64
 template <typename T, int NC>
 __global__ __launch_bounds__(64) void ff_forward_kernel(const T *__restrict__ x, double *__restrict__ Y, int snum,
-                                                        int tnum, int edge, int nc, FiltCoefs c)
+                                                        int tnum, int edge, int nc, FiltCoefs<FF_MAX_COEF> c)
 {
     constexpr int K = (NC - 1 + 3) / 4;
     const int j = blockIdx.x * FF_TRACES + (threadIdx.x >> 2), q = threadIdx.x & 3;
     if (j >= tnum) return;   // whole quads leave together
     const int L = snum + 2 * edge;
-    FfLane<K> f;
-    f.init(c, q, nc, (double)ff_ext_t(x, 0, j, snum, tnum, edge));
+    const T *xj = x + j;   // the trace: one sample per row of the data
+    FiltLane<4, K> f;
+    f.init(c, q, nc, (double)filt_odd_ext(xj, 0, snum, edge, (size_t)tnum));
     T cur[FF_PK], nxt[FF_PK];
     double held[FF_PK];
     int held_i = -1;   // first sample of the chunk whose outputs are still in registers (uniform)
 #pragma unroll
-    for (int k = 0; k < FF_PK; ++k) cur[k] = ff_ext_t(x, 4 * k + q, j, snum, tnum, edge);
+    for (int k = 0; k < FF_PK; ++k) cur[k] = filt_odd_ext(xj, 4 * k + q, snum, edge, (size_t)tnum);
     for (int i = 0; i < L; i += FF_CH) {
         if (held_i >= 0) {
 #pragma unroll
@@ -198,22 +102,14 @@ __global__ __launch_bounds__(64) void ff_forward_kernel(const T *__restrict__ x,
         if (inside) {
             const T *row = x + (size_t)(r0 - edge + q) * tnum + j;
 #pragma unroll
-            for (int k = 0; k < FF_PK; ++k) {
-#ifdef FF_DIAG_NOLOAD   // timing ablation only
-                nxt[k] = (T)(k + threadIdx.x) + (T)(size_t)row;
-#else
-                ff_load_async(nxt[k], row + (size_t)(4 * k) * tnum);
-#endif
-            }
+            for (int k = 0; k < FF_PK; ++k) ff_load_async(nxt[k], row + (size_t)(4 * k) * tnum);
         } else if (r0 < L) {
 #pragma unroll
-            for (int k = 0; k < FF_PK; ++k) nxt[k] = ff_ext_t(x, r0 + 4 * k + q, j, snum, tnum, edge);
+            for (int k = 0; k < FF_PK; ++k) nxt[k] = filt_odd_ext(xj, r0 + 4 * k + q, snum, edge, (size_t)tnum);
         }
         ff_chunk_steps(f, cur, held, q);   // samples past L-1 are filtered too; their outputs are never stored
         held_i = i;
-#ifndef FF_DIAG_NOLOAD
         if (inside) ff_wait_chunk(nxt);
-#endif
 #pragma unroll
         for (int k = 0; k < FF_PK; ++k) cur[k] = nxt[k];
     }
@@ -228,13 +124,13 @@ __global__ __launch_bounds__(64) void ff_forward_kernel(const T *__restrict__ x,
 // data array in its own dtype (the rows in front of `edge` are never needed)
 template <typename T, int NC>
 __global__ __launch_bounds__(64) void ff_backward_kernel(const double *__restrict__ Y, T *__restrict__ out, int snum,
-                                                         int tnum, int edge, int nc, FiltCoefs c)
+                                                         int tnum, int edge, int nc, FiltCoefs<FF_MAX_COEF> c)
 {
     constexpr int K = (NC - 1 + 3) / 4;
     const int j = blockIdx.x * FF_TRACES + (threadIdx.x >> 2), q = threadIdx.x & 3;
     if (j >= tnum) return;
     const int L = snum + 2 * edge;
-    FfLane<K> f;
+    FiltLane<4, K> f;
     f.init(c, q, nc, Y[(size_t)(L - 1) * tnum + j]);
     double cur[FF_PK], nxt[FF_PK];
     T held[FF_PK];
@@ -256,13 +152,7 @@ __global__ __launch_bounds__(64) void ff_backward_kernel(const double *__restric
         if (inside) {
             const double *row = Y + (size_t)(p - FF_CH - q) * tnum + j;
 #pragma unroll
-            for (int k = 0; k < FF_PK; ++k) {
-#ifdef FF_DIAG_NOLOAD
-                nxt[k] = (double)(k + threadIdx.x) + (double)(size_t)row;
-#else
-                ff_load_async(nxt[k], row - (size_t)(4 * k) * tnum);
-#endif
-            }
+            for (int k = 0; k < FF_PK; ++k) ff_load_async(nxt[k], row - (size_t)(4 * k) * tnum);
         } else {
 #pragma unroll
             for (int k = 0; k < FF_PK; ++k) {
@@ -272,9 +162,7 @@ __global__ __launch_bounds__(64) void ff_backward_kernel(const double *__restric
         }
         ff_chunk_steps(f, cur, held, q);
         held_p = p;
-#ifndef FF_DIAG_NOLOAD
         if (inside) ff_wait_chunk(nxt);
-#endif
 #pragma unroll
         for (int k = 0; k < FF_PK; ++k) cur[k] = nxt[k];
     }
@@ -353,41 +241,22 @@ __global__ __launch_bounds__(256) void trace_lerp_kernel(const T *__restrict__ x
 
 // ------------------------------------------------------------------------------------------------ host side
 
-struct PreprocScratch {
-    impdar_ctx *owner = nullptr;
-    DevBuf y, data, aux, idx;
+struct PreprocBufs {
+    DevBuf y, data, aux, idx;   // the fp64 forward pass, staging of the host-buffer forms, FIR / lerp output, lerp tables
+    void release()
+    {
+        y.release();
+        data.release();
+        aux.release();
+        idx.release();
+    }
 };
-static PreprocScratch g_scr;
-// one scratch set per process: entry points of different contexts / threads take turns (re-entrant because the
-// host-buffer forms call the resident ones)
-static std::recursive_mutex g_scr_mu;
-#define PREPROC_LOCK() std::lock_guard<std::recursive_mutex> preproc_lock_(g_scr_mu)
+static StepScratch<PreprocBufs> g_scr;
 
-static void scratch_bind(impdar_ctx *ctx)
-{
-    if (g_scr.owner != ctx) {
-        g_scr.y.release();
-        g_scr.data.release();
-        g_scr.aux.release();
-        g_scr.idx.release();
-        g_scr.owner = ctx;
-    }
-}
-
-void impdar_preproc_forget(impdar_ctx *ctx)
-{
-    PREPROC_LOCK();
-    if (g_scr.owner == ctx) {
-        g_scr.y.release();
-        g_scr.data.release();
-        g_scr.aux.release();
-        g_scr.idx.release();
-        g_scr.owner = nullptr;
-    }
-}
+void impdar_preproc_forget(impdar_ctx *ctx) { g_scr.forget(ctx); }
 
 template <typename T, int NC>
-static int filtfilt_launch(impdar_ctx *ctx, T *d, double *Y, int snum, int tnum, int edge, int nc, const FiltCoefs &c)
+static int filtfilt_launch(impdar_ctx *ctx, T *d, double *Y, int snum, int tnum, int edge, int nc, const FiltCoefs<FF_MAX_COEF> &c)
 {
     const int nb = (tnum + FF_TRACES - 1) / FF_TRACES;
     hipLaunchKernelGGL((ff_forward_kernel<T, NC>), dim3(nb), dim3(64), 0, ctx->stream, d, Y, snum, tnum, edge, nc, c);
@@ -397,18 +266,20 @@ static int filtfilt_launch(impdar_ctx *ctx, T *d, double *Y, int snum, int tnum,
 }
 
 template <typename T>
-static int filtfilt_dispatch(impdar_ctx *ctx, T *d, double *Y, int snum, int tnum, int edge, int ncoef, const FiltCoefs &c)
+static int filtfilt_dispatch(impdar_ctx *ctx, T *d, double *Y, int snum, int tnum, int edge, int ncoef, const FiltCoefs<FF_MAX_COEF> &c)
 {
     if (ncoef <= 5) return filtfilt_launch<T, 5>(ctx, d, Y, snum, tnum, edge, ncoef, c);
     if (ncoef <= 11) return filtfilt_launch<T, 11>(ctx, d, Y, snum, tnum, edge, ncoef, c);
     if (ncoef <= 21) return filtfilt_launch<T, 21>(ctx, d, Y, snum, tnum, edge, ncoef, c);
+    // the last branch is FiltLane<4, 8>: more delays per lane than 8 have not been held to the 256-VGPR rule
+    static_assert(FF_MAX_COEF - 1 <= 4 * 8, "at most 8 delays per lane at 4 lanes per trace");
     return filtfilt_launch<T, FF_MAX_COEF>(ctx, d, Y, snum, tnum, edge, ncoef, c);
 }
 
 extern "C" int impdar_filtfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const double *b,
                                    const double *a, int ncoef, const double *zi)
 {
-    PREPROC_LOCK();
+    const auto lock = g_scr.lock();
     IMPDAR_ARG_CHECK(ctx && d_data && b && a && zi, "impdar_filtfilt: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_filtfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(ncoef >= 2 && ncoef <= FF_MAX_COEF, "impdar_filtfilt: %d filter coefficients (2..%d supported)", ncoef,
@@ -419,14 +290,8 @@ extern "C" int impdar_filtfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int
     IMPDAR_ARG_CHECK(snum > edge, "The length of the input vector x must be greater than padlen, which is %d.", edge);
     IMPDAR_ARG_CHECK(tnum >= 1, "impdar_filtfilt: empty radargram");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    FiltCoefs c;
-    memset(&c, 0, sizeof(c));
-    for (int n = 0; n < ncoef; ++n) {   // SciPy normalises by a[0] once, up front
-        c.b[n] = b[n] / a[0];
-        c.a[n] = a[n] / a[0];
-    }
-    for (int n = 0; n < ncoef - 1; ++n) c.zi[n] = zi[n];
-    scratch_bind(ctx);
+    const FiltCoefs<FF_MAX_COEF> c = filt_coefs<FF_MAX_COEF>(b, a, zi, ncoef);
+    g_scr.bind(ctx);
     IMPDAR_HIP_CHECK(g_scr.y.ensure((size_t)(snum + 2 * edge) * tnum * sizeof(double)));
     const int rc = dtype == IMPDAR_F32
                        ? filtfilt_dispatch<float>(ctx, (float *)d_data, g_scr.y.as<double>(), snum, tnum, edge, ncoef, c)
@@ -437,7 +302,7 @@ extern "C" int impdar_filtfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int
 extern "C" int impdar_fir_shift_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const double *taps,
                                     int ntaps)
 {
-    PREPROC_LOCK();
+    const auto lock = g_scr.lock();
     IMPDAR_ARG_CHECK(ctx && d_data && taps, "impdar_fir_shift: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_fir_shift: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(ntaps >= 1 && ntaps <= 256, "impdar_fir_shift: %d taps (1..256 supported)", ntaps);
@@ -449,7 +314,7 @@ extern "C" int impdar_fir_shift_dev(impdar_ctx *ctx, void *d_data, int dtype, in
     memset(&t, 0, sizeof(t));
     for (int i = 0; i < ntaps; ++i) t.t[FIR_ROWS + i] = taps[i];
     const size_t es = impdar_dtype_size(dtype), n = (size_t)(snum - order) * tnum;
-    scratch_bind(ctx);
+    g_scr.bind(ctx);
     IMPDAR_HIP_CHECK(g_scr.aux.ensure(n * es));
     const dim3 grid((tnum + 255) / 256, (snum - order + FIR_ROWS - 1) / FIR_ROWS);
     if (dtype == IMPDAR_F32)
@@ -466,7 +331,7 @@ extern "C" int impdar_fir_shift_dev(impdar_ctx *ctx, void *d_data, int dtype, in
 extern "C" int impdar_trace_lerp_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const int *lo,
                                      const int *hi, const double *den, const double *t, int n_new, double *d_out)
 {
-    PREPROC_LOCK();
+    const auto lock = g_scr.lock();
     IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && den && t && d_out, "impdar_trace_lerp: null argument");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_trace_lerp: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 2 && n_new >= 0, "impdar_trace_lerp: bad shape %d x %d -> %d", snum, tnum, n_new);
@@ -475,7 +340,7 @@ extern "C" int impdar_trace_lerp_dev(impdar_ctx *ctx, const void *d_data, int dt
         IMPDAR_ARG_CHECK(lo[m] >= 0 && lo[m] < tnum && hi[m] >= 0 && hi[m] < tnum, "impdar_trace_lerp: column index out of range at %d",
                          m);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    scratch_bind(ctx);
+    g_scr.bind(ctx);
     const size_t ib = (size_t)n_new * sizeof(int), db = (size_t)n_new * sizeof(double);
     IMPDAR_HIP_CHECK(g_scr.idx.ensure(2 * ib + 2 * db + 64));
     char *base = g_scr.idx.as<char>();
@@ -531,23 +396,14 @@ extern "C" int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype
 
 // ---- host-buffer forms: upload, run, download ------------------------------------------------------------
 
-static int stage_in(impdar_ctx *ctx, const void *host, size_t bytes)
-{
-    scratch_bind(ctx);
-    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    IMPDAR_HIP_CHECK(g_scr.data.ensure(bytes));
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(g_scr.data.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return IMPDAR_OK;
-}
-
 extern "C" int impdar_filtfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const double *b,
                                const double *a, int ncoef, const double *zi)
 {
-    PREPROC_LOCK();
+    const auto lock = g_scr.lock();
     IMPDAR_ARG_CHECK(ctx && data, "impdar_filtfilt: null argument");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_filtfilt: empty radargram");
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = stage_in(ctx, data, bytes);
+    int rc = g_scr.stage_in(ctx, g_scr.data, data, bytes);
     if (rc) return rc;
     rc = impdar_filtfilt_dev(ctx, g_scr.data.p, dtype, snum, tnum, b, a, ncoef, zi);
     if (rc) return rc;
@@ -556,11 +412,11 @@ extern "C" int impdar_filtfilt(impdar_ctx *ctx, void *data, int dtype, int snum,
 
 extern "C" int impdar_fir_shift(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const double *taps, int ntaps)
 {
-    PREPROC_LOCK();
+    const auto lock = g_scr.lock();
     IMPDAR_ARG_CHECK(ctx && data, "impdar_fir_shift: null argument");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_fir_shift: empty radargram");
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = stage_in(ctx, data, bytes);
+    int rc = g_scr.stage_in(ctx, g_scr.data, data, bytes);
     if (rc) return rc;
     rc = impdar_fir_shift_dev(ctx, g_scr.data.p, dtype, snum, tnum, taps, ntaps);
     if (rc) return rc;
@@ -570,12 +426,12 @@ extern "C" int impdar_fir_shift(impdar_ctx *ctx, void *data, int dtype, int snum
 extern "C" int impdar_trace_lerp(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo,
                                  const int *hi, const double *den, const double *t, int n_new, double *out)
 {
-    PREPROC_LOCK();
+    const auto lock = g_scr.lock();
     IMPDAR_ARG_CHECK(ctx && data && out, "impdar_trace_lerp: null argument");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 2 && n_new >= 0, "impdar_trace_lerp: bad shape %d x %d -> %d", snum, tnum, n_new);
     if (n_new == 0) return IMPDAR_OK;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = stage_in(ctx, data, bytes);
+    int rc = g_scr.stage_in(ctx, g_scr.data, data, bytes);
     if (rc) return rc;
     IMPDAR_HIP_CHECK(g_scr.aux.ensure((size_t)snum * n_new * sizeof(double)));
     rc = impdar_trace_lerp_dev(ctx, g_scr.data.p, dtype, snum, tnum, lo, hi, den, t, n_new, g_scr.aux.as<double>());

@@ -38,15 +38,10 @@ def check_windows(vert_win, hor_win):
 
 
 def _work(data):
-    """float32 / float64 C-contiguous array (integers and bools widened to float64)."""
-    data = np.asarray(data)
-    if data.ndim != 2:
-        raise ValueError('data must be (snum, tnum)')
-    if np.iscomplexobj(data):
-        raise TypeError('denoising complex data is not supported by the MI355X engine')
-    if data.size == 0:
+    work = _hip.work_array(data, 'denoising complex data is', copy=False)
+    if work.size == 0:
         raise ValueError('data is empty')
-    return np.ascontiguousarray(data, dtype=data.dtype if data.dtype in (np.float32, np.float64) else np.float64)
+    return work
 
 
 def _noise_args(noise):
@@ -81,16 +76,12 @@ def wiener_dev(d_arr, vert_win=1, hor_win=10, noise=None):
     float64 array; the caller frees the old one.  Returns ``(d_out, noise_used)``."""
     m, n = check_windows(vert_win, hor_win)
     snum, tnum = d_arr.shape
-    d_out = _hip.DeviceArray(d_arr.ctx, (snum, tnum), np.float64)
     nz, given = _noise_args(noise)
     used = C.c_double(0.0)
-    try:
+    with _hip.new_device_array(d_arr.ctx, (snum, tnum), np.float64) as d_out:
         rc = _hip.load().impdar_wiener_dev(d_arr.ctx, d_arr.ptr, _hip.dtype_code(d_arr.dtype), snum, tnum, m, n, nz,
                                            given, d_out.ptr, C.byref(used))
         _check_wiener(rc)
-    except Exception:
-        d_out.free()
-        raise
     return d_out, used.value
 
 
@@ -113,12 +104,8 @@ def median_dev(d_arr, vert_win=1, hor_win=10):
     one."""
     m, n = check_windows(vert_win, hor_win)
     snum, tnum = d_arr.shape
-    d_out = _hip.DeviceArray(d_arr.ctx, (snum, tnum), d_arr.dtype)
-    try:
+    with _hip.new_device_array(d_arr.ctx, (snum, tnum), d_arr.dtype) as d_out:
         rc = _hip.load().impdar_median_dev(d_arr.ctx, d_arr.ptr, _hip.dtype_code(d_arr.dtype), snum, tnum, m, n,
                                            d_out.ptr)
         _hip.check(rc, 'impdar_median')
-    except Exception:
-        d_out.free()
-        raise
     return d_out

@@ -60,13 +60,8 @@ def _check_scale(scale, snum):
 
 
 def _work(data):
-    """float32 / float64 C-contiguous working copy (integers widened to float64, as ``filter_host`` does)."""
-    data = np.asarray(data)
-    if data.ndim != 2:
-        raise ValueError('data must be (snum, tnum)')
-    if np.iscomplexobj(data):
-        raise TypeError('horizontal filters on complex data are not supported by the MI355X engine')
-    return np.array(data, dtype=data.dtype if data.dtype in (np.float32, np.float64) else np.float64, order='C')
+    """Working copy for the in-place C calls (integers widened to float64, as ``filter_host`` does)."""
+    return _hip.work_array(data, 'horizontal filters on complex data are', copy=True)
 
 
 def _ahfilt_args(shape, lo, hi, scale):

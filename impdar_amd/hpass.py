@@ -106,12 +106,7 @@ def _call(fn, ctx, ptr, code, snum, tnum, spec, out_ptr):
 
 def filtfilt_host(data, spec):
     """``filtfilt(b, a, data, axis=1)`` of a host radargram as a new float64 array (integers widened first)."""
-    data = np.asarray(data)
-    if data.ndim != 2:
-        raise ValueError('data must be (snum, tnum)')
-    if np.iscomplexobj(data):
-        raise TypeError('horizontal filtering of complex data is not supported by the MI355X engine')
-    work = np.ascontiguousarray(data, dtype=data.dtype if data.dtype in (np.float32, np.float64) else np.float64)
+    work = _hip.work_array(data, 'horizontal filtering of complex data is', copy=False)
     snum, tnum = work.shape
     check_length(spec, tnum)
     out = np.empty((snum, tnum), dtype=np.float64)
@@ -132,11 +127,7 @@ def filtfilt_dev(d_arr, spec):
         _call(lib.impdar_hfiltfilt_dev, d_arr.ctx, d_arr.ptr, _hip.dtype_code(d_arr.dtype), snum, tnum, spec,
               d_arr.ptr)
         return d_arr
-    d_out = _hip.DeviceArray(d_arr.ctx, (snum, tnum), np.float64)
-    try:
+    with _hip.new_device_array(d_arr.ctx, (snum, tnum), np.float64) as d_out:
         _call(lib.impdar_hfiltfilt_dev, d_arr.ctx, d_arr.ptr, _hip.dtype_code(d_arr.dtype), snum, tnum, spec,
               d_out.ptr)
-    except Exception:
-        d_out.free()
-        raise
     return d_out

@@ -59,11 +59,7 @@ def filter_host(data, spec):
     """Filtered copy of a host radargram in its own dtype (integers: computed in float64, then ``astype``
     as the reference's ``filtfilt(...).astype(self.data.dtype)``)."""
     data = np.asarray(data)
-    if data.ndim != 2:
-        raise ValueError('data must be (snum, tnum)')
-    if np.iscomplexobj(data):
-        raise TypeError('vertical_band_pass on complex data is not supported by the MI355X engine')
-    work = np.array(data, dtype=data.dtype if data.dtype in (np.float32, np.float64) else np.float64, order='C')
+    work = _hip.work_array(data, 'vertical_band_pass on complex data is', copy=True)
     snum, tnum = work.shape
     _run_filter(_hip.load(), _hip.context(), work.ctypes.data_as(C.c_void_p), _hip.dtype_code(work.dtype), snum, tnum,
                 spec, dev=False)
