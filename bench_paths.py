@@ -205,6 +205,93 @@ def main():
                           "cpu_baseline": cb}), flush=True)
         d_x.free()
 
+        # the steps that change the sample axis: nmo (row blend), a trace-wise pretrigger crop and elev_correct
+        # (column shift).  Traffic model: input read once + float64 output written once; the yardstick is a plain
+        # device-to-device copy that moves the same number of bytes, timed in the same run.
+        from impdar_amd import vaxis
+        import ctypes
+
+        def copy_ms(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8                 # a copy reads and writes: half the bytes each way
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+
+            def call():                                       # what a step's call does around its kernel
+                b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+                lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8))
+                lib.impdar_ctx_sync(ctx)
+                b.free()
+            ms = dev_ms(call)
+            a.free()
+            return ms
+
+        def vline(path, config, fn, algo, cb):
+            def call():
+                o = fn()
+                lib.impdar_ctx_sync(ctx)
+                o.free()
+            ms = dev_ms(call)
+            cms = copy_ms(algo)
+            print(json.dumps({"path": path, "config": config, "device_ms": ms, "traces_per_s": tnum / ms * 1e3,
+                              "algorithmic_bytes": algo, "copy_same_bytes_ms": cms, "time_over_copy": ms / cms,
+                              "roofline": {"bound": "hbm", "achieved": algo / ms / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                           "frac": algo / ms / 1e6 / 8000.0,
+                                           "note": "time per call (host clock around a device synchronise), not kernel "
+                                                   "time: it includes the output allocation and the upload of the "
+                                                   "tables; the copy of equal bytes is timed with the same allocation, "
+                                                   "synchronise and free.  Bytes: input read once + float64 output "
+                                                   "written once"},
+                              "cpu_baseline": cb}), flush=True)
+
+        tt = np.arange(snum) * 1e-2
+        nmotime = vaxis.nmo_times(tt, 60.)
+        new_tt = np.arange(tt.min(), nmotime.max(), 1e-2)
+        mt = min(tnum, 200)
+        for dtype in (np.float32, np.float64):
+            xd = x.astype(dtype)
+            d_x = _hip.DeviceArray.from_host(ctx, xd)
+            tables = vaxis.RowLerpTables(nmotime, new_tt, vaxis.np_interp_convention(dtype))
+
+            def nmo_loop():
+                out = np.empty((len(new_tt), mt))
+                for ti in range(mt):                              # the reference's per-trace loop, restated
+                    out[:, ti] = interp1d(nmotime, xd[:, ti], kind='linear')(new_tt)
+            cb = sample_cpu(nmo_loop, "one scipy interp1d per trace (the reference's loop) on %d of %d traces" % (mt, tnum))
+            if cb:
+                cb["seconds"] *= tnum / mt
+                cb["sample"] += ", scaled to all"
+            vline("nmo 60 m (row blend), resident", "%dx%d %s -> %d rows float64" % (snum, tnum, np.dtype(dtype).name, tables.n_out),
+                  lambda: vaxis.row_lerp_dev(d_x, tables), snum * tnum * xd.itemsize + tables.n_out * tnum * 8, cb)
+            d_x.free()
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+        trig = (20 + np.cumsum(rng.integers(-1, 2, tnum)).clip(-15, 15)).astype(int)
+        n_crop = snum - int(trig.min())
+
+        def crop_loop():
+            out = np.full((n_crop, mt), np.nan)
+            for i in range(mt):
+                out[:snum - trig[i], i] = x[trig[i]:, i]
+        cb = sample_cpu(crop_loop, "one slice per trace (the reference's loop) on %d of %d traces" % (mt, tnum))
+        if cb:
+            cb["seconds"] *= tnum / mt
+            cb["sample"] += ", scaled to all"
+        vline("crop at a trace-wise pretrigger (column shift), resident", "%dx%d float32 -> %d rows float64" % (snum, tnum, n_crop),
+              lambda: vaxis.col_shift_dev(d_x, trig, n_crop), snum * tnum * 4 + n_crop * tnum * 8, cb)
+        elev = 1500. + 8. * np.sin(np.arange(tnum) / 300.) + 0.001 * np.arange(tnum)
+        top_inds, max_samp, _ = vaxis.elev_shifts(elev, 1e-8, 1.69e8, tt)
+
+        def elev_loop():
+            out = np.full((snum + max_samp, mt), np.nan)
+            for i in range(mt):
+                out[top_inds[i]:top_inds[i] + snum, i] = x[:, i]
+        cb = sample_cpu(elev_loop, "one slice per trace (the reference's loop) on %d of %d traces" % (mt, tnum))
+        if cb:
+            cb["seconds"] *= tnum / mt
+            cb["sample"] += ", scaled to all"
+        vline("elev_correct (column shift), resident", "%dx%d float32 -> %d rows float64" % (snum, tnum, snum + max_samp),
+              lambda: vaxis.col_shift_dev(d_x, -top_inds, snum + max_samp), snum * tnum * 4 + (snum + max_samp) * tnum * 8, cb)
+        d_x.free()
+
         def chain(resident):
             d = NoInitRadarDataFiltering()
             d.data, (d.snum, d.tnum) = x.copy(), x.shape

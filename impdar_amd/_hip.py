@@ -93,6 +93,10 @@ SIGNATURES = {
     'impdar_median_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_hfiltfilt': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _i, _dp, _dp]),
     'impdar_hfiltfilt_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _i, _dp, _p]),
+    'impdar_row_lerp': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp, _dp, _i, _p]),
+    'impdar_row_lerp_dev': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp, _dp, _i, _p]),
+    'impdar_col_shift': (_i, [_p, _p, _i, _i, _i, _ip, _i, _p]),
+    'impdar_col_shift_dev': (_i, [_p, _p, _i, _i, _i, _ip, _i, _p]),
     'impdar_comm_unique_id': (_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),
@@ -224,7 +228,7 @@ def work_array(data, what, copy):
 
 
 class DeviceArray(object):
-    """A (rows, cols) row-major array resident in HBM."""
+    """A (rows, cols) row-major array resident in HBM (an empty one still owns a one-byte allocation)."""
 
     def __init__(self, ctx, shape, dtype):
         self.ctx = ctx
@@ -232,7 +236,7 @@ class DeviceArray(object):
         self.dtype = np.dtype(dtype)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self.ptr = _p()
-        check(load().impdar_dev_alloc(ctx, self.nbytes, C.byref(self.ptr)), 'impdar_dev_alloc')
+        check(load().impdar_dev_alloc(ctx, max(self.nbytes, 1), C.byref(self.ptr)), 'impdar_dev_alloc')
 
     @classmethod
     def from_host(cls, ctx, a):

@@ -1,17 +1,19 @@
 #! /usr/bin/env python
-"""``impproc migrate`` (and the steps usually run in front of it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise``,
-``interp``, ``hbp`` and ``lp``) on the MI355X engine.
+"""``impproc migrate`` (and the steps usually run around it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise``,
+``interp``, ``hbp``, ``lp``, ``crop``, ``nmo`` and ``elev``) on the MI355X engine.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
 denoise ``:275-293``, ``main`` ``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig``
 ``:508-519``, ``vbp`` ``:438-440``, ``hbp`` ``:443-445``, ``lp`` ``:448-450``, ``interp`` ``:483-491``,
-``denoise`` ``:503-505``): same options, types and defaults, same output naming
-(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|denoise>.mat``, ``-o`` file or
+``denoise`` ``:503-505``; crop parser ``:152-171``, nmo ``:193-220``, elev ``:71-75``, ``elev`` ``:433-435``,
+``crop`` ``:453-455``, ``nmo`` ``:463-465``): same options, types and defaults, same output naming
+(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|denoise|cropped|nmo|elev>.mat``, ``-o`` file or
 folder).  As in the reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default
 window of 1000 traces.  ``impproc denoise V H`` accepts ``--filt weiner|wiener|median`` (default ``weiner``, the reference's
 spelling, which runs the Wiener filter; the reference's own default fails in its ``RadarData.denoise``).
-The reference's other processing sub-commands are out of scope.
+As in the reference, ``impproc nmo --const_firn_offset X`` parses ``X`` and does not forward it.
+The reference's other processing sub-commands (``hcrop``, ``restack``, ``rev``, ``cat``, gains) are out of scope.
 
     python -m impdar_amd.bin.impproc migrate --mtype kirch line1_raw.mat
 """
@@ -84,6 +86,31 @@ def _get_args():
     parser_lp.set_defaults(func=lp, name='lp')
     parser_lp.add_argument('low', type=float, help='Lowest frequency passed (in wavelength)')
     _add_def_args(parser_lp)
+
+    parser_crop = subparsers.add_parser('crop', help='Crop the data in the vertical')
+    parser_crop.set_defaults(func=crop, name='cropped')
+    parser_crop.add_argument('top_or_bottom', choices=['top', 'bottom'], help='Remove from the top or bottom')
+    parser_crop.add_argument('dimension', choices=['snum', 'twtt', 'depth', 'pretrig'],
+                             help='Set the bound in terms of snum (sample number), twtt (two way travel time in '
+                                  'microseconds), depth (m, from nmo_depth or a light speed of 1.69e8 m/s) or pretrig '
+                                  '(the recorded trigger sample)')
+    parser_crop.add_argument('lim', type=float, help='The cutoff value')
+    _add_def_args(parser_crop)
+
+    parser_nmo = subparsers.add_parser('nmo', help='Normal move-out correction')
+    parser_nmo.set_defaults(func=nmo, name='nmo')
+    parser_nmo.add_argument('ant_sep', type=float, help='Antenna separation')
+    parser_nmo.add_argument('--uice', type=float, default=1.69e8, help='Speed of light in ice in m/s (default 1.69e8)')
+    parser_nmo.add_argument('--uair', type=float, default=3.0e8, help='Speed of light in air in m/s (default 3.0e8)')
+    parser_nmo.add_argument('--const_firn_offset', type=float, default=None,
+                            help='A constant value added to depth to account for firn. Default None (0.0).')
+    parser_nmo.add_argument('--rho_profile', type=str, default=None,
+                            help='Filename for a depth density profile to correct wave velocity.')
+    _add_def_args(parser_nmo)
+
+    parser_elev = subparsers.add_parser('elev', help='Elevation correct')
+    parser_elev.set_defaults(func=elev, name='elev')
+    _add_def_args(parser_elev)
 
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
@@ -172,6 +199,21 @@ def hbp(dat, low=1, high=10, **kwargs):
 def lp(dat, low=1, **kwargs):
     """Low pass filter the data."""
     dat.lowpass(low)
+
+
+def crop(dat, lim=0, top_or_bottom='top', dimension='snum', **kwargs):
+    """Crop in the vertical."""
+    dat.crop(lim, top_or_bottom=top_or_bottom, dimension=dimension)
+
+
+def nmo(dat, ant_sep=0.0, uice=1.69e8, uair=3.0e8, rho_profile=None, **kwargs):
+    """Normal move-out correction.  The parsed ``const_firn_offset`` lands in ``kwargs``, as in the reference."""
+    dat.nmo(ant_sep, uice=uice, uair=uair, rho_profile=rho_profile)
+
+
+def elev(dat, **kwargs):
+    """Move the data to start at the surface elevation (do last)."""
+    dat.elev_correct()
 
 
 def interp(dats, spacing, gps_fn=None, offset=0.0, minmove=1.0e-2, extrapolate=False, **kwargs):

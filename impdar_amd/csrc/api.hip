@@ -174,6 +174,7 @@ void impdar_preproc_forget(impdar_ctx *ctx);       // preproc.hip
 void impdar_hfilt_forget(impdar_ctx *ctx);         // hfilt.hip
 void impdar_denoise_forget(impdar_ctx *ctx);       // denoise.hip
 void impdar_hpass_forget(impdar_ctx *ctx);         // hpass.hip
+void impdar_vaxis_forget(impdar_ctx *ctx);         // vaxis.hip
 
 void impdar_kirch_trim();    // kirchhoff.hip
 void impdar_stolt_trim();    // stolt.hip
@@ -612,6 +613,7 @@ extern "C" void impdar_ctx_destroy(impdar_ctx *ctx)
     impdar_hfilt_forget(ctx);
     impdar_denoise_forget(ctx);
     impdar_hpass_forget(ctx);
+    impdar_vaxis_forget(ctx);
     impdar_devcache_trim(ctx->device);
     pinned_adopt(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);

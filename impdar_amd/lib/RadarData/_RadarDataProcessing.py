@@ -1,10 +1,15 @@
 """``RadarData.constant_space``: restack the radargram onto a constant trace spacing (reference
 ``src/impdar/lib/RadarData/_RadarDataProcessing.py:499-583``).  The stationary-shot bookkeeping and the
 per-trace attribute vectors are host NumPy; the (snum, tnum) interpolation runs on the MI355X
-(``impdar_trace_lerp``), on the resident copy when the radargram is held in HBM (``to_device``)."""
+(``impdar_trace_lerp``), on the resident copy when the radargram is held in HBM (``to_device``).
+``crop``, ``nmo``, ``constant_sample_depth_spacing`` and ``elev_correct`` (``:50-61, 64-236, 238-337, 585-632``)
+change the sample axis the same way: bookkeeping here, tables in ``impdar_amd/vaxis.py``, the radargram through
+``impdar_row_lerp`` / ``impdar_col_shift`` or a device-to-device copy."""
 import numpy as np
 
 from ... import preproc
+from ... import vaxis
+from ..ImpdarError import ImpdarError
 
 
 def picks_struct_holds_picks(struct):
@@ -64,3 +69,153 @@ def constant_space(self, spacing, min_movement=1.0e-2, show_nomove=False):
     except (IndexError, TypeError):
         self.flags.interp = np.ones((2,))
         self.flags.interp[1] = spacing
+
+
+# ------------------------------------------------------------------------------------------ the sample axis
+def _refuse_picks(self, what):
+    """Steps that would have to move picks refuse real ones, as ``constant_space`` does."""
+    if getattr(self, 'picks', None) is not None or picks_struct_holds_picks(getattr(self, '_picks_struct', None)):
+        raise NotImplementedError('{:s} picks is not part of the MI355X migration engine'.format(what))
+
+
+def _data_shape(self):
+    dev = getattr(self, '_dev', None)
+    return dev.shape if dev is not None else np.shape(self.data)
+
+
+def _data_dtype(self):
+    dev = getattr(self, '_dev', None)
+    return dev.dtype if dev is not None else np.asarray(self.data).dtype
+
+
+def _replace_data(self, on_dev, on_host):
+    """Install the result of a step that changes shape or dtype: a new resident array (the old one is freed) or a
+    new host array."""
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        new_dev = on_dev(dev)
+        dev.free()
+        self._dev = new_dev
+        self.data = None
+    else:
+        self.data = on_host(self.data)
+
+
+def crop(self, lim, top_or_bottom='top', dimension='snum', uice=1.69e8, rezero=True, zero_trig=True):
+    """Crop the radargram in the vertical (reference ``:238-337``): take off the top (``lim`` is the first sample
+    kept) or the bottom (``lim`` is the first sample dropped), ``lim`` in samples (``snum``), microseconds
+    (``twtt``) or metres (``depth``: ``nmo_depth``, or ``uice`` without it), or at the recorded trigger
+    (``pretrig``).  A scalar cut keeps the dtype (on the resident path one device-to-device copy of the kept rows);
+    a trace-wise pretrigger moves every trace up by its own trigger sample on the MI355X and gives float64 with
+    NaN below the shorter traces.  Updates ``travel_time`` (``rezero``), ``trig`` (``zero_trig``), ``nmo_depth``,
+    ``snum`` and ``flags.crop`` as the reference does.  A trace-wise pretrigger with a negative entry raises
+    ``ValueError`` (the reference fails on it in its per-trace assignment, with a broadcasting error)."""
+    ind = vaxis.crop_index(lim, top_or_bottom, dimension, self.travel_time, self.nmo_depth, self.trig, uice)
+    if top_or_bottom == 'top':
+        _refuse_picks(self, 'cropping')
+    snum_old = _data_shape(self)[0]
+
+    if not isinstance(ind, np.ndarray) or (dimension != 'pretrig'):
+        lims = [ind, snum_old] if top_or_bottom == 'top' else [0, ind]
+        # the data first: if the device step fails, no attribute has moved
+        _replace_data(self, lambda dev: vaxis.row_range_dev(dev, lims[0], lims[1]), lambda data: data[lims[0]:lims[1], :])
+        if top_or_bottom == 'top':
+            self.trig = self.trig - ind
+            if zero_trig:
+                self.trig = np.zeros_like(self.trig)
+        self.travel_time = self.travel_time[lims[0]:lims[1]]
+        if rezero:
+            self.travel_time = self.travel_time - self.travel_time[0]
+        if self.nmo_depth is not None:
+            self.nmo_depth = self.nmo_depth[lims[0]:lims[1]]
+    else:
+        # trace-wise pretrigger: every trace starts at its own trigger sample, the array at the smallest
+        mintrig = np.nanmin(ind)
+        if mintrig < 0:
+            raise ValueError('cannot crop at a negative pretrigger sample')
+        lims = [mintrig, snum_old]
+        n_out = int(snum_old - mintrig)
+        _replace_data(self, lambda dev: vaxis.col_shift_dev(dev, ind, n_out), lambda data: vaxis.col_shift_host(data, ind, n_out))
+        self.trig = self.trig - ind
+        self.travel_time = self.travel_time[lims[0]:lims[1]]
+        if rezero:
+            self.travel_time = self.travel_time - self.travel_time[0]
+    self.snum = _data_shape(self)[0]
+
+    try:
+        self.flags.crop[0] = 1
+        self.flags.crop[2] = self.flags.crop[1] + lims[1]
+    except (IndexError, TypeError):
+        self.flags.crop = np.zeros((3,))
+        self.flags.crop[0] = 1
+        self.flags.crop[2] = self.flags.crop[1] + lims[1]
+    self.flags.crop[1] = self.flags.crop[1] + lims[0]
+    print('Vertical samples reduced to subset [{:d}:{:d}] of original'.format(
+        int(self.flags.crop[1]), int(self.flags.crop[2])))
+
+
+def constant_sample_depth_spacing(self):
+    """Interpolate the radargram and ``travel_time`` onto equally spaced depths between the first and the last
+    ``nmo_depth`` (reference ``:50-61``); the data become float64.  Returns 1 when the depths already are."""
+    if self.nmo_depth is None:
+        raise AttributeError('Call nmo first...')
+    if np.allclose(np.diff(self.nmo_depth), np.ones((self.snum - 1,)) * (self.nmo_depth[1] - self.nmo_depth[0])):
+        print('No constant sampling when you already have constant sampling...')
+        return 1
+    depths = np.linspace(self.nmo_depth[0], self.nmo_depth[-1], len(self.nmo_depth))
+    # interp1d of the transposed 2-D array: the slope form whatever the dtype
+    tables = vaxis.RowLerpTables(self.nmo_depth, depths, np_interp=False)
+    _replace_data(self, lambda dev: vaxis.row_lerp_dev(dev, tables), lambda data: vaxis.row_lerp_host(data, tables))
+    self.travel_time = preproc.interp1d_linear(self.nmo_depth, self.travel_time, depths)
+    self.nmo_depth = depths
+
+
+def nmo(self, ant_sep, uice=1.69e8, uair=3.0e8, const_firn_offset=None, rho_profile=None,
+        permittivity_model=vaxis.firn_permittivity, const_sample=False):
+    """Normal move-out correction (reference ``:64-193``): every sample moves to its vertical two-way travel time
+    for antennas ``ant_sep`` metres apart, at ``uice`` or under the density profile in the csv file
+    ``rho_profile`` (depth in m, density in kg/m3; ``permittivity_model`` maps density to permittivity, ``uair``
+    is the speed of light above).  The traces are interpolated onto a new ``travel_time`` with the old time
+    step on the MI355X (float64 out), and ``nmo_depth`` is defined: ``const_sample`` re-spaces it evenly
+    afterwards, ``const_firn_offset`` is added to it.  The pretrigger must have been cropped."""
+    if np.any(self.trig > 0):
+        raise ImpdarError('Crop out the pretrigger before doing the nmo correction.')
+    profile = vaxis.load_rho_profile(rho_profile) if rho_profile is not None else None
+    nmotime = vaxis.nmo_times(self.travel_time, ant_sep, uice, uair, self.dt, self.snum, profile, permittivity_model)
+    travel_time = np.arange(min(self.travel_time), max(nmotime), self.dt * 1e6)
+    tables = vaxis.RowLerpTables(nmotime, travel_time, vaxis.np_interp_convention(_data_dtype(self)))
+    _replace_data(self, lambda dev: vaxis.row_lerp_dev(dev, tables), lambda data: vaxis.row_lerp_host(data, tables))
+    self.travel_time = travel_time
+    self.snum = len(self.travel_time)
+
+    if profile is None:
+        self.nmo_depth = self.travel_time / 2. * uice * 1.0e-6
+    else:
+        self.nmo_depth = vaxis.traveltime_to_depth(self.travel_time, self.dt, profile[0], profile[1], c=uair,
+                                                   permittivity_model=permittivity_model)
+    if const_sample:
+        constant_sample_depth_spacing(self)
+    if const_firn_offset is not None:
+        self.nmo_depth = self.nmo_depth + const_firn_offset
+    print('Normal Moveout filter complete.')
+    try:
+        self.flags.nmo[0] = 1
+        self.flags.nmo[1] = ant_sep
+    except (IndexError, TypeError):
+        self.flags.nmo = np.ones((2, ))
+        self.flags.nmo[1] = ant_sep
+
+
+def elev_correct(self, v_avg=1.69e8):
+    """Move every trace down by its surface elevation below the highest point of the profile, in samples of
+    ``dt * v_avg / 2`` metres (reference ``:585-632``), on the MI355X: float64 with NaN above and below the moved
+    traces.  Needs ``nmo_depth``; sets ``elevation`` and ``flags.elev`` and, as the reference, leaves ``snum``."""
+    if self.nmo_depth is None:
+        raise ValueError('Run nmo before elev_correct so that we have depth scale')
+    _refuse_picks(self, 'elevation-correcting')
+    top_inds, max_samp, elevation = vaxis.elev_shifts(self.elev, self.dt, v_avg, self.nmo_depth)
+    n_out = _data_shape(self)[0] + max_samp
+    _replace_data(self, lambda dev: vaxis.col_shift_dev(dev, -top_inds, n_out),
+                  lambda data: vaxis.col_shift_host(data, -top_inds, n_out))
+    self.elevation = elevation
+    self.flags.elev = 1

@@ -9,8 +9,11 @@ Mirrors (re-implemented, not copied) the reference's
 dtype), ``_RadarDataFiltering.py:590-637`` (``migrate``) and the two steps an
 impproc chain runs in front of a migration: ``vertical_band_pass``
 (``_RadarDataFiltering.py:469-549``) and ``constant_space``
-(``_RadarDataProcessing.py:499-583``).  Everything else in the reference's
-class (other filters, picks, GPS, plotting) is out of scope.
+(``_RadarDataProcessing.py:499-583``), and the steps that change the sample
+axis: ``crop``, ``nmo``, ``constant_sample_depth_spacing`` and ``elev_correct``
+(``_RadarDataProcessing.py:50-337, 585-632``).  Everything else in the
+reference's class (``hcrop``, ``restack``, ``reverse``, gains, picks, GPS,
+plotting) is out of scope.
 """
 import numpy as np
 
@@ -21,6 +24,8 @@ from ._RadarDataFiltering import adaptivehfilt as _adaptivehfilt, hfilt as _hfil
 from ._RadarDataFiltering import denoise as _denoise
 from ._RadarDataFiltering import highpass as _highpass, horizontal_band_pass as _horizontal_band_pass, lowpass as _lowpass
 from ._RadarDataProcessing import constant_space as _constant_space
+from ._RadarDataProcessing import constant_sample_depth_spacing as _constant_sample_depth_spacing, crop as _crop
+from ._RadarDataProcessing import elev_correct as _elev_correct, nmo as _nmo
 from ... import resident as _resident
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -42,6 +47,10 @@ class RadarData(object):
     highpass = _highpass
     lowpass = _lowpass
     constant_space = _constant_space
+    crop = _crop
+    nmo = _nmo
+    constant_sample_depth_spacing = _constant_sample_depth_spacing
+    elev_correct = _elev_correct
     to_device = _resident.to_device
     from_device = _resident.from_device
 

@@ -339,6 +339,31 @@ int impdar_hfiltfilt(impdar_ctx *ctx, const void *data, int dtype, int snum, int
 int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const double *b,
                          const double *a, int ncoef, const double *zi, double *d_out);
 
+/* ---- steps that change the sample axis (csrc/vaxis.hip) ------------------
+ * impdar_row_lerp: the data part of RadarData.nmo and
+ * constant_sample_depth_spacing (_RadarDataProcessing.py:50-61, :164-170): the
+ * per-trace interp1d with abscissae shared by all traces, as a blend of rows:
+ * out[i, :] = (data[hi[i], :] - data[lo[i], :]) / den[i] * t[i] + data[lo[i], :]
+ * (the difference in the data's own arithmetic, the rest in fp64), out float64
+ * (n_out, tnum); lo/hi/den/t are host arrays of n_out entries, 0 <= lo, hi < snum.
+ * impdar_col_shift: RadarData.crop with a trace-wise pretrigger (:306-322,
+ * shift = the trigger samples, n_out = snum - min(shift)) and elev_correct
+ * (:618-625, shift = -top_inds, n_out = snum + max_samp):
+ * out[i, j] = data[i + shift[j], j] where 0 <= i + shift[j] < snum, NaN
+ * elsewhere; out float64 (n_out, tnum); shift: tnum host ints.
+ * Input float32 or float64.  A scalar crop is a row range: impdar_cast_dev
+ * with equal dtypes from the first kept row. */
+int impdar_row_lerp(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum,
+                    const int *lo, const int *hi, const double *den, const double *t,
+                    int n_out, double *out);
+int impdar_row_lerp_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
+                        const int *lo, const int *hi, const double *den, const double *t,
+                        int n_out, double *d_out);
+int impdar_col_shift(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum,
+                     const int *shift, int n_out, double *out);
+int impdar_col_shift_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
+                         const int *shift, int n_out, double *d_out);
+
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
 
