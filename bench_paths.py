@@ -5,7 +5,9 @@ constant v and 1-D v(z)), the v(x,z) finite-difference branch (256x512) and the 
 migration at config-3 size (4096x10000 float32, resident in HBM, plus the
 three-step chain with and without residency), the horizontal filters (hfilt, adaptive
 hfilt at windows 10 and 1000), denoise (Wiener and median at several windows) and the horizontal frequency
-filters (hbp, lp, hp; float64, as constant_space hands them on) at the same size, resident,
+filters (hbp, lp, hp; float64, as constant_space hands them on) at the same size, resident, the sample-axis steps
+(nmo, pretrigger crop, elev_correct), the gains (rangegain, agc), the trace-axis steps (reverse, hcrop, restack) and
+winavg_hfilt beside a device-to-device copy of equal bytes,
 each through the product path on one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
@@ -290,6 +292,112 @@ def main():
             cb["sample"] += ", scaled to all"
         vline("elev_correct (column shift), resident", "%dx%d float32 -> %d rows float64" % (snum, tnum, snum + max_samp),
               lambda: vaxis.col_shift_dev(d_x, -top_inds, snum + max_samp), snum * tnum * 4 + (snum + max_samp) * tnum * 8, cb)
+        d_x.free()
+
+        # the gains, the steps that change the trace axis and winavg_hfilt, float32, resident.  The
+        # yardstick is again a device-to-device copy of the bytes of the step's traffic model, timed in the same run:
+        # with a fresh output array per call for the steps that make one (hcrop, restack), into a standing array for
+        # the steps that work in place.
+        from impdar_amd import gain as gainlib, hfilt as hfiltlib, taxis
+
+        def copy_inplace_ms(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+
+            def call():
+                lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8))
+                lib.impdar_ctx_sync(ctx)
+            ms = dev_ms(call)
+            a.free()
+            b.free()
+            return ms
+
+        def gline(path, config, fn, algo, model, cb, makes_output):
+            def call():
+                o = fn()
+                lib.impdar_ctx_sync(ctx)
+                if makes_output:
+                    o.free()
+            ms = dev_ms(call)
+            cms = copy_ms(algo) if makes_output else copy_inplace_ms(algo)
+            print(json.dumps({"path": path, "config": config, "device_ms": ms, "traces_per_s": tnum / ms * 1e3,
+                              "algorithmic_bytes": algo, "copy_same_bytes_ms": cms, "time_over_copy": ms / cms,
+                              "roofline": {"bound": "hbm", "achieved": algo / ms / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                           "frac": algo / ms / 1e6 / 8000.0,
+                                           "note": "time per call (host clock around a device synchronise), not kernel "
+                                                   "time: it includes the upload of the tables%s; the copy of equal bytes "
+                                                   "is timed the same way.  Bytes: %s"
+                                                   % (" and the output allocation" if makes_output else "", model)},
+                              "cpu_baseline": cb}), flush=True)
+
+        def scaled(cb, factor):
+            if cb:
+                cb["seconds"] *= factor
+                cb["sample"] += ", scaled to all"
+            return cb
+
+        E = 4
+        cfg = "%dx%d float32" % (snum, tnum)
+        tt = np.arange(snum) * 1e-2 + 0.01
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+        trig = rng.integers(0, 30, tnum).astype(float)
+        g_tab, start = gainlib.rangegain_tables(tt, trig, 0.02, snum, tnum)
+
+        def rgain_loop():
+            xs = x[:, :mt].copy()
+            for i in range(mt):                                   # the reference's per-trace loop, restated
+                xs[int(trig[i]) + 1:, i] *= tt[int(trig[i]) + 1:] * 0.02
+        cb = scaled(sample_cpu(rgain_loop, "one in-place product per trace (the reference's loop) on %d of %d traces" % (mt, tnum)), tnum / mt)
+        gline("rangegain, trace-wise trigger, resident", cfg, lambda: gainlib.rangegain_dev(d_x, g_tab, start), 2 * E * snum * tnum,
+              "array read once + written once", cb, False)
+        d_x.free()
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+        ma = min(tnum, 500)
+
+        def agc_loop():
+            xs = x[:, :ma].copy()
+            maxamp = np.zeros((snum,))
+            for i in range(snum):                                 # the reference's per-sample loop, restated
+                maxamp[i] = np.max(np.abs(xs[max(0, i - 25):min(i + 25, snum), :]))
+            maxamp[maxamp == 0] = 1.0e-6
+            xs *= (50 / np.atleast_2d(maxamp).transpose()).astype(xs.dtype)
+        cb = scaled(sample_cpu(agc_loop, "one window maximum per sample (the reference's loop) on %d of %d traces" % (ma, tnum)), tnum / ma)
+        gline("agc window 50, resident", cfg, lambda: gainlib.agc_dev(d_x, 25, 50), 3 * E * snum * tnum,
+              "array read once for the row maxima, then read once + written once", cb, False)
+        d_x.free()
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+        cb = sample_cpu(lambda: np.ascontiguousarray(np.fliplr(x)), "np.fliplr made contiguous, all traces")
+        gline("reverse, resident", cfg, lambda: taxis.reverse_dev(d_x), 2 * E * snum * tnum,
+              "array read once + written once", cb, False)
+        lo_c, hi_c = 1235, tnum
+        cb = sample_cpu(lambda: np.ascontiguousarray(x[:, lo_c:hi_c]), "the slice made contiguous, all kept traces")
+        gline("hcrop left at trace 1236, resident", "%s -> %d traces" % (cfg, hi_c - lo_c), lambda: taxis.col_range_dev(d_x, lo_c, hi_c),
+              2 * E * snum * (hi_c - lo_c), "kept traces read once + written once", cb, True)
+        for traces in (5, 101):
+            n_new = tnum // traces
+            mb = min(n_new, 200)
+
+            def restack_loop():
+                stack = np.zeros((snum, mb))
+                for j in range(mb):                               # the reference's per-stack loop, restated
+                    stack[:, j] = np.mean(x[:, j * traces:(j + 1) * traces], axis=1)
+            cb = scaled(sample_cpu(restack_loop, "one mean per stack (the reference's loop) on %d of %d stacks" % (mb, n_new)), n_new / mb)
+            gline("restack %d traces, resident" % traces, "%s -> %d traces float64" % (cfg, n_new), lambda: taxis.restack_dev(d_x, traces),
+                  E * snum * tnum + 8 * snum * n_new, "input read once + float64 output written once", cb, True)
+        scale = hfiltlib.taper(tt)
+        for win in (51, 1001):
+            lo_w, hi_w = hfiltlib.winavg_windows(tnum, win)
+
+            def winavg_loop():
+                out = np.zeros((snum, mt), dtype=x.dtype)
+                for i in range(mt):                               # the reference's per-trace loop, restated
+                    out[:, i] = x[:, i] - np.mean(x[:, lo_w[i]:hi_w[i]], axis=-1) * scale
+            cb = scaled(sample_cpu(winavg_loop, "one window mean per trace (the reference's loop) on %d of %d traces" % (mt, tnum)), tnum / mt)
+            gline("winavg_hfilt window %d, resident" % win, cfg, lambda: hfiltlib.winavg_dev(d_x, lo_w, hi_w, scale), 5 * E * snum * tnum,
+                  "array read once + means written once, then means and array read once + array written once "
+                  "(the fp64 prefix rows are scratch of the workgroup that wrote them)", cb, False)
         d_x.free()
 
         def chain(resident):

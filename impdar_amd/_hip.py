@@ -97,6 +97,17 @@ SIGNATURES = {
     'impdar_row_lerp_dev': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp, _dp, _i, _p]),
     'impdar_col_shift': (_i, [_p, _p, _i, _i, _i, _ip, _i, _p]),
     'impdar_col_shift_dev': (_i, [_p, _p, _i, _i, _i, _ip, _i, _p]),
+    'impdar_winavg': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp]),
+    'impdar_winavg_dev': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _dp]),
+    'impdar_rangegain': (_i, [_p, _p, _i, _i, _i, _dp, _ip]),
+    'impdar_rangegain_dev': (_i, [_p, _p, _i, _i, _i, _dp, _ip]),
+    'impdar_agc': (_i, [_p, _p, _i, _i, _i, _i, _d]),
+    'impdar_agc_dev': (_i, [_p, _p, _i, _i, _i, _i, _d]),
+    'impdar_row_absmax': (_i, [_p, _p, _i, _i, _i, _dp]),
+    'impdar_restack': (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    'impdar_restack_dev': (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    'impdar_reverse_dev': (_i, [_p, _p, _i, _i, _i]),
+    'impdar_hcrop_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_comm_unique_id': (_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),

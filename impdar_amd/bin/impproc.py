@@ -1,19 +1,23 @@
 #! /usr/bin/env python
 """``impproc migrate`` (and the steps usually run around it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise``,
-``interp``, ``hbp``, ``lp``, ``crop``, ``nmo`` and ``elev``) on the MI355X engine.
+``interp``, ``hbp``, ``lp``, ``crop``, ``nmo``, ``elev``, ``rev``, ``hcrop``, ``restack``, ``rgain`` and ``agc``) on the
+MI355X engine.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
 denoise ``:275-293``, ``main`` ``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig``
 ``:508-519``, ``vbp`` ``:438-440``, ``hbp`` ``:443-445``, ``lp`` ``:448-450``, ``interp`` ``:483-491``,
 ``denoise`` ``:503-505``; crop parser ``:152-171``, nmo ``:193-220``, elev ``:71-75``, ``elev`` ``:433-435``,
-``crop`` ``:453-455``, ``nmo`` ``:463-465``): same options, types and defaults, same output naming
-(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|denoise|cropped|nmo|elev>.mat``, ``-o`` file or
+``crop`` ``:453-455``, ``nmo`` ``:463-465``; rev parser ``:57-61``, restack ``:78-87``, rgain ``:90-99``, agc
+``:102-111``, hcrop ``:174-190``, ``rev`` ``:428-430``, ``hcrop`` ``:458-460``, ``restack`` ``:468-470``, ``rgain``
+``:473-475``, ``agc`` ``:478-480``): same options, types and defaults, same output naming
+(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|denoise|cropped|nmo|elev|rev|hcropped|restacked|rgain|agc>.mat``, ``-o`` file or
 folder).  As in the reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default
 window of 1000 traces.  ``impproc denoise V H`` accepts ``--filt weiner|wiener|median`` (default ``weiner``, the reference's
 spelling, which runs the Wiener filter; the reference's own default fails in its ``RadarData.denoise``).
 As in the reference, ``impproc nmo --const_firn_offset X`` parses ``X`` and does not forward it.
-The reference's other processing sub-commands (``hcrop``, ``restack``, ``rev``, ``cat``, gains) are out of scope.
+As in the reference, ``impproc agc`` has no option for the scaling factor and gains with the function's default of 50.
+The reference's other processing sub-commands (``cat``, ``geolocate`` and the rest) are out of scope.
 
     python -m impdar_amd.bin.impproc migrate --mtype kirch line1_raw.mat
 """
@@ -111,6 +115,33 @@ def _get_args():
     parser_elev = subparsers.add_parser('elev', help='Elevation correct')
     parser_elev.set_defaults(func=elev, name='elev')
     _add_def_args(parser_elev)
+
+    parser_rev = subparsers.add_parser('rev', help='Reverse the data')
+    parser_rev.set_defaults(func=rev, name='rev')
+    _add_def_args(parser_rev)
+
+    parser_hcrop = subparsers.add_parser('hcrop', help='Crop the data in the horizontal')
+    parser_hcrop.set_defaults(func=hcrop, name='hcropped')
+    parser_hcrop.add_argument('left_or_right', choices=['left', 'right'], help='Remove from the left or right')
+    parser_hcrop.add_argument('dimension', choices=['tnum', 'dist'],
+                              help='Set the bound in terms of tnum (trace number, 1 indexed) or dist (distance in km)')
+    parser_hcrop.add_argument('lim', type=float, help='The cutoff value')
+    _add_def_args(parser_hcrop)
+
+    parser_restack = subparsers.add_parser('restack', help='Restack to interval')
+    parser_restack.set_defaults(func=restack, name='restacked')
+    parser_restack.add_argument('traces', type=int, help='Number of traces to stack. Must be an odd number')
+    _add_def_args(parser_restack)
+
+    parser_rgain = subparsers.add_parser('rgain', help='Add a range gain')
+    parser_rgain.set_defaults(func=rgain, name='rgain')
+    parser_rgain.add_argument('-slope', type=float, default=0.1, help='Slope of linear range gain. Default 0.1')
+    _add_def_args(parser_rgain)
+
+    parser_agc = subparsers.add_parser('agc', help='Add an automatic gain')
+    parser_agc.set_defaults(func=agc, name='agc')
+    parser_agc.add_argument('-window', type=int, default=50, help='Number of samples to average')
+    _add_def_args(parser_agc)
 
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
@@ -214,6 +245,31 @@ def nmo(dat, ant_sep=0.0, uice=1.69e8, uair=3.0e8, rho_profile=None, **kwargs):
 def elev(dat, **kwargs):
     """Move the data to start at the surface elevation (do last)."""
     dat.elev_correct()
+
+
+def rev(dat, **kwargs):
+    """Flip the data horizontally."""
+    dat.reverse()
+
+
+def hcrop(dat, lim=0, left_or_right='left', dimension='tnum', **kwargs):
+    """Crop in the horizontal."""
+    dat.hcrop(lim, left_or_right=left_or_right, dimension=dimension)
+
+
+def restack(dat, traces=1, **kwargs):
+    """Restack to reduce size and noise."""
+    dat.restack(traces)
+
+
+def rgain(dat, slope=0.1, **kwargs):
+    """Range gain."""
+    dat.rangegain(slope)
+
+
+def agc(dat, window=50, scale_factor=50, **kwargs):
+    """Automatic gain control.  ``scale_factor`` is forwarded as ``scaling_factor``, as in the reference."""
+    dat.agc(window=window, scaling_factor=scale_factor)
 
 
 def interp(dats, spacing, gps_fn=None, offset=0.0, minmove=1.0e-2, extrapolate=False, **kwargs):

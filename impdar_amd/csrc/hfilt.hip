@@ -19,8 +19,11 @@
 //                          flat band -- the very thing the filter is for.
 //   ahfilt_apply_kernel    one thread per trace walks a strip of rows with M[t-3..t+3] in registers, applies the
 //                          stencil and the taper and subtracts in fp64, storing in the data's dtype.
+//   * winavg_hfilt(avg_win)  (:353-440): trace i loses scale[t] * mean(data[:, lo_i:hi_i], -1), the mean in the
+//       data's dtype, with no vertical smoothing: ahfilt_rowmean_kernel with another window table, then
+//       x[t, i] = (T)((double)x[t, i] - (double)M[t, i] * scale[t]) through the in-place frame of rowwise.h.
 // The file is compiled with -ffp-contract=off, like the rest of the library.
-#include "common.h"
+#include "rowwise.h"
 
 #define HF_BLOCK 256
 #define HF_PER 4                          // consecutive elements per thread in one scan chunk
@@ -126,6 +129,20 @@ __global__ __launch_bounds__(256) void ahfilt_apply_kernel(T *__restrict__ x, co
         for (int k = 0; k < 6; ++k) w[k] = w[k + 1];
     }
 }
+
+// the apply pass of winavg_hfilt: the tapered mean trace leaves its trace, in fp64, stored in the data's dtype
+template <typename T> struct WinavgApply {
+    const T *M;             // (snum, tnum) moving means, as aligned as the data
+    const double *scale;    // snum
+    int tnum;
+    template <int V> __device__ __forceinline__ void operator()(int t, int i, T (&v)[V]) const
+    {
+        const RwVec<T, V> m = *reinterpret_cast<const RwVec<T, V> *>(M + (size_t)t * tnum + i);
+        const double st = scale[t];
+#pragma unroll
+        for (int c = 0; c < V; ++c) v[c] = (T)((double)v[c] - (double)m.v[c] * st);
+    }
+};
 
 // one workgroup per row: fp64 sum over [lo, hi), the mean and the tapered mean each cast to T, then the row loses it
 // in T's arithmetic (reference: data - (mean(data[:, lo:hi], -1) * scale).astype(data.dtype)[:, None])
@@ -272,6 +289,43 @@ extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int s
     return impdar_ctx_mark_produced(ctx);
 }
 
+extern "C" int impdar_winavg_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo,
+                                 const int *hi, const double *scale)
+{
+    const auto lock = g_hf.lock();
+    IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && scale, "impdar_winavg: null argument");
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_winavg: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_winavg: empty radargram");
+    for (int i = 0; i < tnum; ++i)
+        IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] <= tnum,
+                         "impdar_winavg: window [%d, %d) of trace %d not inside [0, %d]", lo[i], hi[i], i, tnum);
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_hf.bind(ctx);
+    const size_t es = impdar_dtype_size(dtype);
+    const int nblk = snum < HF_MAX_ROW_BLOCKS ? snum : HF_MAX_ROW_BLOCKS;
+    IMPDAR_HIP_CHECK(g_hf.M.ensure((size_t)snum * tnum * es));
+    IMPDAR_HIP_CHECK(g_hf.P.ensure((size_t)nblk * (tnum + 1) * sizeof(double)));
+    const size_t db = (size_t)snum * sizeof(double), ib = (size_t)tnum * sizeof(int);
+    const void *src[3] = {scale, lo, hi};
+    const size_t bytes[3] = {db, ib, ib};
+    int rc = hf_upload_tables(ctx, src, bytes, 3);
+    if (rc) return rc;
+    const double *d_scale = g_hf.tab.as<double>();
+    const int *d_lo = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15));
+    const int *d_hi = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15) + ((ib + 15) & ~(size_t)15));
+    if (dtype == IMPDAR_F32) {
+        hipLaunchKernelGGL(ahfilt_rowmean_kernel<float>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream, (const float *)d_data,
+                           g_hf.M.as<float>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
+        rowwise_launch(ctx, (float *)d_data, snum, tnum, WinavgApply<float>{g_hf.M.as<float>(), d_scale, tnum});
+    } else {
+        hipLaunchKernelGGL(ahfilt_rowmean_kernel<double>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream,
+                           (const double *)d_data, g_hf.M.as<double>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
+        rowwise_launch(ctx, (double *)d_data, snum, tnum, WinavgApply<double>{g_hf.M.as<double>(), d_scale, tnum});
+    }
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return impdar_ctx_mark_produced(ctx);
+}
+
 // ---- host-buffer forms: upload, run, download ------------------------------------------------------------
 
 extern "C" int impdar_hfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, int lo, int hi,
@@ -302,6 +356,21 @@ extern "C" int impdar_ahfilt(impdar_ctx *ctx, void *data, int dtype, int snum, i
     int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
     if (rc) return rc;
     rc = impdar_ahfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
+    return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
+}
+
+extern "C" int impdar_winavg(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                             const double *scale)
+{
+    const auto lock = g_hf.lock();
+    IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_winavg: null argument");
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_winavg: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_winavg: empty radargram");
+    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
+    int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
+    if (rc) return rc;
+    rc = impdar_winavg_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
     if (rc) return rc;
     return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
 }

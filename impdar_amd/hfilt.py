@@ -1,10 +1,10 @@
-"""Host side of the two horizontal filters an impproc chain runs between the band pass and the migration:
-``horizontalfilt`` (remove the mean trace of a range of traces) and ``adaptivehfilt`` (remove a moving,
-vertically smoothed mean trace).  The O(snum + tnum) tables -- the clamped bounds, the adaptive windows and the
+"""Host side of the horizontal filters an impproc chain runs between the band pass and the migration:
+``horizontalfilt`` (remove the mean trace of a range of traces), ``adaptivehfilt`` (remove a moving,
+vertically smoothed mean trace) and ``winavg_hfilt`` (remove a moving mean trace as it is).  The O(snum + tnum) tables -- the clamped bounds, the adaptive windows and the
 taper -- are built here; everything that touches the (snum, tnum) radargram runs in ``csrc/hfilt.hip`` through
 the C ABI, on host buffers or on an array that is already resident in HBM.
 
-Reference: ``src/impdar/lib/RadarData/_RadarDataFiltering.py:19-135``.
+Reference: ``src/impdar/lib/RadarData/_RadarDataFiltering.py:19-135, 353-440``.
 """
 import ctypes as C
 
@@ -50,6 +50,46 @@ def ahfilt_windows(tnum, window_size):
     lo = _slice_bound(start, tnum)
     hi = np.maximum(_slice_bound(stop, tnum), lo)
     return np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+
+
+def winavg_window(avg_win, tnum):
+    """The window ``winavg_hfilt`` filters with (:390-396): no more than ``tnum`` traces, then the next odd
+    number, with the reference's messages."""
+    if avg_win > tnum:
+        print('Cannot average over more than the whole data matrix. Reducing avg_win to tnum')
+        avg_win = tnum
+    if avg_win % 2 == 0:
+        avg_win = avg_win + 1
+        print('The averaging window must be an odd number of traces.')
+        print('The averaging window has been changed to {:d}'.format(avg_win))
+    return avg_win
+
+
+def winavg_windows(tnum, avg_win):
+    """(lo, hi) int32 arrays of length tnum: trace i of ``winavg_hfilt`` averages ``data[:, lo[i]:hi[i]]`` with
+    ``lo = max(0, i - h)``, ``hi = min(i + h, tnum)`` and ``h = (avg_win - 1) // 2`` (:421-431).  The window is
+    half-open, so trace ``i + h`` is not in it, and ``avg_win = 1`` leaves it empty (lo == hi: a NaN mean)."""
+    h = (int(avg_win) - 1) // 2
+    i = np.arange(int(tnum), dtype=np.int64)
+    lo = np.maximum(i - h, 0)
+    hi = np.maximum(np.minimum(i + h, tnum), lo)
+    return np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+
+
+def winavg_taper(travel_time, kind='full', filtdepth=100):
+    """The depth taper of ``winavg_hfilt`` (:397-416), float64: ``full`` is :func:`taper`; ``pexp`` makes it reach
+    zero at sample ``filtdepth``, stay there, and start from one."""
+    scale = taper(travel_time)
+    if kind == 'full':
+        return scale
+    if kind == 'pexp':
+        scale[:filtdepth] = scale[:filtdepth] - scale[filtdepth]
+        scale[filtdepth:] = 0
+        return np.ascontiguousarray(scale / np.max(scale))
+    if kind == 'tukey':
+        raise NotImplementedError('the tukey taper of winavg_hfilt is not part of the MI355X engine (the reference\'s '
+                                  'fails on an undefined name)')
+    raise ValueError('Unrecognized taper. Options are full, pexp, or tukey')
 
 
 def _check_scale(scale, snum):
@@ -120,3 +160,36 @@ def ahfilt_dev(d_arr, lo, hi, scale):
     rc = _hip.load().impdar_ahfilt_dev(d_arr.ctx, d_arr.ptr, _hip.dtype_code(d_arr.dtype), snum, tnum, p_lo, p_hi,
                                        p_scale)
     _hip.check(rc, 'impdar_ahfilt')
+
+
+def _winavg_args(shape, lo, hi, scale):
+    snum, tnum = shape
+    lo = np.ascontiguousarray(lo, dtype=np.int32)
+    hi = np.ascontiguousarray(hi, dtype=np.int32)
+    if lo.shape != (tnum,) or hi.shape != (tnum,):
+        raise ValueError('window tables must have tnum = %d entries' % tnum)
+    ip = C.POINTER(C.c_int)
+    scale = _check_scale(scale, snum)
+    return lo, hi, scale, lo.ctypes.data_as(ip), hi.ctypes.data_as(ip), _hip.as_dp(scale)[1]
+
+
+def winavg_host(data, lo, hi, scale):
+    """Copy of a host radargram with the tapered moving mean trace removed, in its own dtype (integers: computed
+    in float64, then ``astype``, as :func:`ahfilt_host`)."""
+    data = np.asarray(data)
+    work = _work(data)
+    snum, tnum = work.shape
+    lo, hi, scale, p_lo, p_hi, p_scale = _winavg_args(work.shape, lo, hi, scale)
+    rc = _hip.load().impdar_winavg(_hip.context(), work.ctypes.data_as(C.c_void_p), _hip.dtype_code(work.dtype),
+                                   snum, tnum, p_lo, p_hi, p_scale)
+    _hip.check(rc, 'impdar_winavg')
+    return work.astype(data.dtype) if work.dtype != data.dtype else work
+
+
+def winavg_dev(d_arr, lo, hi, scale):
+    """In place on a resident :class:`impdar_amd._hip.DeviceArray` (float32 / float64)."""
+    snum, tnum = d_arr.shape
+    lo, hi, scale, p_lo, p_hi, p_scale = _winavg_args(d_arr.shape, lo, hi, scale)
+    rc = _hip.load().impdar_winavg_dev(d_arr.ctx, d_arr.ptr, _hip.dtype_code(d_arr.dtype), snum, tnum, p_lo, p_hi,
+                                       p_scale)
+    _hip.check(rc, 'impdar_winavg')

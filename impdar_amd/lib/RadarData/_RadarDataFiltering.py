@@ -3,7 +3,7 @@
 mtype names, per-mtype keyword forwarding, defaults, ValueError for unknown
 names, ``flags.mig`` recorded afterwards), ``RadarData.vertical_band_pass``
 (``:469-549``), the horizontal filters ``hfilt`` / ``horizontalfilt`` / ``adaptivehfilt`` (``:19-135``,
-``:443-466``), ``denoise`` (``:552-587``) and the horizontal frequency filters ``horizontal_band_pass`` /
+``:443-466``), ``winavg_hfilt`` (``:353-440``), ``denoise`` (``:552-587``) and the horizontal frequency filters ``horizontal_band_pass`` /
 ``highpass`` / ``lowpass`` (``:138-350``), the filters an impproc chain runs in front of a migration."""
 import numpy as np
 
@@ -35,6 +35,27 @@ def adaptivehfilt(self, window_size, *args, **kwargs):
     print('Adaptive filtering complete')
     self.flags.hfilt[0] = 1
     self.flags.hfilt[1] = 4
+
+
+def winavg_hfilt(self, avg_win, taper='full', filtdepth=100):
+    """Subtract from every trace the mean of the ``avg_win`` traces around it (made odd and at most ``tnum``,
+    with the reference's messages; the window is the reference's half-open one, so the trace ``avg_win // 2``
+    to the right is not in it and ``avg_win = 1`` gives NaN), tapered with travel time: ``taper='full'`` as
+    ``adaptivehfilt``, ``'pexp'`` down to zero at sample ``filtdepth``.  ``'tukey'`` fails in the reference on an
+    undefined name and raises ``NotImplementedError`` here.  The filtering runs on the MI355X whatever the
+    window."""
+    snum, tnum = _shape(self)
+    avg_win = _hf.winavg_window(avg_win, self.tnum)
+    scale = _hf.winavg_taper(self.travel_time, taper, filtdepth)
+    lo, hi = _hf.winavg_windows(tnum, avg_win)
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        _hf.winavg_dev(dev, lo, hi, scale)
+    else:
+        self.data = _hf.winavg_host(self.data, lo, hi, scale)
+    self.flags.hfilt = np.zeros((2,))
+    self.flags.hfilt[1] = 2
+    print('Horizontal filter complete.')
 
 
 def horizontalfilt(self, ntr1, ntr2, *args, **kwargs):

@@ -4,10 +4,14 @@ per-trace attribute vectors are host NumPy; the (snum, tnum) interpolation runs 
 (``impdar_trace_lerp``), on the resident copy when the radargram is held in HBM (``to_device``).
 ``crop``, ``nmo``, ``constant_sample_depth_spacing`` and ``elev_correct`` (``:50-61, 64-236, 238-337, 585-632``)
 change the sample axis the same way: bookkeeping here, tables in ``impdar_amd/vaxis.py``, the radargram through
-``impdar_row_lerp`` / ``impdar_col_shift`` or a device-to-device copy."""
+``impdar_row_lerp`` / ``impdar_col_shift`` or a device-to-device copy.  ``reverse``, ``hcrop`` and ``restack``
+(``:20-47, 340-453``) change the trace axis (tables in ``impdar_amd/taxis.py``), ``rangegain`` and ``agc``
+(``:456-496``) scale the samples (``impdar_amd/gain.py``)."""
 import numpy as np
 
+from ... import gain as _gain
 from ... import preproc
+from ... import taxis
 from ... import vaxis
 from ..ImpdarError import ImpdarError
 
@@ -219,3 +223,94 @@ def elev_correct(self, v_avg=1.69e8):
                   lambda data: vaxis.col_shift_host(data, -top_inds, n_out))
     self.elevation = elevation
     self.flags.elev = 1
+
+
+# ------------------------------------------------------------------------------------------- the trace axis
+def reverse(self):
+    """Flip the profile left to right (reference ``:20-47``): the data (``np.fliplr`` on the host, a row-reversal
+    kernel on the resident array) and ``x_coord``, ``y_coord``, ``decday``, ``lat``, ``long`` and ``elev``; as in
+    the reference ``dist``, ``trig``, ``pressure`` and ``trace_num`` stay.  A second call undoes the first."""
+    _refuse_picks(self, 'reversing')
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        taxis.reverse_dev(dev)
+    else:
+        self.data = np.fliplr(self.data)
+    for attr in taxis.REVERSED_ATTRS:
+        if getattr(self, attr) is not None:
+            setattr(self, attr, np.flip(getattr(self, attr), 0))
+    if self.flags.reverse:
+        print('Back to original direction')
+        self.flags.reverse = False
+    else:
+        print('Profile direction reversed')
+        self.flags.reverse = True
+
+
+def hcrop(self, lim, left_or_right='left', dimension='tnum'):
+    """Crop the radargram in the horizontal (reference ``:340-402``): take off the left (``lim`` is the first
+    trace kept) or the right (``lim`` is the first trace dropped), ``lim`` a 1-indexed trace number (``tnum``;
+    negative counts from the end) or a distance (``dist``: the first trace at or past it).  The dtype is kept: a
+    slice on the host, one strided device-to-device copy on the resident array.  Subsets every trace-wise
+    attribute, re-zeroes ``dist``, renumbers ``trace_num`` and sets ``tnum`` as the reference does."""
+    lims = taxis.hcrop_lims(lim, left_or_right, dimension, self.dist, self.tnum)
+    _refuse_picks(self, 'cropping')
+    # the data first: if the device step fails, no attribute has moved
+    _replace_data(self, lambda dev: taxis.col_range_dev(dev, lims[0], lims[1]), lambda data: data[:, lims[0]:lims[1]])
+    for attr in taxis.HCROPPED_ATTRS:
+        # some of these are optional, and trig may be a float rather than an array
+        if isinstance(getattr(self, attr), np.ndarray):
+            setattr(self, attr, getattr(self, attr)[lims[0]:lims[1]])
+    if self.dist is not None:
+        self.dist = self.dist[lims[0]:lims[1]] - self.dist[lims[0]]
+    self.trace_num = self.trace_num[lims[0]:lims[1]] - lims[0] + 1
+    self.tnum = _data_shape(self)[1]
+
+
+def restack(self, traces):
+    """Average every ``traces`` neighbouring traces into one (reference ``:405-453``); an even count is bumped to
+    the next odd one and a remainder at the end is dropped.  The data become float64 whatever they were (a
+    resident array is replaced), the means summed in fp64 on the MI355X.  ``dist``, ``pressure``, ``lat``,
+    ``long``, ``x_coord``, ``y_coord``, ``elev``, ``decday`` and ``trig`` become block means; ``trace_int`` becomes
+    zeros and ``trace_num`` 1..tnum."""
+    traces, tnum = taxis.restack_count(traces, self.tnum)
+    _refuse_picks(self, 'restacking')
+    oned = {attr: taxis.block_means(getattr(self, attr), traces, tnum) if getattr(self, attr) is not None else None
+            for attr in taxis.RESTACKED_ATTRS}
+    _replace_data(self, lambda dev: taxis.restack_dev(dev, traces), lambda data: taxis.restack_host(data, traces))
+    self.tnum = tnum
+    self.trace_num = np.arange(self.tnum).astype(int) + 1
+    self.trace_int = np.zeros((tnum, ))
+    for attr, val in oned.items():
+        setattr(self, attr, val)
+    self.flags.restack = True
+
+
+# ------------------------------------------------------------------------------------------------- the gains
+def rangegain(self, slope):
+    """Multiply every sample after a trace's trigger by ``travel_time * slope`` (reference ``:456-471``), an fp64
+    product stored in the data's dtype, on the MI355X.  ``trig`` is a scalar or one value per trace.  Integer
+    data raises ``TypeError``, as NumPy does in the reference."""
+    _gain.refuse_integers(_data_dtype(self))
+    snum, tnum = _data_shape(self)
+    gain, start = _gain.rangegain_tables(self.travel_time, self.trig, slope, snum, tnum)
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        _gain.rangegain_dev(dev, gain, start)
+    else:
+        self.data = _gain.rangegain_host(self.data, gain, start)
+    self.flags.rgain = True
+
+
+def agc(self, window=50, scaling_factor=50):
+    """Automatic gain control (reference ``:474-496``): every sample row is multiplied by ``scaling_factor`` over
+    the largest amplitude of the ``window // 2`` rows above it and the ``window // 2 - 1`` below it (1e-6 where
+    that is zero), the scale cast to the data's dtype first.  Both passes run on the MI355X; a NaN makes the rows
+    whose window holds it NaN, as in the reference.  ``window`` below 2 raises ``ValueError``."""
+    half = _gain.agc_half(window)
+    dev = getattr(self, '_dev', None)
+    if dev is not None:
+        _gain.agc_dev(dev, half, scaling_factor)
+    else:
+        self.data = _gain.agc_host(self.data, half, scaling_factor)
+    self.flags.agc = True

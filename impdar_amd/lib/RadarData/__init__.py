@@ -11,9 +11,11 @@ impproc chain runs in front of a migration: ``vertical_band_pass``
 (``_RadarDataFiltering.py:469-549``) and ``constant_space``
 (``_RadarDataProcessing.py:499-583``), and the steps that change the sample
 axis: ``crop``, ``nmo``, ``constant_sample_depth_spacing`` and ``elev_correct``
-(``_RadarDataProcessing.py:50-337, 585-632``).  Everything else in the
-reference's class (``hcrop``, ``restack``, ``reverse``, gains, picks, GPS,
-plotting) is out of scope.
+(``_RadarDataProcessing.py:50-337, 585-632``), the steps that change the
+trace axis, ``reverse``, ``hcrop`` and ``restack`` (``:20-47, 340-453``), the
+gains ``rangegain`` and ``agc`` (``:456-496``) and ``winavg_hfilt``
+(``_RadarDataFiltering.py:353-440``).  Everything else in the reference's
+class (picks, GPS, plotting) is out of scope.
 """
 import numpy as np
 
@@ -21,11 +23,13 @@ from ..ImpdarError import ImpdarError
 from ..RadarFlags import RadarFlags
 from ._RadarDataFiltering import migrate as _migrate, vertical_band_pass as _vertical_band_pass
 from ._RadarDataFiltering import adaptivehfilt as _adaptivehfilt, hfilt as _hfilt, horizontalfilt as _horizontalfilt
-from ._RadarDataFiltering import denoise as _denoise
+from ._RadarDataFiltering import denoise as _denoise, winavg_hfilt as _winavg_hfilt
 from ._RadarDataFiltering import highpass as _highpass, horizontal_band_pass as _horizontal_band_pass, lowpass as _lowpass
 from ._RadarDataProcessing import constant_space as _constant_space
 from ._RadarDataProcessing import constant_sample_depth_spacing as _constant_sample_depth_spacing, crop as _crop
 from ._RadarDataProcessing import elev_correct as _elev_correct, nmo as _nmo
+from ._RadarDataProcessing import hcrop as _hcrop, restack as _restack, reverse as _reverse
+from ._RadarDataProcessing import agc as _agc, rangegain as _rangegain
 from ... import resident as _resident
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -51,6 +55,12 @@ class RadarData(object):
     nmo = _nmo
     constant_sample_depth_spacing = _constant_sample_depth_spacing
     elev_correct = _elev_correct
+    reverse = _reverse
+    hcrop = _hcrop
+    restack = _restack
+    rangegain = _rangegain
+    agc = _agc
+    winavg_hfilt = _winavg_hfilt
     to_device = _resident.to_device
     from_device = _resident.from_device
 

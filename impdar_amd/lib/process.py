@@ -11,8 +11,9 @@ When more than one of the steps is requested on a float radargram it is uploaded
 last step is done.
 ``process_and_exit`` loads, processes and saves with the reference's file naming (``:30-70``, ``:274-295``).
 The other steps of that driver (crop, nmo, the ``hfilt=(first, last)`` mean-trace filter, restack, reverse)
-are rejected here.  ``RadarData.hfilt(ftype='hfilt')``, ``RadarData.crop`` and ``RadarData.nmo`` exist and run
-on their own (``impproc hfilt / crop / nmo``, or ``dat.to_device()`` and the methods for a resident chain), but
+are rejected here.  ``RadarData.hfilt(ftype='hfilt')``, ``RadarData.crop``, ``RadarData.nmo``, ``RadarData.hcrop``,
+``RadarData.restack`` and ``RadarData.reverse`` exist and run on their own (``impproc hfilt / crop / nmo / hcrop /
+restack / rev``, or ``dat.to_device()`` and the methods for a resident chain), but
 accepting them here would change what ``process`` has always answered to them.
 """
 import os

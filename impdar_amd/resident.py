@@ -2,12 +2,14 @@
 
 ``dat.to_device()`` uploads ``dat.data`` once; ``vertical_band_pass``, ``hfilt``, ``denoise``, ``constant_space``,
 ``horizontal_band_pass`` / ``highpass`` / ``lowpass``, ``crop``, ``nmo``, ``constant_sample_depth_spacing``,
-``elev_correct`` and ``migrate('kirch' | 'stolt' | 'phsh')`` then work on
+``elev_correct``, ``rangegain``, ``agc``, ``reverse``, ``hcrop``, ``restack``, ``winavg_hfilt`` and
+``migrate('kirch' | 'stolt' | 'phsh')`` then work on
 the resident array through the ``*_dev`` entry points of the C ABI (no PCIe traffic between steps), and
 ``dat.from_device()`` brings the result back.  ``denoise``, ``constant_space`` and the horizontal frequency
 filters may replace the resident array with a new one (their results are float64 whatever the input, as the
 reference's are); ``nmo``, ``elev_correct`` and a crop at a trace-wise pretrigger always do (float64, another
-number of samples), and a scalar ``crop`` replaces it with a copy of the kept rows in the same dtype.  While resident,
+number of samples), ``restack`` does too (float64, fewer traces), and a scalar ``crop`` and ``hcrop`` replace it with a
+copy of the kept rows or traces in the same dtype; the gains, ``reverse`` and ``winavg_hfilt`` work in place.  While resident,
 ``dat.data`` is None.  What has no resident form ('tk', the 2-D v(x, z) branch of 'phsh', SeisUnix)
 round-trips through the host.
 """

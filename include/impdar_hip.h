@@ -296,6 +296,14 @@ int impdar_ahfilt(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tn
                   const int *lo, const int *hi, const double *scale);
 int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum,
                       const int *lo, const int *hi, const double *scale);
+/* impdar_winavg: RadarData.winavg_hfilt (:353-440), in place: trace i loses
+ * scale[t] * (T)mean(data[:, lo[i]:hi[i]], -1), the difference taken in fp64
+ * and stored in the data's dtype; no vertical smoothing, so any snum.  lo, hi,
+ * scale as for impdar_ahfilt. */
+int impdar_winavg(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tnum,
+                  const int *lo, const int *hi, const double *scale);
+int impdar_winavg_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum,
+                      const int *lo, const int *hi, const double *scale);
 
 /* impdar_wiener: RadarData.denoise(ftype='wiener') (_RadarDataFiltering.py:552-587) =
  * scipy.signal.wiener(data, mysize=(vert_win, hor_win), noise): box means and
@@ -363,6 +371,44 @@ int impdar_col_shift(impdar_ctx *ctx, const void *data, int dtype, int snum, int
                      const int *shift, int n_out, double *out);
 int impdar_col_shift_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
                          const int *shift, int n_out, double *d_out);
+
+/* ---- gains (csrc/gain.hip) -------------------------------------------------
+ * impdar_rangegain: RadarData.rangegain (_RadarDataProcessing.py:456-471), in
+ * place: data[i, j] = (T)((double)data[i, j] * gain[i]) for i >= start[j]
+ * (NumPy's in-place product of float32 data and a float64 gain).  gain: snum
+ * host doubles (travel_time * slope); start: tnum host ints, the first row of
+ * each trace that is multiplied (snum or more: none).
+ * impdar_agc: RadarData.agc (:474-496), in place: row i is multiplied by
+ * (T)(scaling / m_i), m_i the largest |data| of rows [max(0, i - half),
+ * min(i + half, snum)) (half = window // 2 >= 1), NaN if one of them holds a
+ * NaN, 1e-6 where it is 0.  The window maximum is taken on the device.
+ * impdar_row_absmax: the row maxima alone, max |data[i, :]| (NaN if the row
+ * holds one) into snum host doubles: what agc needs of integer data, whose
+ * truncated integer scale the host applies.
+ * Input float32 or float64. */
+int impdar_rangegain(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tnum,
+                     const double *gain, const int *start);
+int impdar_rangegain_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum,
+                         const double *gain, const int *start);
+int impdar_agc(impdar_ctx *ctx, void *data_inout, int dtype, int snum, int tnum, int half, double scaling);
+int impdar_agc_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum, int half, double scaling);
+int impdar_row_absmax(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, double *rowmax);
+
+/* ---- steps that change the trace axis (csrc/taxis.hip) --------------------
+ * impdar_restack: the data part of RadarData.restack (:405-453):
+ * out[s, j] = mean(data[s, j * traces : (j + 1) * traces]) for j < tnum / traces
+ * (a remainder is dropped), summed in fp64 in trace order; out float64
+ * (snum, tnum / traces); traces odd.
+ * impdar_reverse_dev: RadarData.reverse (:20-47) on a resident array, in place:
+ * every row reversed (np.fliplr).
+ * impdar_hcrop_dev: RadarData.hcrop (:340-402) on a resident array: traces
+ * [lo, hi) of every row into d_out, (snum, hi - lo) of the same dtype.
+ * On host arrays reverse and hcrop are a view and a slice and need no call.
+ * Input float32 or float64. */
+int impdar_restack(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int traces, double *out);
+int impdar_restack_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int traces, double *d_out);
+int impdar_reverse_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum);
+int impdar_hcrop_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int lo, int hi, void *d_out);
 
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
