@@ -109,6 +109,7 @@ void impdar_trace(const char *fmt, ...);
     } while (0)
 
 static inline size_t impdar_dtype_size(int dtype) { return dtype == IMPDAR_F64 ? 8 : 4; }
+static inline bool impdar_dtype_ok(int dtype) { return dtype == IMPDAR_F32 || dtype == IMPDAR_F64; }
 
 // Drop what the entry points keep between calls -- the one-shot Kirchhoff plan with its images and staging copies
 // (hundreds of MB at config 3), the mig_kirch_loop plan, the Stolt and phase-shift plans with their spectra (GBs at
@@ -154,10 +155,37 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// What a processing step (preproc.hip, hfilt.hip, denoise.hip, hpass.hip) keeps between calls: its buffers -- `Bufs`,
-// with a release() that frees every one of them -- and the context they belong to.  One set per process and step:
-// entry points of different contexts / threads take turns, each holding lock() from its first line to its return
-// (re-entrant because the host-buffer forms call the resident ones).
+// The small host tables of a step (gains, windows, row indices): `blk` blocks packed at 16-byte-rounded offsets of
+// one device buffer, so a table of doubles stays aligned whatever precedes it.
+struct TableBlock {
+    const void *src;
+    size_t bytes;
+};
+static inline size_t impdar_round16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// One packed synchronous copy of the tables into `buf`, their device addresses into `dev`: the caller's host arrays
+// are free to go away on return (the stream is drained first because the previous launch may still read `buf`).
+template <int N> static int impdar_upload_tables(impdar_ctx *ctx, DevBuf &buf, const TableBlock (&blk)[N], const void *(&dev)[N])
+{
+    size_t total = 0;
+    for (int k = 0; k < N; ++k) total += impdar_round16(blk[k].bytes);
+    IMPDAR_HIP_CHECK(buf.ensure(total));
+    std::vector<char> pack(total);
+    size_t off = 0;
+    for (int k = 0; k < N; ++k) {
+        memcpy(pack.data() + off, blk[k].src, blk[k].bytes);
+        dev[k] = buf.as<char>() + off;
+        off += impdar_round16(blk[k].bytes);
+    }
+    IMPDAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    IMPDAR_HIP_CHECK(hipMemcpy(buf.p, pack.data(), total, hipMemcpyHostToDevice));
+    return IMPDAR_OK;
+}
+
+// What a processing step (preproc.hip, hfilt.hip, denoise.hip, hpass.hip, vaxis.hip, gain.hip, taxis.hip) keeps
+// between calls: its buffers -- `Bufs`, with a release() that frees every one of them -- and the context they
+// belong to.  One set per process and step: entry points of different contexts / threads take turns, each holding
+// lock() from its argument check to its return (re-entrant because the host-buffer forms call the resident ones).
 template <class Bufs> struct StepScratch : Bufs {
     impdar_ctx *owner = nullptr;
     std::recursive_mutex mu;
@@ -187,5 +215,21 @@ template <class Bufs> struct StepScratch : Bufs {
         IMPDAR_HIP_CHECK(buf.ensure(bytes));
         IMPDAR_HIP_CHECK(hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
         return IMPDAR_OK;
+    }
+    // The host-buffer form of a step, after its argument check: upload `bytes_in` of the caller's array into `in`,
+    // run the resident form as run(d_in, d_out), download `bytes_out`.  With `out` the result is that second
+    // staging buffer, ensured to hold bytes_out; without, the resident form works in place and d_out == d_in.
+    template <class Run>
+    int host_form(impdar_ctx *ctx, DevBuf &in, const void *host_in, size_t bytes_in, DevBuf *out, void *host_out,
+                  size_t bytes_out, const Run &run)
+    {
+        const auto held = lock();
+        int rc = stage_in(ctx, in, host_in, bytes_in);
+        if (rc) return rc;
+        if (out) IMPDAR_HIP_CHECK(out->ensure(bytes_out));
+        DevBuf &res = out ? *out : in;
+        rc = run(in.p, res.p);
+        if (rc) return rc;
+        return impdar_download(ctx, host_out, res.p, bytes_out, ctx->stream);
     }
 };

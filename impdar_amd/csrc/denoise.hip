@@ -436,14 +436,18 @@ static StepScratch<DenoiseBufs> g_dn;
 
 void impdar_denoise_forget(impdar_ctx *ctx) { g_dn.forget(ctx); }
 
-#define DN_CHECK_ARGS(name)                                                                                          \
-    IMPDAR_ARG_CHECK(ctx && d_data && d_out, name ": null argument");                                               \
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, name ": dtype must be float32 or float64");        \
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, name ": empty radargram");                                             \
-    IMPDAR_ARG_CHECK(vert_win >= 1 && hor_win >= 1, name ": window sizes must be at least 1, got (%d, %d)", vert_win, \
-                     hor_win);                                                                                       \
-    IMPDAR_ARG_CHECK(vert_win < (1 << 30) && hor_win < (1 << 30) && (long long)vert_win * hor_win <= 0x7fffffffLL,  \
-                     name ": window of %d x %d elements is too large", vert_win, hor_win)
+// `name` is the entry point's, as the messages have always carried it
+static int dn_check(const char *name, impdar_ctx *ctx, const void *data, const void *out, int dtype, int snum, int tnum,
+                    int vert_win, int hor_win)
+{
+    IMPDAR_ARG_CHECK(ctx && data && out, "%s: null argument", name);
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "%s: dtype must be float32 or float64", name);
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "%s: empty radargram", name);
+    IMPDAR_ARG_CHECK(vert_win >= 1 && hor_win >= 1, "%s: window sizes must be at least 1, got (%d, %d)", name, vert_win, hor_win);
+    IMPDAR_ARG_CHECK(vert_win < (1 << 30) && hor_win < (1 << 30) && (long long)vert_win * hor_win <= 0x7fffffffLL,
+                     "%s: window of %d x %d elements is too large", name, vert_win, hor_win);
+    return IMPDAR_OK;
+}
 
 template <typename T>
 static int wn_run(impdar_ctx *ctx, const T *d_x, int snum, int tnum, int m, int n, double noise, int noise_given,
@@ -483,7 +487,8 @@ extern "C" int impdar_wiener_dev(impdar_ctx *ctx, const void *d_data, int dtype,
                                  int hor_win, double noise, int noise_given, double *d_out, double *noise_used)
 {
     const auto lock = g_dn.lock();
-    DN_CHECK_ARGS("impdar_wiener");
+    const int rc = dn_check("impdar_wiener", ctx, d_data, d_out, dtype, snum, tnum, vert_win, hor_win);
+    if (rc) return rc;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_dn.bind(ctx);
     if (dtype == IMPDAR_F32)
@@ -511,7 +516,8 @@ extern "C" int impdar_median_dev(impdar_ctx *ctx, const void *d_data, int dtype,
                                  int hor_win, void *d_out)
 {
     const auto lock = g_dn.lock();
-    DN_CHECK_ARGS("impdar_median");
+    const int rc = dn_check("impdar_median", ctx, d_data, d_out, dtype, snum, tnum, vert_win, hor_win);
+    if (rc) return rc;
     IMPDAR_ARG_CHECK(d_out != d_data, "impdar_median: the output must be a separate buffer");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     if (dtype == IMPDAR_F32)
@@ -522,37 +528,28 @@ extern "C" int impdar_median_dev(impdar_ctx *ctx, const void *d_data, int dtype,
     return impdar_ctx_mark_produced(ctx);
 }
 
-// ---- host-buffer forms: upload, run, download ------------------------------------------------------------
+// ---- host-buffer forms: the argument check, then StepScratch::host_form ----------------------------------
 
 extern "C" int impdar_wiener(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int vert_win,
                              int hor_win, double noise, int noise_given, double *out, double *noise_used)
 {
-    const auto lock = g_dn.lock();
-    const void *d_data = data;
-    double *d_out = out;
-    DN_CHECK_ARGS("impdar_wiener");
+    const int rc = dn_check("impdar_wiener", ctx, data, out, dtype, snum, tnum, vert_win, hor_win);
+    if (rc) return rc;
     const size_t ne = (size_t)snum * tnum;
-    int rc = g_dn.stage_in(ctx, g_dn.in, data, ne * impdar_dtype_size(dtype));
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(g_dn.out.ensure(ne * sizeof(double)));
-    rc = impdar_wiener_dev(ctx, g_dn.in.p, dtype, snum, tnum, vert_win, hor_win, noise, noise_given,
-                           g_dn.out.as<double>(), noise_used);
-    if (rc) return rc;
-    return impdar_download(ctx, out, g_dn.out.p, ne * sizeof(double), ctx->stream);
+    return g_dn.host_form(ctx, g_dn.in, data, ne * impdar_dtype_size(dtype), &g_dn.out, out, ne * sizeof(double),
+                          [&](void *d_in, void *d_out) {
+                              return impdar_wiener_dev(ctx, d_in, dtype, snum, tnum, vert_win, hor_win, noise, noise_given,
+                                                       (double *)d_out, noise_used);
+                          });
 }
 
 extern "C" int impdar_median(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int vert_win,
                              int hor_win, void *out)
 {
-    const auto lock = g_dn.lock();
-    const void *d_data = data;
-    void *d_out = out;
-    DN_CHECK_ARGS("impdar_median");
+    const int rc = dn_check("impdar_median", ctx, data, out, dtype, snum, tnum, vert_win, hor_win);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_dn.stage_in(ctx, g_dn.in, data, bytes);
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(g_dn.out.ensure(bytes));
-    rc = impdar_median_dev(ctx, g_dn.in.p, dtype, snum, tnum, vert_win, hor_win, g_dn.out.p);
-    if (rc) return rc;
-    return impdar_download(ctx, out, g_dn.out.p, bytes, ctx->stream);
+    return g_dn.host_form(ctx, g_dn.in, data, bytes, &g_dn.out, out, bytes, [&](void *d_in, void *d_out) {
+        return impdar_median_dev(ctx, d_in, dtype, snum, tnum, vert_win, hor_win, d_out);
+    });
 }

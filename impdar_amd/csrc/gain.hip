@@ -105,128 +105,103 @@ static StepScratch<GainBufs> g_gn;
 
 void impdar_gain_forget(impdar_ctx *ctx) { g_gn.forget(ctx); }
 
-static bool gn_float(int dtype) { return dtype == IMPDAR_F32 || dtype == IMPDAR_F64; }
+static int rangegain_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *gain, const int *start)
+{
+    IMPDAR_ARG_CHECK(ctx && data && gain && start, "impdar_rangegain: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_rangegain: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_rangegain: empty radargram");
+    return IMPDAR_OK;
+}
 
 extern "C" int impdar_rangegain_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const double *gain,
                                     const int *start)
 {
     const auto lock = g_gn.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && gain && start, "impdar_rangegain: null argument");
-    IMPDAR_ARG_CHECK(gn_float(dtype), "impdar_rangegain: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_rangegain: empty radargram");
+    int rc = rangegain_check(ctx, d_data, dtype, snum, tnum, gain, start);
+    if (rc) return rc;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_gn.bind(ctx);
-    // the tables are small: one packed synchronous copy keeps the caller's host arrays free to go away (the stream
-    // is drained first because the previous launch may still read the table buffer)
-    const size_t db = (size_t)snum * sizeof(double), ib = (size_t)tnum * sizeof(int);
-    std::vector<char> pack(db + ib);
-    memcpy(pack.data(), gain, db);
-    memcpy(pack.data() + db, start, ib);
-    IMPDAR_HIP_CHECK(g_gn.tab.ensure(pack.size()));
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMPDAR_HIP_CHECK(hipMemcpy(g_gn.tab.p, pack.data(), pack.size(), hipMemcpyHostToDevice));
-    const double *d_gain = g_gn.tab.as<double>();
-    const int *d_start = (const int *)(g_gn.tab.as<char>() + db);
-    if (dtype == IMPDAR_F32) rowwise_launch(ctx, (float *)d_data, snum, tnum, RangeGain<float>{d_gain, d_start});
-    else rowwise_launch(ctx, (double *)d_data, snum, tnum, RangeGain<double>{d_gain, d_start});
+    const void *d_tab[2];
+    rc = impdar_upload_tables(ctx, g_gn.tab, {{gain, (size_t)snum * sizeof(double)}, {start, (size_t)tnum * sizeof(int)}}, d_tab);
+    if (rc) return rc;
+    rowwise_launch(ctx, d_data, dtype, snum, tnum, [&](auto t) {
+        return RangeGain<typename decltype(t)::type>{(const double *)d_tab[0], (const int *)d_tab[1]};
+    });
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
-}
-
-template <typename T, int V> static void agc_rowmax_launch(impdar_ctx *ctx, const void *d_data, double *d_rowmax, int snum, int tnum)
-{
-    const int nblk = snum < AG_MAX_ROW_BLOCKS ? snum : AG_MAX_ROW_BLOCKS;
-    hipLaunchKernelGGL((agc_rowmax_kernel<T, V>), dim3(nblk), dim3(AG_BLOCK), 0, ctx->stream, (const T *)d_data, d_rowmax,
-                       snum, tnum);
 }
 
 // max |x| of every row of a resident array into g_gn.rowmax
 static int gn_rowmax(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum)
 {
     IMPDAR_HIP_CHECK(g_gn.rowmax.ensure((size_t)snum * sizeof(double)));
-    double *d_rowmax = g_gn.rowmax.as<double>();
-    const bool wide = rw_aligned16(d_data);
-    if (dtype == IMPDAR_F32) {
-        if (wide && tnum % 4 == 0) agc_rowmax_launch<float, 4>(ctx, d_data, d_rowmax, snum, tnum);
-        else if (wide && tnum % 2 == 0) agc_rowmax_launch<float, 2>(ctx, d_data, d_rowmax, snum, tnum);
-        else agc_rowmax_launch<float, 1>(ctx, d_data, d_rowmax, snum, tnum);
-    } else {
-        if (wide && tnum % 2 == 0) agc_rowmax_launch<double, 2>(ctx, d_data, d_rowmax, snum, tnum);
-        else agc_rowmax_launch<double, 1>(ctx, d_data, d_rowmax, snum, tnum);
-    }
+    const int nblk = snum < AG_MAX_ROW_BLOCKS ? snum : AG_MAX_ROW_BLOCKS;
+    rw_dispatch(dtype, {d_data}, tnum, [&](auto t, auto v) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL((agc_rowmax_kernel<T, decltype(v)::value>), dim3(nblk), dim3(AG_BLOCK), 0, ctx->stream,
+                           (const T *)d_data, g_gn.rowmax.as<double>(), snum, tnum);
+    });
     IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
+}
+
+static int agc_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int half)
+{
+    IMPDAR_ARG_CHECK(ctx && data, "impdar_agc: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_agc: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_agc: empty radargram");
+    IMPDAR_ARG_CHECK(half >= 1, "impdar_agc: window // 2 = %d leaves no sample to take the maximum of", half);
     return IMPDAR_OK;
 }
 
 extern "C" int impdar_agc_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, int half, double scaling)
 {
     const auto lock = g_gn.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data, "impdar_agc: null argument");
-    IMPDAR_ARG_CHECK(gn_float(dtype), "impdar_agc: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_agc: empty radargram");
-    IMPDAR_ARG_CHECK(half >= 1, "impdar_agc: window // 2 = %d leaves no sample to take the maximum of", half);
+    int rc = agc_check(ctx, d_data, dtype, snum, tnum, half);
+    if (rc) return rc;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_gn.bind(ctx);
-    const int rc = gn_rowmax(ctx, d_data, dtype, snum, tnum);
+    rc = gn_rowmax(ctx, d_data, dtype, snum, tnum);
     if (rc) return rc;
     IMPDAR_HIP_CHECK(g_gn.scale.ensure((size_t)snum * impdar_dtype_size(dtype)));
     const dim3 grid((snum + AG_BLOCK - 1) / AG_BLOCK);
-    if (dtype == IMPDAR_F32) {
-        hipLaunchKernelGGL(agc_scale_kernel<float>, grid, dim3(AG_BLOCK), 0, ctx->stream, g_gn.rowmax.as<double>(),
-                           g_gn.scale.as<float>(), snum, half, scaling);
-        rowwise_launch(ctx, (float *)d_data, snum, tnum, RowScale<float>{g_gn.scale.as<float>()});
-    } else {
-        hipLaunchKernelGGL(agc_scale_kernel<double>, grid, dim3(AG_BLOCK), 0, ctx->stream, g_gn.rowmax.as<double>(),
-                           g_gn.scale.as<double>(), snum, half, scaling);
-        rowwise_launch(ctx, (double *)d_data, snum, tnum, RowScale<double>{g_gn.scale.as<double>()});
-    }
+    rw_typed(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(agc_scale_kernel<T>, grid, dim3(AG_BLOCK), 0, ctx->stream, g_gn.rowmax.as<double>(),
+                           g_gn.scale.as<T>(), snum, half, scaling);
+    });
+    rowwise_launch(ctx, d_data, dtype, snum, tnum,
+                   [&](auto t) { return RowScale<typename decltype(t)::type>{g_gn.scale.as<typename decltype(t)::type>()}; });
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
 }
 
-// ---- host-buffer forms: upload, run, download ------------------------------------------------------------
+// ---- host-buffer forms: the argument check, then StepScratch::host_form ----------------------------------
 
 extern "C" int impdar_rangegain(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const double *gain,
                                 const int *start)
 {
-    const auto lock = g_gn.lock();
-    IMPDAR_ARG_CHECK(ctx && data && gain && start, "impdar_rangegain: null argument");
-    IMPDAR_ARG_CHECK(gn_float(dtype), "impdar_rangegain: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_rangegain: empty radargram");
+    const int rc = rangegain_check(ctx, data, dtype, snum, tnum, gain, start);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_gn.stage_in(ctx, g_gn.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_rangegain_dev(ctx, g_gn.data.p, dtype, snum, tnum, gain, start);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_gn.data.p, bytes, ctx->stream);
+    return g_gn.host_form(ctx, g_gn.data, data, bytes, nullptr, data, bytes,
+                          [&](void *d, void *) { return impdar_rangegain_dev(ctx, d, dtype, snum, tnum, gain, start); });
 }
 
 extern "C" int impdar_agc(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, int half, double scaling)
 {
-    const auto lock = g_gn.lock();
-    IMPDAR_ARG_CHECK(ctx && data, "impdar_agc: null argument");
-    IMPDAR_ARG_CHECK(gn_float(dtype), "impdar_agc: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_agc: empty radargram");
-    IMPDAR_ARG_CHECK(half >= 1, "impdar_agc: window // 2 = %d leaves no sample to take the maximum of", half);
+    const int rc = agc_check(ctx, data, dtype, snum, tnum, half);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_gn.stage_in(ctx, g_gn.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_agc_dev(ctx, g_gn.data.p, dtype, snum, tnum, half, scaling);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_gn.data.p, bytes, ctx->stream);
+    return g_gn.host_form(ctx, g_gn.data, data, bytes, nullptr, data, bytes,
+                          [&](void *d, void *) { return impdar_agc_dev(ctx, d, dtype, snum, tnum, half, scaling); });
 }
 
 extern "C" int impdar_row_absmax(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, double *rowmax)
 {
-    const auto lock = g_gn.lock();
     IMPDAR_ARG_CHECK(ctx && data && rowmax, "impdar_row_absmax: null argument");
-    IMPDAR_ARG_CHECK(gn_float(dtype), "impdar_row_absmax: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_row_absmax: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_row_absmax: empty radargram");
-    int rc = g_gn.stage_in(ctx, g_gn.data, data, (size_t)snum * tnum * impdar_dtype_size(dtype));
-    if (rc) return rc;
-    rc = gn_rowmax(ctx, g_gn.data.p, dtype, snum, tnum);
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(rowmax, g_gn.rowmax.p, (size_t)snum * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return IMPDAR_OK;
+    return g_gn.host_form(ctx, g_gn.data, data, (size_t)snum * tnum * impdar_dtype_size(dtype), &g_gn.rowmax, rowmax,
+                          (size_t)snum * sizeof(double), [&](void *d, void *) { return gn_rowmax(ctx, d, dtype, snum, tnum); });
 }

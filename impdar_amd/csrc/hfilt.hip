@@ -196,11 +196,12 @@ static StepScratch<HfiltBufs> g_hf;
 
 void impdar_hfilt_forget(impdar_ctx *ctx) { g_hf.forget(ctx); }
 
-// the concatenation of `n` host blocks into the device table buffer, enqueued on the compute stream
-static int hf_upload_tables(impdar_ctx *ctx, const void *const *src, const size_t *bytes, int n)
+// the tables of `blk` into the device table buffer at 16-byte-rounded offsets, enqueued on the compute stream; their
+// device addresses into `dev`
+template <int N> static int hf_upload_tables(impdar_ctx *ctx, const TableBlock (&blk)[N], const void *(&dev)[N])
 {
     size_t total = 0;
-    for (int k = 0; k < n; ++k) total += (bytes[k] + 15) & ~(size_t)15;
+    for (int k = 0; k < N; ++k) total += impdar_round16(blk[k].bytes);
     if (g_hf.pending) IMPDAR_HIP_CHECK(hipEventSynchronize(g_hf.ev));
     g_hf.pending = false;
     if (!g_hf.ev) IMPDAR_HIP_CHECK(hipEventCreateWithFlags(&g_hf.ev, hipEventDisableTiming));
@@ -213,9 +214,10 @@ static int hf_upload_tables(impdar_ctx *ctx, const void *const *src, const size_
     }
     IMPDAR_HIP_CHECK(g_hf.tab.ensure(total));
     size_t off = 0;
-    for (int k = 0; k < n; ++k) {
-        memcpy((char *)g_hf.host + off, src[k], bytes[k]);
-        off += (bytes[k] + 15) & ~(size_t)15;
+    for (int k = 0; k < N; ++k) {
+        memcpy((char *)g_hf.host + off, blk[k].src, blk[k].bytes);
+        dev[k] = g_hf.tab.as<char>() + off;
+        off += impdar_round16(blk[k].bytes);
     }
     IMPDAR_HIP_CHECK(hipMemcpyAsync(g_hf.tab.p, g_hf.host, total, hipMemcpyHostToDevice, ctx->stream));
     IMPDAR_HIP_CHECK(hipEventRecord(g_hf.ev, ctx->stream));
@@ -223,154 +225,143 @@ static int hf_upload_tables(impdar_ctx *ctx, const void *const *src, const size_
     return IMPDAR_OK;
 }
 
-extern "C" int impdar_hfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, int lo, int hi,
-                                const double *scale)
+// the moving means of ahfilt and winavg: the scratch arrays, the three tables, the row-mean launch
+template <class Apply>
+static int hf_windowed(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                       const double *scale, const Apply &apply)
 {
-    const auto lock = g_hf.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && scale, "impdar_hfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfilt: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
-    IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_hf.bind(ctx);
-    const void *src[1] = {scale};
-    const size_t bytes[1] = {(size_t)snum * sizeof(double)};
-    int rc = hf_upload_tables(ctx, src, bytes, 1);
+    const int nblk = snum < HF_MAX_ROW_BLOCKS ? snum : HF_MAX_ROW_BLOCKS;
+    IMPDAR_HIP_CHECK(g_hf.M.ensure((size_t)snum * tnum * impdar_dtype_size(dtype)));
+    IMPDAR_HIP_CHECK(g_hf.P.ensure((size_t)nblk * (tnum + 1) * sizeof(double)));
+    const size_t ib = (size_t)tnum * sizeof(int);
+    const void *d_tab[3];
+    const int rc = hf_upload_tables(ctx, {{scale, (size_t)snum * sizeof(double)}, {lo, ib}, {hi, ib}}, d_tab);
     if (rc) return rc;
-    if (dtype == IMPDAR_F32)
-        hipLaunchKernelGGL(hfilt_mean_kernel<float>, dim3(snum), dim3(HF_BLOCK), 0, ctx->stream, (float *)d_data, tnum, lo,
-                           hi, g_hf.tab.as<double>());
-    else
-        hipLaunchKernelGGL(hfilt_mean_kernel<double>, dim3(snum), dim3(HF_BLOCK), 0, ctx->stream, (double *)d_data, tnum,
-                           lo, hi, g_hf.tab.as<double>());
+    rw_typed(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(ahfilt_rowmean_kernel<T>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream, (const T *)d_data,
+                           g_hf.M.as<T>(), g_hf.P.as<double>(), (const int *)d_tab[1], (const int *)d_tab[2], snum, tnum);
+    });
+    apply((const double *)d_tab[0]);
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
 }
 
-extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo,
-                                 const int *hi, const double *scale)
+static int hfilt_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int lo, int hi, const double *scale)
+{
+    IMPDAR_ARG_CHECK(ctx && data && scale, "impdar_hfilt: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_hfilt: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
+    IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_hfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, int lo, int hi,
+                                const double *scale)
 {
     const auto lock = g_hf.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && scale, "impdar_ahfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_ahfilt: dtype must be float32 or float64");
+    int rc = hfilt_check(ctx, d_data, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_hf.bind(ctx);
+    const void *d_tab[1];
+    rc = hf_upload_tables(ctx, {{scale, (size_t)snum * sizeof(double)}}, d_tab);
+    if (rc) return rc;
+    rw_typed(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(hfilt_mean_kernel<T>, dim3(snum), dim3(HF_BLOCK), 0, ctx->stream, (T *)d_data, tnum, lo, hi,
+                           (const double *)d_tab[0]);
+    });
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return impdar_ctx_mark_produced(ctx);
+}
+
+static int ahfilt_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                        const double *scale)
+{
+    IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_ahfilt: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_ahfilt: dtype must be float32 or float64");
     // scipy.signal.filtfilt's own guard and message (padlen = 3 * 4 taps)
     IMPDAR_ARG_CHECK(snum > 12, "The length of the input vector x must be greater than padlen, which is %d.", 12);
     IMPDAR_ARG_CHECK(tnum >= 1, "impdar_ahfilt: empty radargram");
     for (int i = 0; i < tnum; ++i)
         IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] <= tnum,
                          "impdar_ahfilt: window [%d, %d) of trace %d not inside [0, %d]", lo[i], hi[i], i, tnum);
-    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    g_hf.bind(ctx);
-    const size_t es = impdar_dtype_size(dtype);
-    const int nblk = snum < HF_MAX_ROW_BLOCKS ? snum : HF_MAX_ROW_BLOCKS;
-    IMPDAR_HIP_CHECK(g_hf.M.ensure((size_t)snum * tnum * es));
-    IMPDAR_HIP_CHECK(g_hf.P.ensure((size_t)nblk * (tnum + 1) * sizeof(double)));
-    const size_t db = (size_t)snum * sizeof(double), ib = (size_t)tnum * sizeof(int);
-    const void *src[3] = {scale, lo, hi};
-    const size_t bytes[3] = {db, ib, ib};
-    int rc = hf_upload_tables(ctx, src, bytes, 3);
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_ahfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo,
+                                 const int *hi, const double *scale)
+{
+    const auto lock = g_hf.lock();
+    const int rc = ahfilt_check(ctx, d_data, dtype, snum, tnum, lo, hi, scale);
     if (rc) return rc;
-    const double *d_scale = g_hf.tab.as<double>();
-    const int *d_lo = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15));
-    const int *d_hi = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15) + ((ib + 15) & ~(size_t)15));
     const dim3 grid2((tnum + 255) / 256, (snum + HF_ROWS - 1) / HF_ROWS);
-    if (dtype == IMPDAR_F32) {
-        hipLaunchKernelGGL(ahfilt_rowmean_kernel<float>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream, (const float *)d_data,
-                           g_hf.M.as<float>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
-        hipLaunchKernelGGL(ahfilt_apply_kernel<float>, grid2, dim3(256), 0, ctx->stream, (float *)d_data,
-                           (const float *)g_hf.M.as<float>(), d_scale, snum, tnum);
-    } else {
-        hipLaunchKernelGGL(ahfilt_rowmean_kernel<double>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream,
-                           (const double *)d_data, g_hf.M.as<double>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
-        hipLaunchKernelGGL(ahfilt_apply_kernel<double>, grid2, dim3(256), 0, ctx->stream, (double *)d_data,
-                           (const double *)g_hf.M.as<double>(), d_scale, snum, tnum);
-    }
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    return impdar_ctx_mark_produced(ctx);
+    return hf_windowed(ctx, d_data, dtype, snum, tnum, lo, hi, scale, [&](const double *d_scale) {
+        rw_typed(dtype, [&](auto t) {
+            typedef typename decltype(t)::type T;
+            hipLaunchKernelGGL(ahfilt_apply_kernel<T>, grid2, dim3(256), 0, ctx->stream, (T *)d_data, (const T *)g_hf.M.as<T>(),
+                               d_scale, snum, tnum);
+        });
+    });
+}
+
+static int winavg_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                        const double *scale)
+{
+    IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_winavg: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_winavg: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_winavg: empty radargram");
+    for (int i = 0; i < tnum; ++i)
+        IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] <= tnum,
+                         "impdar_winavg: window [%d, %d) of trace %d not inside [0, %d]", lo[i], hi[i], i, tnum);
+    return IMPDAR_OK;
 }
 
 extern "C" int impdar_winavg_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const int *lo,
                                  const int *hi, const double *scale)
 {
     const auto lock = g_hf.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && scale, "impdar_winavg: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_winavg: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_winavg: empty radargram");
-    for (int i = 0; i < tnum; ++i)
-        IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] <= hi[i] && hi[i] <= tnum,
-                         "impdar_winavg: window [%d, %d) of trace %d not inside [0, %d]", lo[i], hi[i], i, tnum);
-    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    g_hf.bind(ctx);
-    const size_t es = impdar_dtype_size(dtype);
-    const int nblk = snum < HF_MAX_ROW_BLOCKS ? snum : HF_MAX_ROW_BLOCKS;
-    IMPDAR_HIP_CHECK(g_hf.M.ensure((size_t)snum * tnum * es));
-    IMPDAR_HIP_CHECK(g_hf.P.ensure((size_t)nblk * (tnum + 1) * sizeof(double)));
-    const size_t db = (size_t)snum * sizeof(double), ib = (size_t)tnum * sizeof(int);
-    const void *src[3] = {scale, lo, hi};
-    const size_t bytes[3] = {db, ib, ib};
-    int rc = hf_upload_tables(ctx, src, bytes, 3);
+    const int rc = winavg_check(ctx, d_data, dtype, snum, tnum, lo, hi, scale);
     if (rc) return rc;
-    const double *d_scale = g_hf.tab.as<double>();
-    const int *d_lo = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15));
-    const int *d_hi = (const int *)(g_hf.tab.as<char>() + ((db + 15) & ~(size_t)15) + ((ib + 15) & ~(size_t)15));
-    if (dtype == IMPDAR_F32) {
-        hipLaunchKernelGGL(ahfilt_rowmean_kernel<float>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream, (const float *)d_data,
-                           g_hf.M.as<float>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
-        rowwise_launch(ctx, (float *)d_data, snum, tnum, WinavgApply<float>{g_hf.M.as<float>(), d_scale, tnum});
-    } else {
-        hipLaunchKernelGGL(ahfilt_rowmean_kernel<double>, dim3(nblk), dim3(HF_BLOCK), 0, ctx->stream,
-                           (const double *)d_data, g_hf.M.as<double>(), g_hf.P.as<double>(), d_lo, d_hi, snum, tnum);
-        rowwise_launch(ctx, (double *)d_data, snum, tnum, WinavgApply<double>{g_hf.M.as<double>(), d_scale, tnum});
-    }
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    return impdar_ctx_mark_produced(ctx);
+    return hf_windowed(ctx, d_data, dtype, snum, tnum, lo, hi, scale, [&](const double *d_scale) {
+        rowwise_launch(ctx, d_data, dtype, snum, tnum, [&](auto t) {
+            typedef typename decltype(t)::type T;
+            return WinavgApply<T>{g_hf.M.as<T>(), d_scale, tnum};
+        });
+    });
 }
 
-// ---- host-buffer forms: upload, run, download ------------------------------------------------------------
+// ---- host-buffer forms: the argument check, then StepScratch::host_form ----------------------------------
 
 extern "C" int impdar_hfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, int lo, int hi,
                             const double *scale)
 {
-    const auto lock = g_hf.lock();
-    IMPDAR_ARG_CHECK(ctx && data && scale, "impdar_hfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfilt: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfilt: empty radargram");
-    IMPDAR_ARG_CHECK(lo >= 0 && lo < hi && hi <= tnum, "impdar_hfilt: trace range [%d, %d) not inside [0, %d)", lo, hi, tnum);
+    const int rc = hfilt_check(ctx, data, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_hfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
+    return g_hf.host_form(ctx, g_hf.data, data, bytes, nullptr, data, bytes,
+                          [&](void *d, void *) { return impdar_hfilt_dev(ctx, d, dtype, snum, tnum, lo, hi, scale); });
 }
 
 extern "C" int impdar_ahfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
                              const double *scale)
 {
-    const auto lock = g_hf.lock();
-    IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_ahfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_ahfilt: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum > 12, "The length of the input vector x must be greater than padlen, which is %d.", 12);
-    IMPDAR_ARG_CHECK(tnum >= 1, "impdar_ahfilt: empty radargram");
+    const int rc = ahfilt_check(ctx, data, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_ahfilt_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
+    return g_hf.host_form(ctx, g_hf.data, data, bytes, nullptr, data, bytes,
+                          [&](void *d, void *) { return impdar_ahfilt_dev(ctx, d, dtype, snum, tnum, lo, hi, scale); });
 }
 
 extern "C" int impdar_winavg(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
                              const double *scale)
 {
-    const auto lock = g_hf.lock();
-    IMPDAR_ARG_CHECK(ctx && data && lo && hi && scale, "impdar_winavg: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_winavg: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_winavg: empty radargram");
+    const int rc = winavg_check(ctx, data, dtype, snum, tnum, lo, hi, scale);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_hf.stage_in(ctx, g_hf.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_winavg_dev(ctx, g_hf.data.p, dtype, snum, tnum, lo, hi, scale);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_hf.data.p, bytes, ctx->stream);
+    return g_hf.host_form(ctx, g_hf.data, data, bytes, nullptr, data, bytes,
+                          [&](void *d, void *) { return impdar_winavg_dev(ctx, d, dtype, snum, tnum, lo, hi, scale); });
 }

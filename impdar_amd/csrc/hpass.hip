@@ -213,12 +213,11 @@ static void hp_dispatch(impdar_ctx *ctx, const T *x, double *Y, double *out, int
     else hp_launch<T, 8, 2>(ctx, x, Y, out, snum, tnum, pad, nc, c);
 }
 
-extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const double *b,
-                                    const double *a, int ncoef, const double *zi, double *d_out)
+static int hfiltfilt_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *b, const double *a,
+                           int ncoef, const double *zi, const double *out)
 {
-    const auto lock = g_hp.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && b && a && zi && d_out, "impdar_hfiltfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfiltfilt: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(ctx && data && b && a && zi && out, "impdar_hfiltfilt: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_hfiltfilt: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(ncoef >= 2 && ncoef <= HP_MAX_COEF, "impdar_hfiltfilt: %d filter coefficients (2..%d supported)",
                      ncoef, HP_MAX_COEF);
     IMPDAR_ARG_CHECK(a[0] != 0.0, "impdar_hfiltfilt: a[0] is zero");
@@ -226,8 +225,18 @@ extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dty
     const int pad = 3 * ncoef;
     // scipy.signal.filtfilt's own guard and message
     IMPDAR_ARG_CHECK(tnum > pad, "The length of the input vector x must be greater than padlen, which is %d.", pad);
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F64 || d_out != d_data, "impdar_hfiltfilt: float32 input needs a separate output");
     IMPDAR_ARG_CHECK((long long)snum * (tnum + 2 * pad) < (1LL << 40), "impdar_hfiltfilt: radargram too large");
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const double *b,
+                                    const double *a, int ncoef, const double *zi, double *d_out)
+{
+    const auto lock = g_hp.lock();
+    const int rc = hfiltfilt_check(ctx, d_data, dtype, snum, tnum, b, a, ncoef, zi, d_out);
+    if (rc) return rc;
+    IMPDAR_ARG_CHECK(dtype == IMPDAR_F64 || d_out != d_data, "impdar_hfiltfilt: float32 input needs a separate output");
+    const int pad = 3 * ncoef;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     const FiltCoefs<HP_MAX_COEF> c = filt_coefs<HP_MAX_COEF>(b, a, zi, ncoef);
     g_hp.bind(ctx);
@@ -240,22 +249,16 @@ extern "C" int impdar_hfiltfilt_dev(impdar_ctx *ctx, const void *d_data, int dty
     return impdar_ctx_mark_produced(ctx);
 }
 
+// ---- host-buffer form: the argument check, then StepScratch::host_form (float64 runs in place) -------------
+
 extern "C" int impdar_hfiltfilt(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *b,
                                 const double *a, int ncoef, const double *zi, double *out)
 {
-    const auto lock = g_hp.lock();
-    IMPDAR_ARG_CHECK(ctx && data && out, "impdar_hfiltfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_hfiltfilt: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hfiltfilt: empty radargram");
+    const int rc = hfiltfilt_check(ctx, data, dtype, snum, tnum, b, a, ncoef, zi, out);
+    if (rc) return rc;
     const size_t ne = (size_t)snum * tnum;
-    int rc = g_hp.stage_in(ctx, g_hp.in, data, ne * impdar_dtype_size(dtype));
-    if (rc) return rc;
-    double *d_out = g_hp.in.as<double>();   // float64 runs in place
-    if (dtype == IMPDAR_F32) {
-        IMPDAR_HIP_CHECK(g_hp.out.ensure(ne * sizeof(double)));
-        d_out = g_hp.out.as<double>();
-    }
-    rc = impdar_hfiltfilt_dev(ctx, g_hp.in.p, dtype, snum, tnum, b, a, ncoef, zi, d_out);
-    if (rc) return rc;
-    return impdar_download(ctx, out, d_out, ne * sizeof(double), ctx->stream);
+    return g_hp.host_form(ctx, g_hp.in, data, ne * impdar_dtype_size(dtype), dtype == IMPDAR_F32 ? &g_hp.out : nullptr, out,
+                          ne * sizeof(double), [&](void *d_in, void *d_out) {
+                              return impdar_hfiltfilt_dev(ctx, d_in, dtype, snum, tnum, b, a, ncoef, zi, (double *)d_out);
+                          });
 }

@@ -276,19 +276,27 @@ static int filtfilt_dispatch(impdar_ctx *ctx, T *d, double *Y, int snum, int tnu
     return filtfilt_launch<T, FF_MAX_COEF>(ctx, d, Y, snum, tnum, edge, ncoef, c);
 }
 
+static int filtfilt_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *b, const double *a,
+                          int ncoef, const double *zi)
+{
+    IMPDAR_ARG_CHECK(ctx && data && b && a && zi, "impdar_filtfilt: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_filtfilt: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(ncoef >= 2 && ncoef <= FF_MAX_COEF, "impdar_filtfilt: %d filter coefficients (2..%d supported)", ncoef,
+                     FF_MAX_COEF);
+    IMPDAR_ARG_CHECK(a[0] != 0.0, "impdar_filtfilt: a[0] is zero");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_filtfilt: empty radargram");
+    // scipy.signal.filtfilt's own guard and message
+    IMPDAR_ARG_CHECK(snum > 3 * ncoef, "The length of the input vector x must be greater than padlen, which is %d.", 3 * ncoef);
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_filtfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const double *b,
                                    const double *a, int ncoef, const double *zi)
 {
     const auto lock = g_scr.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && b && a && zi, "impdar_filtfilt: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_filtfilt: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(ncoef >= 2 && ncoef <= FF_MAX_COEF, "impdar_filtfilt: %d filter coefficients (2..%d supported)", ncoef,
-                     FF_MAX_COEF);
-    IMPDAR_ARG_CHECK(a[0] != 0.0, "impdar_filtfilt: a[0] is zero");
+    const int bad = filtfilt_check(ctx, d_data, dtype, snum, tnum, b, a, ncoef, zi);
+    if (bad) return bad;
     const int edge = 3 * ncoef;
-    // scipy.signal.filtfilt's own guard and message
-    IMPDAR_ARG_CHECK(snum > edge, "The length of the input vector x must be greater than padlen, which is %d.", edge);
-    IMPDAR_ARG_CHECK(tnum >= 1, "impdar_filtfilt: empty radargram");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     const FiltCoefs<FF_MAX_COEF> c = filt_coefs<FF_MAX_COEF>(b, a, zi, ncoef);
     g_scr.bind(ctx);
@@ -299,14 +307,21 @@ extern "C" int impdar_filtfilt_dev(impdar_ctx *ctx, void *d_data, int dtype, int
     return rc ? rc : impdar_ctx_mark_produced(ctx);
 }
 
+static int fir_shift_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *taps, int ntaps)
+{
+    IMPDAR_ARG_CHECK(ctx && data && taps, "impdar_fir_shift: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_fir_shift: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(ntaps >= 1 && ntaps <= 256, "impdar_fir_shift: %d taps (1..256 supported)", ntaps);
+    IMPDAR_ARG_CHECK(tnum >= 1 && snum >= 1, "impdar_fir_shift: empty radargram");
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_fir_shift_dev(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const double *taps,
                                     int ntaps)
 {
     const auto lock = g_scr.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && taps, "impdar_fir_shift: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_fir_shift: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(ntaps >= 1 && ntaps <= 256, "impdar_fir_shift: %d taps (1..256 supported)", ntaps);
-    IMPDAR_ARG_CHECK(tnum >= 1 && snum >= 1, "impdar_fir_shift: empty radargram");
+    const int rc = fir_shift_check(ctx, d_data, dtype, snum, tnum, taps, ntaps);
+    if (rc) return rc;
     const int order = ntaps - 1;
     if (snum <= order) return IMPDAR_OK;   // data[:-order] is empty: nothing is assigned
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
@@ -328,33 +343,33 @@ extern "C" int impdar_fir_shift_dev(impdar_ctx *ctx, void *d_data, int dtype, in
     return impdar_ctx_mark_produced(ctx);
 }
 
+static int trace_lerp_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                            const double *den, const double *t, int n_new, const double *out)
+{
+    IMPDAR_ARG_CHECK(ctx && data && lo && hi && den && t && out, "impdar_trace_lerp: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_trace_lerp: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 2 && n_new >= 0, "impdar_trace_lerp: bad shape %d x %d -> %d", snum, tnum, n_new);
+    for (int m = 0; m < n_new; ++m)
+        IMPDAR_ARG_CHECK(lo[m] >= 0 && lo[m] < tnum && hi[m] >= 0 && hi[m] < tnum, "impdar_trace_lerp: column index out of range at %d",
+                         m);
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_trace_lerp_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const int *lo,
                                      const int *hi, const double *den, const double *t, int n_new, double *d_out)
 {
     const auto lock = g_scr.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && den && t && d_out, "impdar_trace_lerp: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_trace_lerp: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 2 && n_new >= 0, "impdar_trace_lerp: bad shape %d x %d -> %d", snum, tnum, n_new);
+    int rc = trace_lerp_check(ctx, d_data, dtype, snum, tnum, lo, hi, den, t, n_new, d_out);
+    if (rc) return rc;
     if (n_new == 0) return IMPDAR_OK;
-    for (int m = 0; m < n_new; ++m)
-        IMPDAR_ARG_CHECK(lo[m] >= 0 && lo[m] < tnum && hi[m] >= 0 && hi[m] < tnum, "impdar_trace_lerp: column index out of range at %d",
-                         m);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_scr.bind(ctx);
     const size_t ib = (size_t)n_new * sizeof(int), db = (size_t)n_new * sizeof(double);
-    IMPDAR_HIP_CHECK(g_scr.idx.ensure(2 * ib + 2 * db + 64));
-    char *base = g_scr.idx.as<char>();
-    double *d_den = (double *)base, *d_t = (double *)(base + db);
-    int *d_lo = (int *)(base + 2 * db), *d_hi = (int *)(base + 2 * db + ib);
-    // the tables are small: one packed synchronous copy keeps the caller's host arrays free to go away (the
-    // stream is drained first because the previous launch may still read the table buffer)
-    std::vector<char> pack(2 * ib + 2 * db);
-    memcpy(pack.data(), den, db);
-    memcpy(pack.data() + db, t, db);
-    memcpy(pack.data() + 2 * db, lo, ib);
-    memcpy(pack.data() + 2 * db + ib, hi, ib);
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMPDAR_HIP_CHECK(hipMemcpy(base, pack.data(), pack.size(), hipMemcpyHostToDevice));
+    const void *d_tab[4];
+    rc = impdar_upload_tables(ctx, g_scr.idx, {{den, db}, {t, db}, {lo, ib}, {hi, ib}}, d_tab);
+    if (rc) return rc;
+    const double *d_den = (const double *)d_tab[0], *d_t = (const double *)d_tab[1];
+    const int *d_lo = (const int *)d_tab[2], *d_hi = (const int *)d_tab[3];
     const dim3 grid((n_new + 255) / 256, (snum + LERP_ROWS - 1) / LERP_ROWS);
     if (dtype == IMPDAR_F32)
         hipLaunchKernelGGL(trace_lerp_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float *)d_data, d_out, snum,
@@ -377,7 +392,7 @@ __global__ __launch_bounds__(256) void cast_kernel(const TI *__restrict__ in, TO
 extern "C" int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n)
 {
     IMPDAR_ARG_CHECK(ctx && d_src && d_dst, "impdar_cast_dev: null argument");
-    IMPDAR_ARG_CHECK((src_dtype == IMPDAR_F32 || src_dtype == IMPDAR_F64) && (dst_dtype == IMPDAR_F32 || dst_dtype == IMPDAR_F64),
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(src_dtype) && impdar_dtype_ok(dst_dtype),
                      "impdar_cast_dev: dtypes must be float32 or float64");
     if (n == 0) return IMPDAR_OK;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
@@ -394,47 +409,36 @@ extern "C" int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype
     return impdar_ctx_mark_produced(ctx);
 }
 
-// ---- host-buffer forms: upload, run, download ------------------------------------------------------------
+// ---- host-buffer forms: the argument check, then StepScratch::host_form ----------------------------------
 
 extern "C" int impdar_filtfilt(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const double *b,
                                const double *a, int ncoef, const double *zi)
 {
-    const auto lock = g_scr.lock();
-    IMPDAR_ARG_CHECK(ctx && data, "impdar_filtfilt: null argument");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_filtfilt: empty radargram");
+    const int rc = filtfilt_check(ctx, data, dtype, snum, tnum, b, a, ncoef, zi);
+    if (rc) return rc;
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_scr.stage_in(ctx, g_scr.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_filtfilt_dev(ctx, g_scr.data.p, dtype, snum, tnum, b, a, ncoef, zi);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_scr.data.p, bytes, ctx->stream);
+    return g_scr.host_form(ctx, g_scr.data, data, bytes, nullptr, data, bytes,
+                           [&](void *d, void *) { return impdar_filtfilt_dev(ctx, d, dtype, snum, tnum, b, a, ncoef, zi); });
 }
 
 extern "C" int impdar_fir_shift(impdar_ctx *ctx, void *data, int dtype, int snum, int tnum, const double *taps, int ntaps)
 {
-    const auto lock = g_scr.lock();
-    IMPDAR_ARG_CHECK(ctx && data, "impdar_fir_shift: null argument");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_fir_shift: empty radargram");
+    const int rc = fir_shift_check(ctx, data, dtype, snum, tnum, taps, ntaps);
+    if (rc) return rc;
+    if (snum <= ntaps - 1) return IMPDAR_OK;   // as the resident form: nothing is assigned
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_scr.stage_in(ctx, g_scr.data, data, bytes);
-    if (rc) return rc;
-    rc = impdar_fir_shift_dev(ctx, g_scr.data.p, dtype, snum, tnum, taps, ntaps);
-    if (rc) return rc;
-    return impdar_download(ctx, data, g_scr.data.p, bytes, ctx->stream);
+    return g_scr.host_form(ctx, g_scr.data, data, bytes, nullptr, data, bytes,
+                           [&](void *d, void *) { return impdar_fir_shift_dev(ctx, d, dtype, snum, tnum, taps, ntaps); });
 }
 
 extern "C" int impdar_trace_lerp(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo,
                                  const int *hi, const double *den, const double *t, int n_new, double *out)
 {
-    const auto lock = g_scr.lock();
-    IMPDAR_ARG_CHECK(ctx && data && out, "impdar_trace_lerp: null argument");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 2 && n_new >= 0, "impdar_trace_lerp: bad shape %d x %d -> %d", snum, tnum, n_new);
+    const int rc = trace_lerp_check(ctx, data, dtype, snum, tnum, lo, hi, den, t, n_new, out);
+    if (rc) return rc;
     if (n_new == 0) return IMPDAR_OK;
-    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
-    int rc = g_scr.stage_in(ctx, g_scr.data, data, bytes);
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(g_scr.aux.ensure((size_t)snum * n_new * sizeof(double)));
-    rc = impdar_trace_lerp_dev(ctx, g_scr.data.p, dtype, snum, tnum, lo, hi, den, t, n_new, g_scr.aux.as<double>());
-    if (rc) return rc;
-    return impdar_download(ctx, out, g_scr.aux.p, (size_t)snum * n_new * sizeof(double), ctx->stream);
+    return g_scr.host_form(ctx, g_scr.data, data, (size_t)snum * tnum * impdar_dtype_size(dtype), &g_scr.aux, out,
+                           (size_t)snum * n_new * sizeof(double), [&](void *d_in, void *d_out) {
+                               return impdar_trace_lerp_dev(ctx, d_in, dtype, snum, tnum, lo, hi, den, t, n_new, (double *)d_out);
+                           });
 }

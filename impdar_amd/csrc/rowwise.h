@@ -2,28 +2,10 @@
 // that depend on the row (a gain, a taper) or on the trace (a start row): rangegain and agc of gain.hip, the apply
 // pass of winavg_hfilt in hfilt.hip.  They do nothing a copy does not do: one read and one write of the array.
 #pragma once
-#include "common.h"
+#include "vecwidth.h"
 
 #define RW_ROWS 4            // consecutive rows per thread and trip: that many 16-byte loads in flight
 #define RW_MAX_BLOCKS 2048   // resident workgroups (8 per CU); the rows beyond are reached by a grid stride
-
-// at most 16 bytes of alignment: that is what the host checks, and the widest single access
-template <typename T, int V> struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) RwVec {
-    T v[V];
-};
-
-// one access of V elements through the native vector type (the struct alone may be split into narrower loads)
-template <typename T, int V> __device__ __forceinline__ RwVec<T, V> rw_load(const T *p)
-{
-    typedef T Native __attribute__((ext_vector_type(V)));
-    const Native n = *reinterpret_cast<const Native *>(p);
-    RwVec<T, V> r;
-#pragma unroll
-    for (int c = 0; c < V; ++c) r.v[c] = n[c];
-    return r;
-}
-
-static inline bool rw_aligned16(const void *p) { return ((size_t)p & 15) == 0; }
 
 // A thread owns V consecutive traces (one 16-byte access for float32 x 4 and float64 x 2) and walks the rows
 // RW_ROWS at a time.  `f(i, j, y)` rewrites the V values y of row i, traces j .. j + V - 1.  V is chosen by the host
@@ -62,18 +44,11 @@ static void rowwise_launch_v(impdar_ctx *ctx, T *d_data, int snum, int tnum, con
     hipLaunchKernelGGL((rowwise_kernel<T, V, F>), grid, dim3(256), 0, ctx->stream, d_data, snum, tnum, f);
 }
 
-// the widest access every row start allows: 16 bytes when the array is 16-byte aligned and the row pitch a
-// multiple of it, else a narrower form for the whole array
-template <class F> static void rowwise_launch(impdar_ctx *ctx, float *d_data, int snum, int tnum, const F &f)
+// `make(RwType<T>())` gives the functor for the dtype; the access width is rw_dispatch's
+template <class Make> static void rowwise_launch(impdar_ctx *ctx, void *d_data, int dtype, int snum, int tnum, const Make &make)
 {
-    const bool wide = rw_aligned16(d_data);
-    if (wide && tnum % 4 == 0) rowwise_launch_v<float, 4>(ctx, d_data, snum, tnum, f);
-    else if (wide && tnum % 2 == 0) rowwise_launch_v<float, 2>(ctx, d_data, snum, tnum, f);
-    else rowwise_launch_v<float, 1>(ctx, d_data, snum, tnum, f);
-}
-
-template <class F> static void rowwise_launch(impdar_ctx *ctx, double *d_data, int snum, int tnum, const F &f)
-{
-    if (rw_aligned16(d_data) && tnum % 2 == 0) rowwise_launch_v<double, 2>(ctx, d_data, snum, tnum, f);
-    else rowwise_launch_v<double, 1>(ctx, d_data, snum, tnum, f);
+    rw_dispatch(dtype, {d_data}, tnum, [&](auto t, auto v) {
+        typedef typename decltype(t)::type T;
+        rowwise_launch_v<T, decltype(v)::value>(ctx, (T *)d_data, snum, tnum, make(t));
+    });
 }

@@ -130,8 +130,6 @@ static StepScratch<TaxisBufs> g_tx;
 
 void impdar_taxis_forget(impdar_ctx *ctx) { g_tx.forget(ctx); }
 
-static bool tx_float(int dtype) { return dtype == IMPDAR_F32 || dtype == IMPDAR_F64; }
-
 template <typename T, int V>
 static void restack_launch(impdar_ctx *ctx, const void *d_data, double *d_out, int snum, int tnum, int traces, int tnum_new)
 {
@@ -150,27 +148,28 @@ static void restack_launch(impdar_ctx *ctx, const void *d_data, double *d_out, i
     }
 }
 
+static int restack_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int traces, const double *out)
+{
+    IMPDAR_ARG_CHECK(ctx && data && out, "impdar_restack: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_restack: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_restack: empty radargram");
+    IMPDAR_ARG_CHECK(traces >= 1 && traces % 2 == 1, "impdar_restack: %d traces per stack (an odd number, at least 1)", traces);
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_restack_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int traces,
                                   double *d_out)
 {
     const auto lock = g_tx.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && d_out, "impdar_restack: null argument");
-    IMPDAR_ARG_CHECK(tx_float(dtype), "impdar_restack: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_restack: empty radargram");
-    IMPDAR_ARG_CHECK(traces >= 1 && traces % 2 == 1, "impdar_restack: %d traces per stack (an odd number, at least 1)", traces);
+    const int rc = restack_check(ctx, d_data, dtype, snum, tnum, traces, d_out);
+    if (rc) return rc;
     const int tnum_new = tnum / traces;
     if (tnum_new == 0) return IMPDAR_OK;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_tx.bind(ctx);
-    const bool wide = rw_aligned16(d_data);
-    if (dtype == IMPDAR_F32) {
-        if (wide && tnum % 4 == 0) restack_launch<float, 4>(ctx, d_data, d_out, snum, tnum, traces, tnum_new);
-        else if (wide && tnum % 2 == 0) restack_launch<float, 2>(ctx, d_data, d_out, snum, tnum, traces, tnum_new);
-        else restack_launch<float, 1>(ctx, d_data, d_out, snum, tnum, traces, tnum_new);
-    } else {
-        if (wide && tnum % 2 == 0) restack_launch<double, 2>(ctx, d_data, d_out, snum, tnum, traces, tnum_new);
-        else restack_launch<double, 1>(ctx, d_data, d_out, snum, tnum, traces, tnum_new);
-    }
+    rw_dispatch(dtype, {d_data}, tnum, [&](auto t, auto v) {
+        restack_launch<typename decltype(t)::type, decltype(v)::value>(ctx, d_data, d_out, snum, tnum, traces, tnum_new);
+    });
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
 }
@@ -189,18 +188,12 @@ extern "C" int impdar_reverse_dev(impdar_ctx *ctx, void *d_data, int dtype, int 
 {
     const auto lock = g_tx.lock();
     IMPDAR_ARG_CHECK(ctx && d_data, "impdar_reverse: null argument");
-    IMPDAR_ARG_CHECK(tx_float(dtype), "impdar_reverse: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_reverse: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_reverse: empty radargram");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
-    const bool wide = rw_aligned16(d_data);
-    if (dtype == IMPDAR_F32) {
-        if (wide && tnum % 4 == 0) reverse_launch<float, 4>(ctx, d_data, snum, tnum);
-        else if (wide && tnum % 2 == 0) reverse_launch<float, 2>(ctx, d_data, snum, tnum);
-        else reverse_launch<float, 1>(ctx, d_data, snum, tnum);
-    } else {
-        if (wide && tnum % 2 == 0) reverse_launch<double, 2>(ctx, d_data, snum, tnum);
-        else reverse_launch<double, 1>(ctx, d_data, snum, tnum);
-    }
+    rw_dispatch(dtype, {d_data}, tnum, [&](auto t, auto v) {
+        reverse_launch<typename decltype(t)::type, decltype(v)::value>(ctx, d_data, snum, tnum);
+    });
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
 }
@@ -209,7 +202,7 @@ extern "C" int impdar_hcrop_dev(impdar_ctx *ctx, const void *d_data, int dtype, 
                                 void *d_out)
 {
     IMPDAR_ARG_CHECK(ctx && d_data && d_out, "impdar_hcrop: null argument");
-    IMPDAR_ARG_CHECK(tx_float(dtype), "impdar_hcrop: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_hcrop: dtype must be float32 or float64");
     IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_hcrop: empty radargram");
     IMPDAR_ARG_CHECK(lo >= 0 && lo <= hi && hi <= tnum, "impdar_hcrop: trace range [%d, %d) not inside [0, %d]", lo, hi, tnum);
     if (hi == lo) return IMPDAR_OK;
@@ -220,22 +213,16 @@ extern "C" int impdar_hcrop_dev(impdar_ctx *ctx, const void *d_data, int dtype, 
     return impdar_ctx_mark_produced(ctx);
 }
 
-// ---- host-buffer form: upload, run, download ---------------------------------------------------------------
+// ---- host-buffer form: the argument check, then StepScratch::host_form -------------------------------------
 
 extern "C" int impdar_restack(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int traces, double *out)
 {
-    const auto lock = g_tx.lock();
-    IMPDAR_ARG_CHECK(ctx && data && out, "impdar_restack: null argument");
-    IMPDAR_ARG_CHECK(tx_float(dtype), "impdar_restack: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1, "impdar_restack: empty radargram");
-    IMPDAR_ARG_CHECK(traces >= 1 && traces % 2 == 1, "impdar_restack: %d traces per stack (an odd number, at least 1)", traces);
+    const int rc = restack_check(ctx, data, dtype, snum, tnum, traces, out);
+    if (rc) return rc;
     const int tnum_new = tnum / traces;
     if (tnum_new == 0) return IMPDAR_OK;
-    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype), obytes = (size_t)snum * tnum_new * sizeof(double);
-    int rc = g_tx.stage_in(ctx, g_tx.data, data, bytes);
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(g_tx.out.ensure(obytes));
-    rc = impdar_restack_dev(ctx, g_tx.data.p, dtype, snum, tnum, traces, g_tx.out.as<double>());
-    if (rc) return rc;
-    return impdar_download(ctx, out, g_tx.out.p, obytes, ctx->stream);
+    return g_tx.host_form(ctx, g_tx.data, data, (size_t)snum * tnum * impdar_dtype_size(dtype), &g_tx.out, out,
+                          (size_t)snum * tnum_new * sizeof(double), [&](void *d_in, void *d_out) {
+                              return impdar_restack_dev(ctx, d_in, dtype, snum, tnum, traces, (double *)d_out);
+                          });
 }

@@ -12,14 +12,9 @@
 // not, apart from the second row read of the blend: they are HBM-streaming kernels.  The file is compiled with
 // -ffp-contract=off; the blend is in scipy's operation order (the difference in the data's own arithmetic,
 // everything after it in fp64), as trace_lerp_kernel of preproc.hip.
-#include "common.h"
+#include "vecwidth.h"
 
 #define VA_ROWS 8   // consecutive output rows per thread
-
-// at most 16 bytes of alignment: that is what the host checks, and the widest single access
-template <typename T, int V> struct alignas(sizeof(T) * V < 16 ? sizeof(T) * V : 16) VaVec {
-    T v[V];
-};
 
 // A thread owns V consecutive traces (one 16-byte load for float32 x 4 and float64 x 2) of VA_ROWS consecutive
 // output rows.  The rows a row group reads are the same or neighbouring ones (a move-out stretches by a few per
@@ -34,8 +29,8 @@ __global__ __launch_bounds__(256) void row_lerp_kernel(const T *__restrict__ x, 
                                                        int n_out, const int *__restrict__ lo, const int *__restrict__ hi,
                                                        const double *__restrict__ den, const double *__restrict__ t)
 {
-    typedef VaVec<T, V> In;
-    typedef VaVec<double, V> Out;
+    typedef RwVec<T, V> In;
+    typedef RwVec<double, V> Out;
     const int j = (blockIdx.x * 256 + threadIdx.x) * V;
     if (j >= tnum) return;
     const int i0 = blockIdx.y * VA_ROWS;
@@ -69,7 +64,7 @@ template <typename T, int V>
 __global__ __launch_bounds__(256) void col_shift_kernel(const T *__restrict__ x, double *__restrict__ out, int snum,
                                                         int tnum, int n_out, const int *__restrict__ shift)
 {
-    typedef VaVec<double, V> Out;
+    typedef RwVec<double, V> Out;
     const int j = (blockIdx.x * 256 + threadIdx.x) * V;
     if (j >= tnum) return;
     const int i0 = blockIdx.y * VA_ROWS;
@@ -111,18 +106,6 @@ static StepScratch<VaxisBufs> g_va;
 
 void impdar_vaxis_forget(impdar_ctx *ctx) { g_va.forget(ctx); }
 
-// the tables are small: one packed synchronous copy keeps the caller's host arrays free to go away (the stream
-// is drained first because the previous launch may still read the table buffer)
-static int va_upload_tables(impdar_ctx *ctx, const std::vector<char> &pack)
-{
-    IMPDAR_HIP_CHECK(g_va.idx.ensure(pack.size() + 64));
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    IMPDAR_HIP_CHECK(hipMemcpy(g_va.idx.p, pack.data(), pack.size(), hipMemcpyHostToDevice));
-    return IMPDAR_OK;
-}
-
-static bool va_aligned16(const void *p) { return ((size_t)p & 15) == 0; }
-
 template <typename T, int V>
 static void row_lerp_launch(impdar_ctx *ctx, const void *d_data, double *d_out, int tnum, int n_out, const int *d_lo,
                             const int *d_hi, const double *d_den, const double *d_t)
@@ -132,41 +115,38 @@ static void row_lerp_launch(impdar_ctx *ctx, const void *d_data, double *d_out, 
                        d_lo, d_hi, d_den, d_t);
 }
 
+static int row_lerp_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo, const int *hi,
+                          const double *den, const double *t, int n_out, const double *out)
+{
+    IMPDAR_ARG_CHECK(ctx && data && lo && hi && den && t && out, "impdar_row_lerp: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_row_lerp: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1 && n_out >= 0, "impdar_row_lerp: bad shape %d x %d -> %d rows", snum, tnum, n_out);
+    IMPDAR_ARG_CHECK((size_t)n_out <= (size_t)65535 * VA_ROWS, "impdar_row_lerp: %d output rows (at most %d)", n_out,
+                     65535 * VA_ROWS);
+    for (int i = 0; i < n_out; ++i)
+        IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] < snum && hi[i] >= 0 && hi[i] < snum, "impdar_row_lerp: row index out of range at %d", i);
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_row_lerp_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const int *lo,
                                    const int *hi, const double *den, const double *t, int n_out, double *d_out)
 {
     const auto lock = g_va.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && lo && hi && den && t && d_out, "impdar_row_lerp: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_row_lerp: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1 && n_out >= 0, "impdar_row_lerp: bad shape %d x %d -> %d rows", snum, tnum, n_out);
-    IMPDAR_ARG_CHECK((size_t)n_out <= (size_t)65535 * VA_ROWS, "impdar_row_lerp: %d output rows (at most %d)", n_out,
-                     65535 * VA_ROWS);
+    int rc = row_lerp_check(ctx, d_data, dtype, snum, tnum, lo, hi, den, t, n_out, d_out);
+    if (rc) return rc;
     if (n_out == 0) return IMPDAR_OK;
-    for (int i = 0; i < n_out; ++i)
-        IMPDAR_ARG_CHECK(lo[i] >= 0 && lo[i] < snum && hi[i] >= 0 && hi[i] < snum, "impdar_row_lerp: row index out of range at %d", i);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_va.bind(ctx);
     const size_t ib = (size_t)n_out * sizeof(int), db = (size_t)n_out * sizeof(double);
-    std::vector<char> pack(2 * ib + 2 * db);
-    memcpy(pack.data(), den, db);
-    memcpy(pack.data() + db, t, db);
-    memcpy(pack.data() + 2 * db, lo, ib);
-    memcpy(pack.data() + 2 * db + ib, hi, ib);
-    const int rc = va_upload_tables(ctx, pack);
+    const void *d_tab[4];
+    rc = impdar_upload_tables(ctx, g_va.idx, {{den, db}, {t, db}, {lo, ib}, {hi, ib}}, d_tab);
     if (rc) return rc;
-    char *base = g_va.idx.as<char>();
-    const double *d_den = (const double *)base, *d_t = (const double *)(base + db);
-    const int *d_lo = (const int *)(base + 2 * db), *d_hi = (const int *)(base + 2 * db + ib);
     // 16-byte accesses need every row on a 16-byte boundary: the arrays themselves and the row pitch
-    const bool wide = va_aligned16(d_data) && va_aligned16(d_out);
-    if (dtype == IMPDAR_F32) {
-        if (wide && tnum % 4 == 0) row_lerp_launch<float, 4>(ctx, d_data, d_out, tnum, n_out, d_lo, d_hi, d_den, d_t);
-        else if (wide && tnum % 2 == 0) row_lerp_launch<float, 2>(ctx, d_data, d_out, tnum, n_out, d_lo, d_hi, d_den, d_t);
-        else row_lerp_launch<float, 1>(ctx, d_data, d_out, tnum, n_out, d_lo, d_hi, d_den, d_t);
-    } else {
-        if (wide && tnum % 2 == 0) row_lerp_launch<double, 2>(ctx, d_data, d_out, tnum, n_out, d_lo, d_hi, d_den, d_t);
-        else row_lerp_launch<double, 1>(ctx, d_data, d_out, tnum, n_out, d_lo, d_hi, d_den, d_t);
-    }
+    rw_dispatch(dtype, {d_data, d_out}, tnum, [&](auto ty, auto v) {
+        row_lerp_launch<typename decltype(ty)::type, decltype(v)::value>(ctx, d_data, d_out, tnum, n_out, (const int *)d_tab[2],
+                                                                         (const int *)d_tab[3], (const double *)d_tab[0],
+                                                                         (const double *)d_tab[1]);
+    });
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
 }
@@ -180,67 +160,59 @@ static void col_shift_launch(impdar_ctx *ctx, const void *d_data, double *d_out,
                        n_out, d_shift);
 }
 
+static int col_shift_check(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *shift, int n_out,
+                           const double *out)
+{
+    IMPDAR_ARG_CHECK(ctx && data && shift && out, "impdar_col_shift: null argument");
+    IMPDAR_ARG_CHECK(impdar_dtype_ok(dtype), "impdar_col_shift: dtype must be float32 or float64");
+    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1 && n_out >= 0, "impdar_col_shift: bad shape %d x %d -> %d rows", snum, tnum, n_out);
+    IMPDAR_ARG_CHECK((size_t)n_out <= (size_t)65535 * VA_ROWS, "impdar_col_shift: %d output rows (at most %d)", n_out,
+                     65535 * VA_ROWS);
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_col_shift_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const int *shift,
                                     int n_out, double *d_out)
 {
     const auto lock = g_va.lock();
-    IMPDAR_ARG_CHECK(ctx && d_data && shift && d_out, "impdar_col_shift: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_col_shift: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1 && n_out >= 0, "impdar_col_shift: bad shape %d x %d -> %d rows", snum, tnum, n_out);
-    IMPDAR_ARG_CHECK((size_t)n_out <= (size_t)65535 * VA_ROWS, "impdar_col_shift: %d output rows (at most %d)", n_out,
-                     65535 * VA_ROWS);
+    int rc = col_shift_check(ctx, d_data, dtype, snum, tnum, shift, n_out, d_out);
+    if (rc) return rc;
     if (n_out == 0) return IMPDAR_OK;
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     g_va.bind(ctx);
-    std::vector<char> pack((size_t)tnum * sizeof(int));
-    memcpy(pack.data(), shift, pack.size());
-    const int rc = va_upload_tables(ctx, pack);
+    const void *d_tab[1];
+    rc = impdar_upload_tables(ctx, g_va.idx, {{shift, (size_t)tnum * sizeof(int)}}, d_tab);
     if (rc) return rc;
-    const int *d_shift = g_va.idx.as<int>();
-    const bool wide = va_aligned16(d_out) && tnum % 2 == 0;
-    if (dtype == IMPDAR_F32) {
-        if (wide) col_shift_launch<float, 2>(ctx, d_data, d_out, snum, tnum, n_out, d_shift);
-        else col_shift_launch<float, 1>(ctx, d_data, d_out, snum, tnum, n_out, d_shift);
-    } else {
-        if (wide) col_shift_launch<double, 2>(ctx, d_data, d_out, snum, tnum, n_out, d_shift);
-        else col_shift_launch<double, 1>(ctx, d_data, d_out, snum, tnum, n_out, d_shift);
-    }
+    // the loads are scalar: only the stores of the float64 output are vectors, two of them at the most
+    rw_dispatch<2>(dtype, {d_out}, tnum, [&](auto t, auto v) {
+        col_shift_launch<typename decltype(t)::type, decltype(v)::value>(ctx, d_data, d_out, snum, tnum, n_out, (const int *)d_tab[0]);
+    });
     IMPDAR_HIP_CHECK(hipGetLastError());
     return impdar_ctx_mark_produced(ctx);
 }
 
-// ---- host-buffer forms: upload, run, download ------------------------------------------------------------
+// ---- host-buffer forms: the argument check, then StepScratch::host_form ----------------------------------
 
 extern "C" int impdar_row_lerp(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *lo,
                                const int *hi, const double *den, const double *t, int n_out, double *out)
 {
-    const auto lock = g_va.lock();
-    IMPDAR_ARG_CHECK(ctx && data && out, "impdar_row_lerp: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_row_lerp: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1 && n_out >= 0, "impdar_row_lerp: bad shape %d x %d -> %d rows", snum, tnum, n_out);
+    const int rc = row_lerp_check(ctx, data, dtype, snum, tnum, lo, hi, den, t, n_out, out);
+    if (rc) return rc;
     if (n_out == 0) return IMPDAR_OK;
-    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype), obytes = (size_t)n_out * tnum * sizeof(double);
-    int rc = g_va.stage_in(ctx, g_va.data, data, bytes);
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(g_va.out.ensure(obytes));
-    rc = impdar_row_lerp_dev(ctx, g_va.data.p, dtype, snum, tnum, lo, hi, den, t, n_out, g_va.out.as<double>());
-    if (rc) return rc;
-    return impdar_download(ctx, out, g_va.out.p, obytes, ctx->stream);
+    return g_va.host_form(ctx, g_va.data, data, (size_t)snum * tnum * impdar_dtype_size(dtype), &g_va.out, out,
+                          (size_t)n_out * tnum * sizeof(double), [&](void *d_in, void *d_out) {
+                              return impdar_row_lerp_dev(ctx, d_in, dtype, snum, tnum, lo, hi, den, t, n_out, (double *)d_out);
+                          });
 }
 
 extern "C" int impdar_col_shift(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *shift,
                                 int n_out, double *out)
 {
-    const auto lock = g_va.lock();
-    IMPDAR_ARG_CHECK(ctx && data && out, "impdar_col_shift: null argument");
-    IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "impdar_col_shift: dtype must be float32 or float64");
-    IMPDAR_ARG_CHECK(snum >= 1 && tnum >= 1 && n_out >= 0, "impdar_col_shift: bad shape %d x %d -> %d rows", snum, tnum, n_out);
+    const int rc = col_shift_check(ctx, data, dtype, snum, tnum, shift, n_out, out);
+    if (rc) return rc;
     if (n_out == 0) return IMPDAR_OK;
-    const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype), obytes = (size_t)n_out * tnum * sizeof(double);
-    int rc = g_va.stage_in(ctx, g_va.data, data, bytes);
-    if (rc) return rc;
-    IMPDAR_HIP_CHECK(g_va.out.ensure(obytes));
-    rc = impdar_col_shift_dev(ctx, g_va.data.p, dtype, snum, tnum, shift, n_out, g_va.out.as<double>());
-    if (rc) return rc;
-    return impdar_download(ctx, out, g_va.out.p, obytes, ctx->stream);
+    return g_va.host_form(ctx, g_va.data, data, (size_t)snum * tnum * impdar_dtype_size(dtype), &g_va.out, out,
+                          (size_t)n_out * tnum * sizeof(double), [&](void *d_in, void *d_out) {
+                              return impdar_col_shift_dev(ctx, d_in, dtype, snum, tnum, shift, n_out, (double *)d_out);
+                          });
 }

@@ -12,11 +12,7 @@ from ... import denoise as _dn
 from ... import hfilt as _hf
 from ... import hpass as _hp
 from ... import preproc
-
-
-def _shape(self):
-    dev = getattr(self, '_dev', None)
-    return dev.shape if dev is not None else np.shape(self.data)
+from ._resident import data_shape as _data_shape, replace_data as _replace_data, update_data as _update_data
 
 
 def adaptivehfilt(self, window_size, *args, **kwargs):
@@ -24,14 +20,10 @@ def adaptivehfilt(self, window_size, *args, **kwargs):
     (``filtfilt([.25] * 4, 1, .)``) and tapered with travel time; the reference's windows, including their
     edge branches and empty windows (NaN traces).  The filtering runs on the MI355X whatever the window."""
     print('Adaptive filtering')
-    snum, tnum = _shape(self)
+    snum, tnum = _data_shape(self)
     lo, hi = _hf.ahfilt_windows(tnum, window_size)
     scale = _hf.taper(self.travel_time)
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        _hf.ahfilt_dev(dev, lo, hi, scale)
-    else:
-        self.data = _hf.ahfilt_host(self.data, lo, hi, scale)
+    _update_data(self, lambda dev: _hf.ahfilt_dev(dev, lo, hi, scale), lambda data: _hf.ahfilt_host(data, lo, hi, scale))
     print('Adaptive filtering complete')
     self.flags.hfilt[0] = 1
     self.flags.hfilt[1] = 4
@@ -44,15 +36,11 @@ def winavg_hfilt(self, avg_win, taper='full', filtdepth=100):
     ``adaptivehfilt``, ``'pexp'`` down to zero at sample ``filtdepth``.  ``'tukey'`` fails in the reference on an
     undefined name and raises ``NotImplementedError`` here.  The filtering runs on the MI355X whatever the
     window."""
-    snum, tnum = _shape(self)
+    snum, tnum = _data_shape(self)
     avg_win = _hf.winavg_window(avg_win, self.tnum)
     scale = _hf.winavg_taper(self.travel_time, taper, filtdepth)
     lo, hi = _hf.winavg_windows(tnum, avg_win)
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        _hf.winavg_dev(dev, lo, hi, scale)
-    else:
-        self.data = _hf.winavg_host(self.data, lo, hi, scale)
+    _update_data(self, lambda dev: _hf.winavg_dev(dev, lo, hi, scale), lambda data: _hf.winavg_host(data, lo, hi, scale))
     self.flags.hfilt = np.zeros((2,))
     self.flags.hfilt[1] = 2
     print('Horizontal filter complete.')
@@ -61,15 +49,11 @@ def winavg_hfilt(self, avg_win, taper='full', filtdepth=100):
 def horizontalfilt(self, ntr1, ntr2, *args, **kwargs):
     """Subtract the tapered mean of traces ``ntr1`` to ``ntr2`` (clamped as the reference clamps them) from
     every trace, in the data's own dtype."""
-    snum, tnum = _shape(self)
+    snum, tnum = _data_shape(self)
     htr1, htrn = _hf.hfilt_bounds(ntr1, ntr2, tnum)
     print('Subtracting mean trace found between {:d} and {:d}'.format(htr1, htrn))
     scale = _hf.taper(self.travel_time)
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        _hf.hfilt_dev(dev, htr1, htrn, scale)
-    else:
-        self.data = _hf.hfilt_host(self.data, htr1, htrn, scale)
+    _update_data(self, lambda dev: _hf.hfilt_dev(dev, htr1, htrn, scale), lambda data: _hf.hfilt_host(data, htr1, htrn, scale))
     print('Horizontal filter complete.')
     self.flags.hfilt = np.ones((2,))
 
@@ -103,33 +87,17 @@ def denoise(self, vert_win=1, hor_win=10, noise=None, ftype='wiener'):
     """
     if ftype not in ('wiener', 'median'):
         raise ValueError(_dn.FTYPE_MESSAGE)
-    dev = getattr(self, '_dev', None)
     if ftype == 'wiener':
-        if dev is not None:
-            new_dev, _ = _dn.wiener_dev(dev, vert_win, hor_win, noise=noise)
-        else:
-            self.data, _ = _dn.wiener_host(self.data, vert_win, hor_win, noise=noise)
+        # both forms return (result, noise used)
+        _replace_data(self, lambda dev: _dn.wiener_dev(dev, vert_win, hor_win, noise=noise)[0],
+                      lambda data: _dn.wiener_host(data, vert_win, hor_win, noise=noise)[0])
     else:
-        if dev is not None:
-            new_dev = _dn.median_dev(dev, vert_win, hor_win)
-        else:
-            self.data = _dn.median_host(self.data, vert_win, hor_win)
-    if dev is not None:
-        dev.free()
-        self._dev = new_dev
-        self.data = None
+        _replace_data(self, lambda dev: _dn.median_dev(dev, vert_win, hor_win), lambda data: _dn.median_host(data, vert_win, hor_win))
 
 
 def _hpass_apply(self, spec):
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        new_dev = _hp.filtfilt_dev(dev, spec)
-        if new_dev is not dev:
-            dev.free()
-            self._dev = new_dev
-            self.data = None
-    else:
-        self.data = _hp.filtfilt_host(self.data, spec)
+    # a resident float64 radargram is filtered in place and handed back: nothing is freed then
+    _replace_data(self, lambda dev: _hp.filtfilt_dev(dev, spec), lambda data: _hp.filtfilt_host(data, spec))
     self.flags.hfilt = np.ones((2,))
     self.flags.hfilt[1] = 3
 
@@ -169,11 +137,7 @@ def vertical_band_pass(self, low, high, order=5, filttype='butter', cheb_rp=5, f
     the reference (SciPy), the filtering itself on the MI355X."""
     spec = preproc.design_filter(self.dt, low, high, order=order, filttype=filttype, cheb_rp=cheb_rp)
     print('Bandpassing from {:4.1f} to {:4.1f} MHz...'.format(low, high))
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        preproc.filter_dev(dev, spec)
-    else:
-        self.data = preproc.filter_host(self.data, spec)
+    _update_data(self, lambda dev: preproc.filter_dev(dev, spec), lambda data: preproc.filter_host(data, spec))
     print('Bandpass filter complete.')
     self.flags.bpass[0] = 1
     self.flags.bpass[1] = low

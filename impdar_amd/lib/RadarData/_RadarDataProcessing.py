@@ -14,6 +14,8 @@ from ... import preproc
 from ... import taxis
 from ... import vaxis
 from ..ImpdarError import ImpdarError
+from ._resident import data_dtype as _data_dtype, data_shape as _data_shape
+from ._resident import replace_data as _replace_data, update_data as _update_data
 
 
 def picks_struct_holds_picks(struct):
@@ -45,16 +47,8 @@ def constant_space(self, spacing, min_movement=1.0e-2, show_nomove=False):
     plan = preproc.SpacingPlan(self.dist, spacing, min_movement)
     good_vals, temp_dist, new_dists = plan.good_vals, plan.temp_dist, plan.new_dists
 
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        new_dev = plan.apply_dev(dev)
-        dev.free()
-        self._dev = new_dev
-        self.data = None
-        snum = new_dev.shape[0]
-    else:
-        self.data = plan.apply_host(self.data)
-        snum = self.data.shape[0]
+    _replace_data(self, plan.apply_dev, plan.apply_host)
+    snum = _data_shape(self)[0]
 
     for attr in ['lat', 'long', 'x_coord', 'y_coord', 'decday', 'pressure', 'trig']:
         setattr(self, attr, preproc.interp1d_linear(temp_dist, getattr(self, attr)[good_vals], new_dists))
@@ -80,29 +74,6 @@ def _refuse_picks(self, what):
     """Steps that would have to move picks refuse real ones, as ``constant_space`` does."""
     if getattr(self, 'picks', None) is not None or picks_struct_holds_picks(getattr(self, '_picks_struct', None)):
         raise NotImplementedError('{:s} picks is not part of the MI355X migration engine'.format(what))
-
-
-def _data_shape(self):
-    dev = getattr(self, '_dev', None)
-    return dev.shape if dev is not None else np.shape(self.data)
-
-
-def _data_dtype(self):
-    dev = getattr(self, '_dev', None)
-    return dev.dtype if dev is not None else np.asarray(self.data).dtype
-
-
-def _replace_data(self, on_dev, on_host):
-    """Install the result of a step that changes shape or dtype: a new resident array (the old one is freed) or a
-    new host array."""
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        new_dev = on_dev(dev)
-        dev.free()
-        self._dev = new_dev
-        self.data = None
-    else:
-        self.data = on_host(self.data)
 
 
 def crop(self, lim, top_or_bottom='top', dimension='snum', uice=1.69e8, rezero=True, zero_trig=True):
@@ -231,11 +202,7 @@ def reverse(self):
     kernel on the resident array) and ``x_coord``, ``y_coord``, ``decday``, ``lat``, ``long`` and ``elev``; as in
     the reference ``dist``, ``trig``, ``pressure`` and ``trace_num`` stay.  A second call undoes the first."""
     _refuse_picks(self, 'reversing')
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        taxis.reverse_dev(dev)
-    else:
-        self.data = np.fliplr(self.data)
+    _update_data(self, taxis.reverse_dev, np.fliplr)
     for attr in taxis.REVERSED_ATTRS:
         if getattr(self, attr) is not None:
             setattr(self, attr, np.flip(getattr(self, attr), 0))
@@ -294,11 +261,7 @@ def rangegain(self, slope):
     _gain.refuse_integers(_data_dtype(self))
     snum, tnum = _data_shape(self)
     gain, start = _gain.rangegain_tables(self.travel_time, self.trig, slope, snum, tnum)
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        _gain.rangegain_dev(dev, gain, start)
-    else:
-        self.data = _gain.rangegain_host(self.data, gain, start)
+    _update_data(self, lambda dev: _gain.rangegain_dev(dev, gain, start), lambda data: _gain.rangegain_host(data, gain, start))
     self.flags.rgain = True
 
 
@@ -308,9 +271,6 @@ def agc(self, window=50, scaling_factor=50):
     that is zero), the scale cast to the data's dtype first.  Both passes run on the MI355X; a NaN makes the rows
     whose window holds it NaN, as in the reference.  ``window`` below 2 raises ``ValueError``."""
     half = _gain.agc_half(window)
-    dev = getattr(self, '_dev', None)
-    if dev is not None:
-        _gain.agc_dev(dev, half, scaling_factor)
-    else:
-        self.data = _gain.agc_host(self.data, half, scaling_factor)
+    _update_data(self, lambda dev: _gain.agc_dev(dev, half, scaling_factor),
+                 lambda data: _gain.agc_host(data, half, scaling_factor))
     self.flags.agc = True
