@@ -19,6 +19,7 @@
 // (forward) or before (inverse) the complex transform of length N / 2, in LDS.
 #pragma once
 #include "common.h"
+#include "own_fft_len.h"
 #include <cmath>
 #include <vector>
 
@@ -27,8 +28,6 @@ template <typename T> struct OCp { T x, y; };
 enum { OWN_C2C_FWD = 0, OWN_C2C_INV = 1, OWN_R2C = 2, OWN_C2R = 3, OWN_C2C_INV_RE = 4 };     // 4: the inverse's REAL parts only
 
 __host__ __device__ constexpr int own_pad(int i) { return i + (i >> 5); }
-// complex length M the kernel supports: a power of two, 16 ... 8192 (float64 rows of 8192 take 132 KB of LDS)
-static inline bool own_fft_len_ok(long long m) { return m >= 16 && m <= 8192 && (m & (m - 1)) == 0; }
 
 template <typename T> __device__ __forceinline__ OCp<T> own_mul(OCp<T> a, OCp<T> b)
 {

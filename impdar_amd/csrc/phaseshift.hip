@@ -1372,29 +1372,34 @@ __global__ __launch_bounds__(256) void ps_dc_kernel(const Cp<T> *__restrict__ F,
 #include "ps_mfma.h"
 
 struct PsPlan {
+    // A device buffer of the plan is a Buf{this}: it enrols itself in dev_, which release_device() walks.
+    std::vector<DevBuf *> dev_;
+    struct Buf : DevBuf {
+        explicit Buf(PsPlan *pl) { pl->dev_.push_back(this); }
+    };
     OwnTwiddles tw_time, tw_trace;       // the library's own row transforms (own_fft.h): what the first call of a size runs on
-    DevBuf d_taper;                      // [tnum + snum] float64 taper weights (the transform over the traces taken first: P.fhalf)
+    Buf d_taper{this};                     // [tnum + snum] float64 taper weights (the transform over the traces taken first: P.fhalf)
     int own_calls = 0;                   // ... calls of this size that did
     int dtype = -1, snum = 0, tnum = 0, nt = 0;
     const impdar_ctx *owner = nullptr;   // plans and buffers live on this context's device and stream
     FftPlan f_time, f_trace, b_trace;
-    // launch order of the runs kernels (order_rows in ps_run) and what it was made from: kept for the next call
+    // launch order of the runs kernels (ps_order_rows) and what it was made from: kept for the next call
     std::vector<double> rm_kx, rm_ws, rm_v;
     int rm_state = -1;                   // -1 none, 0 natural order, 1 d_rowmap holds the order
     bool rows_form = true;               // b_trace / r_trace / b_slab run on contiguous rows of transposed arrays (else rocFFT's strided plans)
     FftPlan r_time, r_trace;             // Hermitian walk: real-to-complex along time (nt/2 + 1 rows), then over the traces
     bool r_ready = false, c_ready = false;
-    DevBuf Xr;                           // ... its real input [tnum][nt]
+    Buf Xr{this};                        // ... its real input [tnum][nt]
     FftPlan b_slab;                      // kx-sharded run: inverse transform over k of this rank's depth rows
     int slab_key[3] = {-1, -1, -1};
     const impdar_ctx *slab_owner = nullptr;
-    DevBuf d_sendbuf, d_slab;            // ... packed blocks of the all-to-all; the transposed slab
-    DevBuf d_blocks, d_edge, d_runtab;   // matrix-core path: row-block table; boundary-frequency counts + lists; per-run phases
-    DevBuf d_pr_runs, d_pr_stages, d_rw; // many-runs matrix-core path (ps_runs.h): runs, stages, 1 / w
-    DevBuf d_mcount;                     // matrix-core paths: MFMA instructions the kernel issued (one 64-bit counter)
-    DevBuf d_pn_pieces, d_pn_corr, d_pn_e1;    // transform path (ps_nufft.h): pieces, the window's correction tables, the first-order sums
+    Buf d_sendbuf{this}, d_slab{this};   // ... packed blocks of the all-to-all; the transposed slab
+    Buf d_blocks{this}, d_edge{this}, d_runtab{this};   // matrix-core path: row-block table; boundary-frequency counts + lists; per-run phases
+    Buf d_pr_runs{this}, d_pr_stages{this}, d_rw{this}; // many-runs matrix-core path (ps_runs.h): runs, stages, 1 / w
+    Buf d_mcount{this};                  // matrix-core paths: MFMA instructions the kernel issued (one 64-bit counter)
+    Buf d_pn_pieces{this}, d_pn_corr{this}, d_pn_e1{this};    // transform path (ps_nufft.h): pieces, the window's correction tables, the first-order sums
     SrHostPlan sr_plan;                  // series path (ps_series.h): the pieces of the last velocity profile, and on the device
-    DevBuf d_sr_pieces, d_sr_ev;
+    Buf d_sr_pieces{this}, d_sr_ev{this};
     bool sr_dev = false;                 // ... the device copies are those of sr_plan
     OwnTwiddles pn_tw[14];               // ... twiddles of the grid lengths 2^l
     std::vector<float> h_pn_corr;        // ... the tables on the host (made once per padded length)
@@ -1405,9 +1410,20 @@ struct PsPlan {
     // a (kx, runs) geometry whose boundary-frequency lists overflowed in a matrix-core path: not tried again
     std::vector<double> ovf_kx;
     std::vector<PsMfmaRun> ovf_runs;
-    DevBuf X, TK, d_kx, d_w, d_vz, d_thr, d_sched, d_rowmap, d_eps, d_sm, d_part;
+    Buf X{this}, TK{this}, d_kx{this}, d_w{this}, d_vz{this}, d_thr{this}, d_sched{this}, d_rowmap{this}, d_eps{this}, d_sm{this}, d_part{this};
     std::vector<double> h_sm_step, h_sm_tile;
     bool b_ready = false;
+    // another device / stream: drop everything bound to the old one (tw_time / tw_trace rebuild themselves)
+    void release_device()
+    {
+        for (DevBuf *b : dev_) b->release();
+        for (OwnTwiddles &t : pn_tw) {
+            t.buf.release();
+            t.nt = 0;
+        }
+        pn_corr_dev = -1;
+        sr_dev = false;
+    }
 };
 static std::mutex g_ps_mu;
 static PsPlan *g_ps_plan = nullptr;
@@ -1725,7 +1741,7 @@ static std::vector<T> &pn_corr_tables(PsPlan &pl, const bool (&need)[13], int (&
 // ---- transform path (ps_nufft.h): pieces, correction tables, launch.  Same contract as ps_mfma_run.
 template <typename T>
 static int ps_nufft_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &runs, bool vz, const double *kx_host, const double *w_host,
-                        const double *thr, hipStream_t st, bool *done, const double *vmig = nullptr, bool allow_pairs = false)
+                        const double *thr, hipStream_t st, bool *done, bool kx_antisym, const double *vmig = nullptr, bool allow_pairs = false)
 {
     // vmig (float64 data, v(z)): the per-step velocities -- the runs' rounding noise enters as a first-order term (ps_nufft.h)
     // allow_pairs: the sums go on into the inverse transform (not to a caller who asked for the rows TK themselves): rows k and
@@ -1745,8 +1761,7 @@ static int ps_nufft_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &ru
         if (std::fabs(w_host[i] - (double)i * dw) > 1e-9 * (double)i * dw) return IMPDAR_OK;
     if (std::fabs(std::fabs(w_host[0]) - (double)nf * dw) > 1e-9 * (double)nf * dw) return IMPDAR_OK;
     // the whole wavenumber axis with kx[tnum - k] = -kx[k]: a pair of rows per workgroup, as ps_runs_kernel's
-    bool pairs = allow_pairs && P.k0 == 0 && P.nk == tnum && tnum >= 2 && tnum % 2 == 0;
-    for (int k = 1; 2 * k < tnum && pairs; ++k) pairs = kx_host[k] == -kx_host[tnum - k];
+    const bool pairs = allow_pairs && P.k0 == 0 && P.nk == tnum && tnum >= 2 && tnum % 2 == 0 && kx_antisym;     // (ps_route.h)
     if (P.fhalf && !pairs) return IMPDAR_OK;           // (the half layout is read by the pairs only; ps_run repeats the transforms)
     const int lmax_steps = pn_lmax<T>(pairs);
     std::vector<PnPiece> pc;
@@ -1998,7 +2013,7 @@ static int ps_series_run(PsPlan &pl, PsParams P, const double *vmig, const doubl
 // IMPDAR_OK with *done = true when the frequency sums were produced here; *done = false: not eligible, the vector
 // kernels take the call.
 static int ps_mfma_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &runs, bool vz, const double *kx_host, const double *thr,
-                       hipStream_t st, bool *done, const char **kernel_name)
+                       bool force_overflow, hipStream_t st, bool *done, const char **kernel_name)
 {
     *done = false;
     *kernel_name = "ps_mfma_kernel";
@@ -2099,7 +2114,6 @@ static int ps_mfma_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &run
         IMPDAR_HIP_CHECK(hipMemcpy(cnt.data(), Q.edge_cnt + P.k0, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
         int worst = 0;
         for (int c : cnt) worst = std::max(worst, c);
-        const bool force_overflow = getenv("IMPDAR_PS_TEST_EDGE_OVERFLOW") != nullptr;      // test hook (read per call)
         if (worst > PM_EMAX) ps_note_overflow(pl, kx_host, tnum, runs);    // (remembered: not tried again on this geometry)
         if (worst > PM_EMAX || force_overflow) return IMPDAR_OK;           // *done stays false
     }
@@ -2109,6 +2123,307 @@ static int ps_mfma_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &run
         pl.mfma_instructions = (double)n;
     }
     *done = true;
+    return IMPDAR_OK;
+}
+
+// ---- ps_run, stage by stage.  What is decided on the host -- the walk, the runs, the layout, the order of attempts -- is
+// ps_route.h's; the stages below allocate, upload and launch.
+
+// the cached plan belongs to one context, size, dtype and transform form: anything else starts it over
+static int ps_plan_bind(impdar_ctx *ctx, PsPlan &pl, bool dbl, int snum, int tnum, int nt, bool rows_form)
+{
+    const size_t csize = dbl ? 16 : 8;
+    if (pl.owner == ctx && pl.dtype == (dbl ? IMPDAR_F64 : IMPDAR_F32) && pl.snum == snum && pl.tnum == tnum && pl.nt == nt &&
+        pl.rows_form == rows_form)
+        return IMPDAR_OK;
+    pl.own_calls = 0;
+    pl.dtype = -1;
+    pl.rm_state = -1;
+    if (pl.owner != ctx) {               // another device / stream: drop everything bound to the old one
+        pl.release_device();
+        pl.owner = ctx;
+    }
+    pl.r_ready = pl.c_ready = false;     // the forward transforms are made on first use (ps_make_plans): which pair depends on the walk
+    pl.rows_form = rows_form;
+    pl.b_ready = false;                  // the inverse transform over the traces: made beside the forward pair
+    IMPDAR_HIP_CHECK(pl.X.ensure((size_t)tnum * nt * csize));
+    IMPDAR_HIP_CHECK(pl.d_kx.ensure((size_t)tnum * 8));
+    IMPDAR_HIP_CHECK(pl.d_w.ensure((size_t)nt * 8));
+    IMPDAR_HIP_CHECK(pl.d_vz.ensure((size_t)snum * 8));
+    IMPDAR_HIP_CHECK(pl.d_thr.ensure((size_t)snum * 8));
+    pl.dtype = dbl ? IMPDAR_F64 : IMPDAR_F32;
+    pl.snum = snum;
+    pl.tnum = tnum;
+    pl.nt = nt;
+    return IMPDAR_OK;
+}
+
+// what the transforms run on: the twiddles of the library's own row kernels, or the rocFFT plans this call still lacks
+template <typename T>
+static int ps_make_plans(impdar_ctx *ctx, PsPlan &pl, const PsRoute &R, int snum, int tnum, int nt)
+{
+    hipStream_t st = ctx->stream;
+    const bool dbl = sizeof(T) == 8, herm = R.herm;
+    const int fstride = R.fstride;
+    int rc;
+    if (R.use_own) {
+        IMPDAR_HIP_CHECK(pl.Xr.ensure((size_t)tnum * nt * sizeof(T)));
+        pl.own_calls += 1;
+        impdar_trace("phaseshift: transforms on the library's own row kernels");
+        if ((rc = pl.tw_time.ensure<T>(nt, st)) || (rc = pl.tw_trace.ensure<T>(tnum, st))) return rc;
+        return IMPDAR_OK;
+    }
+    // n-point complex transforms in place, `batch` of them: on contiguous rows, or strided through the array as it lies
+    auto c2c = [&](FftPlan &p, rocfft_transform_type type, int n, int batch, bool rows, double scale) {
+        const rocfft_array_type ci = rocfft_array_type_complex_interleaved;
+        return rows ? p.create(type, dbl, true, n, batch, ci, ci, 1, n, 1, n, scale, st) : p.create(type, dbl, true, n, batch, ci, ci, batch, 1, batch, 1, scale, st);
+    };
+    // created side by side (run-time compilation: impdar_parallel_plans)
+    std::vector<std::function<int()>> makers;
+    if (!pl.b_ready) makers.push_back([&] { return c2c(pl.b_trace, rocfft_transform_type_complex_inverse, tnum, snum, pl.rows_form, 1.0 / tnum); });
+    if (herm && !pl.r_ready) {
+        IMPDAR_HIP_CHECK(pl.Xr.ensure((size_t)tnum * nt * sizeof(T)));
+        makers.push_back([&] {
+            return pl.r_time.create(rocfft_transform_type_real_forward, dbl, false, nt, tnum, rocfft_array_type_real,
+                                    rocfft_array_type_hermitian_interleaved, 1, nt, 1, fstride, 1.0, st);
+        });
+        makers.push_back([&] { return c2c(pl.r_trace, rocfft_transform_type_complex_forward, tnum, fstride, pl.rows_form, 1.0); });
+    }
+    if (!herm && !pl.c_ready) {
+        makers.push_back([&] { return c2c(pl.f_time, rocfft_transform_type_complex_forward, nt, tnum, true, 1.0); });
+        makers.push_back([&] { return c2c(pl.f_trace, rocfft_transform_type_complex_forward, tnum, nt, false, 1.0); });
+    }
+    if (!makers.empty()) {
+        impdar_trace("phaseshift: %zu rocFFT plans to make", makers.size());
+        if ((rc = impdar_parallel_plans(ctx->device, makers))) return rc;
+        impdar_trace("phaseshift: plans ready");
+        pl.b_ready = true;
+        if (herm) pl.r_ready = true;
+        else pl.c_ready = true;
+    }
+    return IMPDAR_OK;
+}
+
+// the axes, the profile and the runs schedule of the call on the device (R owns the host copies: alive until ps_run's last sync)
+static int ps_upload(PsPlan &pl, PsParams &P, const PsRoute &R, bool dbl, const double *kx, const double *vmig, hipStream_t st)
+{
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_kx.p, kx, (size_t)P.tnum * 8, hipMemcpyHostToDevice, st));
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_w.p, R.w.data(), (size_t)R.nf * 8, hipMemcpyHostToDevice, st));
+    if (P.vz_mode) {
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_vz.p, vmig, (size_t)P.snum * 8, hipMemcpyHostToDevice, st));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_thr.p, R.thr.data(), (size_t)P.snum * 8, hipMemcpyHostToDevice, st));
+    }
+    if (R.use_sched) {
+        IMPDAR_HIP_CHECK(pl.d_sched.ensure(R.sched.size() * sizeof(int)));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sched.p, R.sched.data(), R.sched.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        P.sched = pl.d_sched.as<int>();
+        P.tsched = P.sched + P.snum;
+        if (dbl) {
+            IMPDAR_HIP_CHECK(pl.d_eps.ensure(R.epsum.size() * sizeof(double)));
+            IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_eps.p, R.epsum.data(), R.epsum.size() * sizeof(double), hipMemcpyHostToDevice, st));
+            P.eps = pl.d_eps.as<double>();
+        }
+    }
+    return IMPDAR_OK;
+}
+
+// the taper weights of the half layout (tap: the caller's, alive until its last sync); no room for them: the full layout
+static int ps_taper_upload(PsPlan &pl, std::vector<double> &tap, int snum, int tnum, double htaper, double vtaper, hipStream_t st, bool *half_front)
+{
+    tap.resize((size_t)tnum + snum);
+    for (int j = 0; j < tnum; ++j) tap[j] = impdar_taper_w(j, tnum, htaper);
+    for (int i = 0; i < snum; ++i) tap[(size_t)tnum + i] = impdar_taper_w(i, snum, vtaper);
+    if (pl.d_taper.ensure(((size_t)tnum + snum) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        *half_front = false;
+        return IMPDAR_OK;
+    }
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_taper.p, tap.data(), (size_t)tnum * 8, hipMemcpyHostToDevice, st));
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_taper.as<double>() + tnum, tap.data() + tnum, (size_t)snum * 8, hipMemcpyHostToDevice, st));
+    return IMPDAR_OK;
+}
+
+// the transforms of the [k][w > 0] layout every kernel reads (Hermitian walk on the library's own or rocFFT's plans)
+template <typename T>
+static int ps_front_full(PsPlan &pl, const PsParams &P, const PsRoute &R, const void *d_data, double htaper, double vtaper, hipStream_t st)
+{
+    const int snum = P.snum, tnum = P.tnum, nt = P.nt, fstride = R.fstride;
+    int rc;
+    hipLaunchKernelGGL((ps_taper_pad_transpose_real<T>), dim3((tnum + 63) / 64, (nt + 63) / 64), dim3(256), 0, st, (const T *)d_data,
+                       pl.Xr.as<T>(), snum, tnum, nt, htaper, vtaper);
+    if (R.use_own) {
+        if ((rc = own_fft_launch<T>(OWN_R2C, nt, (size_t)tnum, pl.Xr.p, pl.X.p, (size_t)nt, (size_t)fstride, 1.0, pl.tw_time, st))) return rc;
+    } else if ((rc = pl.r_time.exec(pl.Xr.p, pl.X.p))) {
+        return rc;
+    }
+    if (pl.rows_form) {
+        // over the traces on contiguous rows: X [x][fstride] -> [fstride][x] (pl.TK is free until the frequency sums
+        // write it, and large enough: snum > nt / 2), transform, and back -> X [k][fstride]
+        ps_launch_transpose<T>(pl.X.p, pl.TK.p, tnum, fstride, st);
+        if (R.use_own) {
+            if ((rc = own_fft_launch<T>(OWN_C2C_FWD, tnum, (size_t)fstride, pl.TK.p, pl.TK.p, (size_t)tnum, (size_t)tnum, 1.0, pl.tw_trace, st))) return rc;
+        } else if ((rc = pl.r_trace.exec(pl.TK.p, nullptr))) {
+            return rc;
+        }
+        ps_launch_transpose<T>(pl.TK.p, pl.X.p, fstride, tnum, st);
+        IMPDAR_HIP_CHECK(hipGetLastError());
+    } else if ((rc = pl.r_trace.exec(pl.X.p, nullptr))) {
+        return rc;
+    }
+    return IMPDAR_OK;
+}
+
+// the forward transforms in one of three layouts: k >= 0 with all frequencies (half_front: the trace transform first), the
+// Hermitian walk's [k][w > 0], or the reference's complex walk
+template <typename T>
+static int ps_front(PsPlan &pl, PsParams &P, const PsRoute &R, bool half_front, const void *d_data, double htaper, double vtaper, hipStream_t st)
+{
+    const int snum = P.snum, tnum = P.tnum, nt = P.nt;
+    int rc;
+    if (R.herm && half_front) {
+        const int hs = tnum / 2 + 1;
+        const double *th = pl.d_taper.as<double>(), *tv = th + tnum;
+        // (pl.TK: free until the frequency sums write it, and at least tnum x snum complex)
+        if ((rc = own_fft_launch<T>(OWN_R2C, tnum, (size_t)snum, d_data, pl.TK.p, (size_t)tnum, (size_t)hs, 1.0, pl.tw_trace, st, th, tv))) return rc;
+        constexpr int TS = sizeof(T) == 4 ? 64 : 32;
+        hipLaunchKernelGGL((ps_transpose_pad<T, TS>), dim3((hs + TS - 1) / TS, (nt + TS - 1) / TS), dim3(256), 0, st, pl.TK.as<Cp<T>>(),
+                           pl.X.as<Cp<T>>(), snum, hs, nt);
+        if ((rc = own_fft_launch<T>(OWN_C2C_FWD, nt, (size_t)hs, pl.X.p, pl.X.p, (size_t)nt, (size_t)nt, 1.0, pl.tw_time, st))) return rc;
+        IMPDAR_HIP_CHECK(hipGetLastError());
+        P.fhalf = 1;
+        P.fstride = nt;
+        impdar_trace("phaseshift: the transform over the traces first: wavenumbers k >= 0 with all frequencies, for pairs in ps_nufft_kernel");
+        return IMPDAR_OK;
+    }
+    if (R.herm) return ps_front_full<T>(pl, P, R, d_data, htaper, vtaper, st);
+    hipLaunchKernelGGL((ps_taper_pad_transpose<T>), dim3((tnum + 63) / 64, (nt + 63) / 64), dim3(256), 0, st, (const T *)d_data,
+                       pl.X.as<Cp<T>>(), snum, tnum, nt, htaper, vtaper);
+    if ((rc = pl.f_time.exec(pl.X.p, nullptr))) return rc;
+    return pl.f_trace.exec(pl.X.p, nullptr);
+}
+
+// the launch order of the runs kernels of the vector path (ps_row_order, ps_route.h).  It depends on the axes and the profile
+// only: a repeated geometry re-uses the last one.  rowmap: the caller's, alive until its last sync.
+static int ps_order_rows(PsPlan &pl, PsParams &P, const PsRoute &R, std::vector<int> &rowmap, const double *kx, const double *ws,
+                         const double *vmig, bool dbl, hipStream_t st)
+{
+    const int snum = P.snum, tnum = P.tnum, nt = P.nt;
+    if (P.nk != tnum) return IMPDAR_OK;                          // (a slab of a sharded run keeps the natural order)
+    if (pl.rm_state >= 0 && pl.rm_kx.size() == (size_t)tnum && pl.rm_ws.size() == (size_t)nt && pl.rm_v.size() == (size_t)snum &&
+        memcmp(pl.rm_kx.data(), kx, (size_t)tnum * 8) == 0 && memcmp(pl.rm_ws.data(), ws, (size_t)nt * 8) == 0 &&
+        memcmp(pl.rm_v.data(), vmig, (size_t)snum * 8) == 0) {
+        if (pl.rm_state == 1) P.rowmap = pl.d_rowmap.as<int>();
+        return IMPDAR_OK;
+    }
+    pl.rm_state = -1;
+    pl.rm_kx.assign(kx, kx + tnum);
+    pl.rm_ws.assign(ws, ws + nt);
+    pl.rm_v.assign(vmig, vmig + snum);
+    rowmap = ps_row_order(kx, tnum, ws, nt, R.runs, P.dt, dbl);
+    pl.rm_state = 0;
+    if (!rowmap.empty()) {
+        IMPDAR_HIP_CHECK(pl.d_rowmap.ensure((size_t)tnum * sizeof(int)));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_rowmap.p, rowmap.data(), (size_t)tnum * sizeof(int), hipMemcpyHostToDevice, st));
+        P.rowmap = pl.d_rowmap.as<int>();
+        pl.rm_state = 1;
+    }
+    return IMPDAR_OK;
+}
+
+// no runs of constant velocity to live on (the velocity changes in most 16-step tiles): ps_smooth_kernel.  Declines (*done
+// false) on a profile that is not finite, a vertical taper inside the record, or no room for the partial images.
+template <typename T>
+static int ps_smooth_run(PsPlan &pl, PsParams &P, const PsRoute &R, const double *vmig, hipStream_t st, bool *done)
+{
+    const int snum = P.snum, tnum = P.tnum;
+    *done = false;
+    for (int i = 0; i < snum; ++i)
+        if (!(std::isfinite(vmig[i]) && vmig[i] != 0.0 && R.thr[i] < 1e-10)) return IMPDAR_OK;
+    // float32, the whole wavenumber axis with kx[tnum - k] = -kx[k]: rows k and tnum - k in one wave (ps_smooth.h)
+    const bool sm_pairs = P.k0 == 0 && P.nk == tnum && tnum >= 2 && R.kx_antisym;
+    P.sm_m = ps_smooth_m(sizeof(T) == 8, sm_pairs);
+    P.sm_nchunks = ps_smooth_chunks(R.nf, P.sm_m);
+    const size_t part_bytes = P.sm_nchunks > 1 ? (size_t)P.sm_nchunks * P.nk * snum * sizeof(Cp<T>) : 0;
+    std::vector<double> &sm_step = pl.h_sm_step, &sm_tile = pl.h_sm_tile;     // (alive until the next call: async copies)
+    if (sizeof(T) == 4) ps_smooth_tables(vmig, R.thr.data(), snum, sm_step, sm_tile);
+    if (pl.d_sm.ensure((sm_step.size() + sm_tile.size()) * 8 + 64) != hipSuccess || (part_bytes && pl.d_part.ensure(part_bytes) != hipSuccess)) {
+        (void)hipGetLastError();
+        P.sm_nchunks = 1;
+        return IMPDAR_OK;
+    }
+    if (sizeof(T) == 4) {
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sm.p, sm_step.data(), sm_step.size() * 8, hipMemcpyHostToDevice, st));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sm.as<double>() + sm_step.size(), sm_tile.data(), sm_tile.size() * 8, hipMemcpyHostToDevice, st));
+        P.sm_step = pl.d_sm.as<double>();
+        P.sm_tile = pl.d_sm.as<double>() + sm_step.size();
+    }
+    P.sm_part = pl.d_part.p;
+    ps_smooth_launch<T>(P, st, sm_pairs);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    t_ps_kernel = sizeof(T) == 4 ? "ps_smooth32_kernel" : "ps_smooth_kernel";
+    *done = true;
+    return IMPDAR_OK;
+}
+
+// the metrics line of the call (kernel: the frequency-sum kernel that took it)
+static void ps_metrics(impdar_ctx *ctx, const PsPlan &pl, const PsParams &P, const PsRoute &R, const char *kernel, bool matrix_counted, bool tk_out)
+{
+    ctx->m_entry = tk_out ? "impdar_phaseshift_tk_dev" : "impdar_phaseshift";
+    ctx->m_kernel = kernel;
+    ctx->m_kernel_ms = -1.f;                 // (bracketed by ktic / ktoc)
+    char *x = ctx->m_extra;
+    const size_t cap = sizeof ctx->m_extra;      // (320: the part both forms share is under 110)
+    const int n = snprintf(x, cap, "\"hermitian_walk\": %s, \"frequencies\": %d, \"transforms\": \"%s\", \"long_runs\": %d, ", R.herm ? "true" : "false", R.nf,
+                           R.use_own ? "own" : "rocfft", R.long_runs_metric);
+    if (matrix_counted)      // (MFMA instructions the kernel issued, counted by the kernel: rounds and blocks it skips are not in it)
+        snprintf(x + n, cap - n, "\"mfma_instructions\": %.0f, \"flop_per_mfma\": %d", pl.mfma_instructions, strcmp(kernel, "ps_runs_kernel") == 0 ? 16384 : 32768);
+    else
+        snprintf(x + n, cap - n, "\"spectrum\": \"%s\"", P.fhalf ? "k >= 0, all frequencies" : "all k, frequencies walked");
+}
+
+// the zero-frequency rows, then the inverse transform over k and the real part (:282); a rank of a kx-sharded run stops at its sums
+template <typename T>
+static int ps_back(impdar_ctx *ctx, PsPlan &pl, const PsParams &P, const PsRoute &R, bool tk_out, void *d_out)
+{
+    hipStream_t st = ctx->stream;
+    const int snum = P.snum, tnum = P.tnum;
+    int rc;
+    if (R.herm)
+        for (int kz : R.k_zero)
+            if (kz >= P.k0 && kz < P.k0 + P.nk)
+                hipLaunchKernelGGL((ps_dc_kernel<T>), dim3((snum + 255) / 256), dim3(256), 0, st, pl.X.as<Cp<T>>(),
+                                   reinterpret_cast<Cp<T> *>(P.TK), kz, kz - P.k0, P.fstride, snum, R.w0 * P.dt);
+    if ((rc = impdar_ctx_ktoc(ctx))) return rc;
+    if (tk_out) {
+        IMPDAR_HIP_CHECK(hipGetLastError());
+        return impdar_ctx_toc(ctx);
+    }
+    if (pl.rows_form) {
+        // inverse over k on contiguous rows: TK [k][tau] -> [tau][k] (pl.X: the spectrum is not needed any more, and
+        // nt >= snum), transform, real part (:282) -- already (snum, tnum)
+        if (R.use_own && tnum >= 32) {
+            // (the real part is all that is kept: the Hermitian half of the sums goes through a real inverse transform of half
+            // the length -- ps_transpose_herm; until round 6 a full transpose and a complex transform that stored real parts:
+            // 175 + 314 us at 8192^2 float32)
+            const int hs = tnum / 2 + 1;
+            ps_launch_transpose_herm<T>(pl.TK.p, pl.X.p, tnum, snum, hs, st);
+            if ((rc = own_fft_launch<T>(OWN_C2R, tnum, (size_t)snum, pl.X.p, d_out, (size_t)hs, (size_t)tnum, 1.0 / tnum, pl.tw_trace, st))) return rc;
+        } else if (R.use_own) {
+            ps_launch_transpose<T>(pl.TK.p, pl.X.p, tnum, snum, st);
+            if ((rc = own_fft_launch<T>(OWN_C2C_INV_RE, tnum, (size_t)snum, pl.X.p, d_out, (size_t)tnum, (size_t)tnum, 1.0 / tnum, pl.tw_trace, st))) return rc;
+        } else {
+            ps_launch_transpose<T>(pl.TK.p, pl.X.p, tnum, snum, st);
+            if ((rc = pl.b_trace.exec(pl.X.p, nullptr))) return rc;
+            const size_t n = (size_t)snum * tnum;
+            hipLaunchKernelGGL((ps_real_part<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pl.X.as<Cp<T>>(), (T *)d_out, n);
+        }
+    } else {
+        if ((rc = pl.b_trace.exec(pl.TK.p, nullptr))) return rc;
+        hipLaunchKernelGGL((ps_real_transpose<T>), dim3((tnum + 63) / 64, (snum + 63) / 64), dim3(256), 0, st, pl.TK.as<Cp<T>>(), (T *)d_out, snum, tnum);
+    }
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    if ((rc = impdar_ctx_toc(ctx))) return rc;
+    impdar_trace("phaseshift: all kernels enqueued");
     return IMPDAR_OK;
 }
 
@@ -2122,178 +2437,21 @@ static int ps_run(impdar_ctx *ctx, PsPlan &pl, const void *d_data, int snum, int
     if (nk < 0) nk = tnum;
     hipStream_t st = ctx->stream;
     const bool dbl = sizeof(T) == 8;
-    // IMPDAR_PS_FFT=strided: the transforms over the traces / wavenumbers as rocFFT's strided plans on the arrays as
-    // they lie (rounds 1-3a); default: transpose, contiguous plan, transpose (see ps_transpose_c)
-    // rocfft: rocFFT's plans also where the library's own row transforms apply; own: that default spelled out (tests that pin one)
-    const char *fe = getenv("IMPDAR_PS_FFT");
-    const bool rows_form = !(fe && strcmp(fe, "strided") == 0);
-    const bool no_own = fe && strcmp(fe, "rocfft") == 0;
-    if (pl.owner != ctx || pl.dtype != (dbl ? IMPDAR_F64 : IMPDAR_F32) || pl.snum != snum || pl.tnum != tnum || pl.nt != nt ||
-        pl.rows_form != rows_form) {
-        pl.own_calls = 0;
-        pl.dtype = -1;
-        pl.rm_state = -1;
-        pl.r_ready = pl.c_ready = false;
-        if (pl.owner != ctx) {               // another device / stream: drop everything bound to the old one
-            pl.Xr.release();
-            pl.d_taper.release();
-            pl.d_blocks.release();
-            pl.d_edge.release();
-            pl.d_runtab.release();
-            pl.d_pr_runs.release();
-            pl.d_pn_pieces.release();
-            pl.d_pn_corr.release();
-            pl.d_pn_e1.release();
-            pl.pn_corr_dev = -1;
-            pl.d_sr_pieces.release();
-            pl.d_sr_ev.release();
-            pl.sr_dev = false;
-            for (OwnTwiddles &t : pl.pn_tw) {
-                t.buf.release();
-                t.nt = 0;
-            }
-            pl.d_mcount.release();
-            pl.d_pr_stages.release();
-            pl.d_rw.release();
-            pl.d_sendbuf.release();
-            pl.d_slab.release();
-            pl.X.release(); pl.TK.release(); pl.d_kx.release(); pl.d_w.release(); pl.d_vz.release(); pl.d_thr.release(); pl.d_sm.release(); pl.d_part.release();
-            pl.d_sched.release();
-            pl.d_rowmap.release();
-            pl.d_eps.release();
-            pl.owner = ctx;
-        }
-        pl.c_ready = false;              // the forward transforms are made on first use (below): which pair depends on the walk
-        pl.rows_form = rows_form;
-        pl.b_ready = false;              // the inverse transform over the traces: made below, beside the forward pair
-        IMPDAR_HIP_CHECK(pl.X.ensure((size_t)tnum * nt * 2 * sizeof(T)));
-        IMPDAR_HIP_CHECK(pl.d_kx.ensure((size_t)tnum * 8));
-        IMPDAR_HIP_CHECK(pl.d_w.ensure((size_t)nt * 8));
-        IMPDAR_HIP_CHECK(pl.d_vz.ensure((size_t)snum * 8));
-        IMPDAR_HIP_CHECK(pl.d_thr.ensure((size_t)snum * 8));
-        pl.dtype = dbl ? IMPDAR_F64 : IMPDAR_F32;
-        pl.snum = snum;
-        pl.tnum = tnum;
-        pl.nt = nt;
-    }
-    std::vector<double> w(ws, ws + nt), thr(snum, 0.0);
-    for (int i = 0; i < nt; ++i)
-        if (w[i] == 0.0) w[i] = 1e-10 / dt;                            // :400-402
-    // Hermitian walk (see ps_load_slot): the radargram is real, so frequencies 1..nt/2-1 also stand for their mirror
-    // images.  Taken only when the axes are exactly antisymmetric and the replaced zero frequency is evanescent
-    // wherever kx != 0 (it always is for a physical geometry: |v kx / 2| >= v pi / (tnum dx) against 1e-10/dt);
-    // anything else -- and IMPDAR_PS_HERMITIAN=0 -- keeps the reference's walk over all nt frequencies.
-    const double w0 = 1e-10 / dt;
-    std::vector<int> k_zero;                // wavenumbers with kx = 0 (the zero-frequency row propagates there)
-    bool herm = nt >= 4 && (nt & (nt - 1)) == 0 && ws[0] == 0.0;
-    {
-        const char *he = getenv("IMPDAR_PS_HERMITIAN");      // read per call: the tests compare the two walks in one process
-        if (he && atoi(he) == 0) herm = false;
-    }
-    if (herm) {
-        for (int i = 1; i < nt / 2 && herm; ++i) herm = std::isfinite(ws[i]) && ws[i] != 0.0 && ws[nt - i] == -ws[i];
-        herm = herm && std::isfinite(ws[nt / 2]) && ws[nt / 2] != 0.0;
-        double vmin = std::fabs(vconst);
-        if (vlen) {
-            vmin = std::fabs(vmig[0]);
-            for (int i = 0; i < snum; ++i) {
-                herm = herm && std::isfinite(vmig[i]);
-                vmin = std::min(vmin, std::fabs(vmig[i]));
-            }
-        }
-        herm = herm && std::isfinite(vmin) && std::isfinite(w0);
-        for (int k = 0; k < tnum && herm; ++k) {
-            // (the wavenumber Nyquist row of an even trace count is its own mirror image: only kx^2 enters)
-            const int km = (tnum - k) % tnum;
-            herm = std::isfinite(kx[k]) && (km == k || kx[km] == -kx[k]);
-            if (kx[k] == 0.0) k_zero.push_back(k);
-            else herm = herm && std::fabs(0.5 * vmin * kx[k]) > 2.0 * w0;     // w0 evanescent with a wide margin
-        }
-        herm = herm && k_zero.size() <= 4;
-    }
-    const int nf = herm ? nt / 2 : nt;
-    const int fstride = herm ? nt / 2 + 1 : nt;
-    if (herm) {
-        w[0] = ws[nt / 2];                  // slot order: Nyquist first, then rows 1..nt/2-1 (already in place)
-    }
+    const PsKnobs K = ps_knobs_read();
+    int rc;
+    if ((rc = ps_plan_bind(ctx, pl, dbl, snum, tnum, nt, K.rows_form))) return rc;
+    const PsRoute R = ps_route(dbl, snum, tnum, nt, kx, ws, dt, tt_us, vconst, vmig, vlen, k0, nk, tk_out != nullptr, K);
     {
         // TK: the frequency sums [tnum][snum] of an unsharded call, and the scratch of the transposed forward transform
         // (nt / 2 + 1 rows of tnum -- more than snum rows when the caller pads the time axis beyond the next power of
         // two).  A rank of a kx-sharded run writes its sums to the caller's slab: it only needs the scratch.
-        const size_t scratch_rows = (herm && pl.rows_form) ? (size_t)(nt / 2 + 1) : 0;
+        const size_t scratch_rows = (R.herm && pl.rows_form) ? (size_t)(nt / 2 + 1) : 0;
         const size_t rows = tk_out ? scratch_rows : std::max<size_t>((size_t)snum, scratch_rows);
         if (rows) IMPDAR_HIP_CHECK(pl.TK.ensure((size_t)tnum * rows * 2 * sizeof(T)));
     }
-    // Power-of-two sizes run their transforms on the library's own row kernels (own_fft.h), every call: nothing to compile,
-    // no plan to make (rocFFT: 0.25-3 s per process, its kernels for lengths above 1024 are compiled at run time), and within
-    // 0.1 ms of rocFFT's plans at 8192^2 since the long rows run 1024 threads (round 5; until then the first call of a size
-    // only).  (Plans made on a thread during a first call: a process that exits while rocFFT is still compiling on
-    // another thread crashes in its teardown -- rc -11 / -6 in 2 of 2 such exits, profiles/r05_first_call.txt.)
-    bool use_own = false;
-    if (herm && pl.rows_form && !no_own && own_fft_len_ok(nt / 2) && own_fft_len_ok(tnum)) {
-        IMPDAR_HIP_CHECK(pl.Xr.ensure((size_t)tnum * nt * sizeof(T)));
-        use_own = true;
-        pl.own_calls += 1;
-        impdar_trace("phaseshift: transforms on the library's own row kernels");
-        int rc;
-        if ((rc = pl.tw_time.ensure<T>(nt, st)) || (rc = pl.tw_trace.ensure<T>(tnum, st))) return rc;
-    }
-    if (!use_own) {
-        int rc;
-        const rocfft_array_type ci = rocfft_array_type_complex_interleaved;
-        // the plans this call still lacks, created side by side (run-time compilation: impdar_parallel_plans)
-        std::vector<std::function<int()>> makers;
-        const bool rows_form_b = pl.rows_form;
-        if (!pl.b_ready)
-            makers.push_back([&] {
-                return rows_form_b ? pl.b_trace.create(rocfft_transform_type_complex_inverse, dbl, true, tnum, snum, ci, ci, 1, tnum, 1, tnum,
-                                                       1.0 / tnum, st)
-                                   : pl.b_trace.create(rocfft_transform_type_complex_inverse, dbl, true, tnum, snum, ci, ci, snum, 1, snum, 1,
-                                                       1.0 / tnum, st);
-            });
-        if (herm && !pl.r_ready) {
-            IMPDAR_HIP_CHECK(pl.Xr.ensure((size_t)tnum * nt * sizeof(T)));
-            makers.push_back([&] {
-                return pl.r_time.create(rocfft_transform_type_real_forward, dbl, false, nt, tnum, rocfft_array_type_real,
-                                        rocfft_array_type_hermitian_interleaved, 1, nt, 1, fstride, 1.0, st);
-            });
-            makers.push_back([&] {
-                return pl.rows_form ? pl.r_trace.create(rocfft_transform_type_complex_forward, dbl, true, tnum, fstride, ci, ci, 1, tnum,
-                                                        1, tnum, 1.0, st)
-                                    : pl.r_trace.create(rocfft_transform_type_complex_forward, dbl, true, tnum, fstride, ci, ci, fstride, 1,
-                                                        fstride, 1, 1.0, st);
-            });
-        }
-        if (!herm && !pl.c_ready) {
-            makers.push_back([&] { return pl.f_time.create(rocfft_transform_type_complex_forward, dbl, true, nt, tnum, ci, ci, 1, nt, 1, nt, 1.0, st); });
-            makers.push_back([&] { return pl.f_trace.create(rocfft_transform_type_complex_forward, dbl, true, tnum, nt, ci, ci, nt, 1, nt, 1, 1.0, st); });
-        }
-        if (!makers.empty()) {
-            impdar_trace("phaseshift: %zu rocFFT plans to make", makers.size());
-            if ((rc = impdar_parallel_plans(ctx->device, makers))) return rc;
-            impdar_trace("phaseshift: plans ready");
-            pl.b_ready = true;
-            if (herm) pl.r_ready = true;
-            else pl.c_ready = true;
-        }
-    }
-    if (vlen)
-        for (int i = 0; i < snum; ++i) {
-            const double tau = tt_us[i] / 1.0e6;                         // :441
-            const double r = tau / tt_us[snum - 1] / 1e6;                // :484
-            thr[i] = r * r;
-        }
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_kx.p, kx, (size_t)tnum * 8, hipMemcpyHostToDevice, st));
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_w.p, w.data(), (size_t)nf * 8, hipMemcpyHostToDevice, st));
-    if (vlen) {
-        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_vz.p, vmig, (size_t)snum * 8, hipMemcpyHostToDevice, st));
-        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_thr.p, thr.data(), (size_t)snum * 8, hipMemcpyHostToDevice, st));
-    }
-    PsParams P;
+    if ((rc = ps_make_plans<T>(ctx, pl, R, snum, tnum, nt))) return rc;
+    PsParams P = {};                         // (no schedule, row order or smooth tables, fhalf 0: set where they are made)
     P.F = pl.X.p;
-    P.fstride = fstride;
-    P.k0 = k0;
-    P.nk = nk;
     P.TK = tk_out ? tk_out : pl.TK.p;
     P.kx = pl.d_kx.as<double>();
     P.w = pl.d_w.as<double>();
@@ -2301,448 +2459,73 @@ static int ps_run(impdar_ctx *ctx, PsPlan &pl, const void *d_data, int snum, int
     P.thr = pl.d_thr.as<double>();
     P.vconst = vconst;
     P.dt = dt;
+    P.vtol = dbl ? 1e-11 : 1e-10;
     P.snum = snum;
     P.tnum = tnum;
     P.nt = nt;
-    P.nf = nf;
-    P.herm = herm ? 1 : 0;
+    P.nf = R.nf;
+    P.fstride = R.fstride;
+    P.k0 = k0;
+    P.nk = nk;
+    P.herm = R.herm ? 1 : 0;
     P.vz_mode = vlen ? 1 : 0;
-    P.fhalf = 0;
-    P.vtol = dbl ? 1e-11 : 1e-10;
-    P.sched = P.tsched = P.rowmap = nullptr;
-    P.eps = nullptr;
-    P.sm_step = P.sm_tile = nullptr;
-    P.sm_part = nullptr;
     P.sm_nchunks = 1;
     P.sm_m = 8;
-    std::vector<int> sched, rowmap;
-    std::vector<double> epsum;
-    if (vlen) {
-        // runs of constant velocity (ps_vz32_kernel): a step starts a new run when its velocity differs from the
-        // run's first by more than vtol (relative) -- 2*gradient(z(t)) of a layered table is constant inside a
-        // layer up to ~4e-13 of rounding noise, and a 1e-10 velocity error moves the phase by < 3e-6 rad over
-        // 8192 steps (float32: ignored; float64: vtol 1e-11 and the deviation is carried along as a phase,
-        // ps_vz64_kernel).  Profiles that change at (nearly) every step keep the per-step kernels.
-        const int ntile = (snum + 15) / 16;
-        sched.assign((size_t)snum + (ntile + 31) / 32, 0);
-        double vrun = -1.0;
-        int ndirty = 0;
-        epsum.assign(ntile, 0.0);
-        for (int i = 0; i < snum; ++i) {
-            if (i == 0 || std::fabs(vmig[i] - vrun) > P.vtol * std::fabs(vmig[i])) {     // a run always starts at step 0
-                const int tile = i / 16;
-                const unsigned bit = 1u << (tile & 31);
-                unsigned &word = reinterpret_cast<unsigned &>(sched[snum + tile / 32]);
-                sched[i] = 1;
-                ndirty += (word & bit) ? 0 : 1;
-                word |= bit;
-                vrun = vmig[i];
-            }
-            epsum[i / 16] += vmig[i] / vrun - 1.0;      // float64 kernel: the run's velocity noise, tile by tile
-        }
-        // the per-step tiles of the runs kernels cost several quiet tiles each: beyond a share of such tiles the
-        // per-step kernel is faster for float32 (2048^2, 40 / 80 / 160 layers: 4.6 / 7.5 / 12.2 ms against
-        // 5.5 / 6.8 / 9.5 ms); the float64 runs kernel stays ahead until every tile holds a change (10.1 / 16.6 /
-        // 27.5 ms against 26.4 ms throughout: its per-step tiles pay the square root and sincos at the changes
-        // only).  profiles/tools/ps_dirty.py.
-        const double dirty_max = dbl ? 0.9 : 0.5;
-        bool vfinite = true;                // a velocity profile with NaN / inf entries takes the per-step kernel
-        for (int i = 0; i < snum; ++i) vfinite = vfinite && std::isfinite(vmig[i]) && vmig[i] != 0.0;
-        if (vfinite && ((double)ndirty <= dirty_max * ntile || snum <= 64)) {
-            IMPDAR_HIP_CHECK(pl.d_sched.ensure(sched.size() * sizeof(int)));
-            IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sched.p, sched.data(), sched.size() * sizeof(int), hipMemcpyHostToDevice, st));
-            P.sched = pl.d_sched.as<int>();
-            P.tsched = P.sched + snum;
-            if (dbl) {
-                IMPDAR_HIP_CHECK(pl.d_eps.ensure(epsum.size() * sizeof(double)));
-                IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_eps.p, epsum.data(), epsum.size() * sizeof(double), hipMemcpyHostToDevice, st));
-                P.eps = pl.d_eps.as<double>();
-            }
-        }
-    }
-    // ---- which layout of the spectrum (P.fhalf).  When ps_nufft_kernel will take the call with a pair of wavenumbers per workgroup
-    // (the whole axis, antisymmetric kx; a constant velocity or a table of up to 16 thick layers and 64 runs -- the conditions of the
-    // dispatch below that can be told before the transforms), the transform over the TRACES goes first, on the radargram's own rows
-    // with the taper applied on their way in, and only the wavenumbers k = 0 .. tnum/2 are kept, with all frequencies:
-    //   R2C over x [snum][tnum] -> [snum][tnum/2 + 1];  transpose (zero rows up to nt) -> [tnum/2 + 1][nt];  C2C over t in place
-    // instead of taper + transpose, R2C over t, transpose, C2C over x, transpose: two passes over the array less.  The pair (k, tnum - k)
-    // reads both of its rows out of row k (FK[tnum - k][w] = conj FK[k][-w]).  Should the kernel hand the call on after all (boundary
-    // frequencies beyond its lists), the transforms are repeated in the other layout (front_full below).
-    // ---- will the transform path (ps_nufft_kernel) take a v(z) table?  Its cost is per PIECE (a run of constant velocity, cut at
-    // 4096 / 2048 steps) and per directly summed step of the short runs between them, and hardly depends on the record's length; the
-    // runs kernels' is per (frequency, step) plus a term per run.  Device ms per 8192 wavenumbers, pairs of wavenumbers per transform
-    // (profiles/r06_transforms.txt section 4: tables of 4 ... 41 rows at 8192^2, 4096^2, 2048^2):
-    //   float32  ps_nufft_kernel (0.135 + 0.06 nf/4096) (pieces + short steps / 3)     ps_runs_kernel 1.2 + 8.5 (nf/4096)(snum/8192) + 0.05 runs nf/4096
-    //   float64  up to 24 thick layers from 2048 frequencies on (33.6 against ps_vz64_kernel's 57.2 ms at 41 rows / 21 layers, 8192^2; level at
-    //            4096^2), 16 below
-    bool nufft_first = false;
-    int vz_runs = 0, vz_long = 0;
-    if (vlen) {
-        int len = 0, pieces = 0, nshort = 0;
-        const int lmax = dbl ? 2048 : 4096;
-        auto close_run = [&]() {
-            if (len > PN_SHORT) pieces += (len + lmax - 1) / lmax;
-            else nshort += len;
-            vz_long += len > PM_SHORT;
-        };
-        for (int i = 0; i < snum; ++i) {
-            if (sched[i]) {
-                if (vz_runs) close_run();
-                vz_runs += 1;
-                len = 0;
-            }
-            len += 1;
-        }
-        close_run();
-        const double fq = (double)nf / 4096.0;
-        if (dbl)
-            nufft_first = vz_long <= (nf >= 2048 ? 24 : 16);
-        else
-            nufft_first = nshort <= 128 && (0.135 + 0.06 * fq) * ((double)pieces + (double)nshort / 3.0) <=
-                                               1.2 + 8.5 * fq * ((double)snum / 8192.0) + 0.05 * (double)vz_runs * fq;
-    }
-    // ---- which layout of the spectrum (P.fhalf): see above
-    bool half_front = false;
-    {
-        const char *me = getenv("IMPDAR_PS_MFMA");
-        const int pref = me ? atoi(me) : 1;
-        bool sym = herm && use_own && pl.rows_form && !tk_out && k0 == 0 && nk == tnum && tnum % 2 == 0 && tnum >= 64 && own_fft_len_ok(nt) &&
-                   nf >= 64 && nf <= PN_NFMAX && snum >= 64 && (pref == 1 || pref == 6) &&
-                   !(k_zero.size() > 1 || (k_zero.size() == 1 && k_zero[0] != 0));
-        for (int k = 1; 2 * k < tnum && sym; ++k) sym = kx[k] == -kx[tnum - k];
-        if (sym && !vlen) sym = std::isfinite(vconst) && vconst != 0.0;
-        if (sym && vlen) sym = P.sched != nullptr && (pref == 6 || nufft_first);
-        half_front = sym;
-    }
-    std::vector<double> tap_h, tap_v;
-    if (half_front) {
-        tap_h.resize((size_t)tnum);
-        tap_v.resize((size_t)snum);
-        for (int j = 0; j < tnum; ++j) tap_h[j] = impdar_taper_w(j, tnum, htaper);
-        for (int i = 0; i < snum; ++i) tap_v[i] = impdar_taper_w(i, snum, vtaper);
-        if (pl.d_taper.ensure(((size_t)tnum + snum) * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            half_front = false;
-        } else {
-            IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_taper.p, tap_h.data(), (size_t)tnum * 8, hipMemcpyHostToDevice, st));
-            IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_taper.as<double>() + tnum, tap_v.data(), (size_t)snum * 8, hipMemcpyHostToDevice, st));
-        }
-    }
-    dim3 tgrid((tnum + 63) / 64, (nt + 63) / 64);
-    int rc;
-    // the transforms of the [k][w > 0] layout every kernel reads (Hermitian walk on the library's own or rocFFT's plans)
-    auto front_full = [&]() -> int {
-        int rc;
-        hipLaunchKernelGGL((ps_taper_pad_transpose_real<T>), tgrid, dim3(256), 0, st, (const T *)d_data, pl.Xr.as<T>(), snum,
-                           tnum, nt, htaper, vtaper);
-        if (use_own) {
-            if ((rc = own_fft_launch<T>(OWN_R2C, nt, (size_t)tnum, pl.Xr.p, pl.X.p, (size_t)nt, (size_t)fstride, 1.0, pl.tw_time, st))) return rc;
-        } else if ((rc = pl.r_time.exec(pl.Xr.p, pl.X.p))) {
-            return rc;
-        }
-        if (pl.rows_form) {
-            // over the traces on contiguous rows: X [x][fstride] -> [fstride][x] (pl.TK is free until the frequency sums
-            // write it, and large enough: snum > nt / 2), transform, and back -> X [k][fstride]
-            ps_launch_transpose<T>(pl.X.p, pl.TK.p, tnum, fstride, st);
-            if (use_own) {
-                if ((rc = own_fft_launch<T>(OWN_C2C_FWD, tnum, (size_t)fstride, pl.TK.p, pl.TK.p, (size_t)tnum, (size_t)tnum, 1.0, pl.tw_trace, st))) return rc;
-            } else if ((rc = pl.r_trace.exec(pl.TK.p, nullptr))) {
-                return rc;
-            }
-            ps_launch_transpose<T>(pl.TK.p, pl.X.p, fstride, tnum, st);
-            IMPDAR_HIP_CHECK(hipGetLastError());
-        } else if ((rc = pl.r_trace.exec(pl.X.p, nullptr))) {
-            return rc;
-        }
-        return IMPDAR_OK;
-    };
-    // the call handed on by ps_nufft_kernel after the transforms were made for its pairs: the other layout after all
-    auto leave_half_front = [&]() -> int {
-        if (!P.fhalf) return IMPDAR_OK;
-        impdar_trace("phaseshift: the transform path handed the call on: transforms repeated in the [k][w > 0] layout");
-        P.fhalf = 0;
-        P.fstride = fstride;
-        return front_full();
-    };
+    if ((rc = ps_upload(pl, P, R, dbl, kx, vmig, st))) return rc;
+    bool half_front = R.half_front;
+    std::vector<double> tap;                 // (host staging of this call: alive until the last sync)
+    std::vector<int> rowmap;
+    if (half_front && (rc = ps_taper_upload(pl, tap, snum, tnum, htaper, vtaper, st, &half_front))) return rc;
     if ((rc = impdar_ctx_tic(ctx))) return rc;
-    if (herm && half_front) {
-        const int hs = tnum / 2 + 1;
-        const double *th = pl.d_taper.as<double>(), *tv = th + tnum;
-        // (pl.TK: free until the frequency sums write it, and at least tnum x snum complex)
-        if ((rc = own_fft_launch<T>(OWN_R2C, tnum, (size_t)snum, d_data, pl.TK.p, (size_t)tnum, (size_t)hs, 1.0, pl.tw_trace, st, th, tv))) return rc;
-        {
-            constexpr int TS = sizeof(T) == 4 ? 64 : 32;
-            hipLaunchKernelGGL((ps_transpose_pad<T, TS>), dim3((hs + TS - 1) / TS, (nt + TS - 1) / TS), dim3(256), 0, st, pl.TK.as<Cp<T>>(),
-                               pl.X.as<Cp<T>>(), snum, hs, nt);
-        }
-        if ((rc = own_fft_launch<T>(OWN_C2C_FWD, nt, (size_t)hs, pl.X.p, pl.X.p, (size_t)nt, (size_t)nt, 1.0, pl.tw_time, st))) return rc;
-        IMPDAR_HIP_CHECK(hipGetLastError());
-        P.fhalf = 1;
-        P.fstride = nt;
-        impdar_trace("phaseshift: the transform over the traces first: wavenumbers k >= 0 with all frequencies, for pairs in ps_nufft_kernel");
-    } else if (herm) {
-        if ((rc = front_full())) return rc;
-    } else {
-        hipLaunchKernelGGL((ps_taper_pad_transpose<T>), tgrid, dim3(256), 0, st, (const T *)d_data, pl.X.as<Cp<T>>(), snum,
-                           tnum, nt, htaper, vtaper);
-        if ((rc = pl.f_time.exec(pl.X.p, nullptr))) return rc;
-        if ((rc = pl.f_trace.exec(pl.X.p, nullptr))) return rc;
-    }
-    // (only the runs kernels of the vector path use it, and it costs ~2 ms of host time at config 5 with the GPU idle:
-    // made when they are about to be launched, not when the matrix-core path takes the call)
-    auto order_rows = [&]() -> int {
-        // Launch order.  A wavenumber that holds a frequency on the evanescent boundary of a run walks it in
-        // fp64 in every tile of that run (~2x the tile time); spread over the launch, the last such rows finish
-        // alone after everything else (2 ms at config 5).  They go first, longest first.  The test here only
-        // orders the launch -- generous tolerance, the kernel decides for itself: |0.5 v kx| within 1e-7 of
-        // some |w|.
-        if (nk != tnum) return IMPDAR_OK;                          // (a slab of a sharded run keeps the natural order)
-        // the order depends on the axes and the profile only: a repeated geometry re-uses the last one
-        if (pl.rm_state >= 0 && pl.rm_kx.size() == (size_t)tnum && pl.rm_ws.size() == (size_t)nt && pl.rm_v.size() == (size_t)snum &&
-            memcmp(pl.rm_kx.data(), kx, (size_t)tnum * 8) == 0 && memcmp(pl.rm_ws.data(), ws, (size_t)nt * 8) == 0 &&
-            memcmp(pl.rm_v.data(), vmig, (size_t)snum * 8) == 0) {
-            if (pl.rm_state == 1) P.rowmap = pl.d_rowmap.as<int>();
-            return IMPDAR_OK;
-        }
-        pl.rm_state = -1;
-        pl.rm_kx.assign(kx, kx + tnum);
-        pl.rm_ws.assign(ws, ws + nt);
-        pl.rm_v.assign(vmig, vmig + snum);
-        std::vector<std::pair<double, int>> runs;      // (velocity, steps) of every run
-        for (int i = 0; i < snum; ++i) {
-            if (sched[i]) runs.emplace_back(vmig[i], 0);
-            runs.back().second += 1;
-        }
-        pl.rm_state = 0;
-        if (runs.size() <= 64 && tnum >= 512) {
-            std::vector<double> aw(nt);
-            for (int j = 0; j < nt; ++j) aw[j] = std::fabs(ws[j] == 0.0 ? 1e-10 / dt : ws[j]);
-            std::sort(aw.begin(), aw.end());
-            std::vector<std::pair<int, int>> score(tnum);      // (-steps spent walking, row)
-            int flagged = 0;
-            for (int k = 0; k < tnum; ++k) {
-                int steps = 0;
-                for (const auto &r : runs) {
-                    const double target = 0.5 * r.first * std::fabs(kx[k]);
-                    const auto it = std::lower_bound(aw.begin(), aw.end(), target);
-                    const double hi = it != aw.end() ? *it : aw.back(), lo = it != aw.begin() ? *(it - 1) : aw.front();
-                    const double band = dbl ? 2e-6 : 1e-7;
-                    if (std::fabs(hi - target) <= band * target || std::fabs(lo - target) <= band * target) steps += r.second;
-                }
-                score[k] = std::make_pair(-steps, k);
-                flagged += steps > 0;
-            }
-            if (flagged > 0 && flagged < tnum) {
-                std::stable_sort(score.begin(), score.end());
-                rowmap.resize(tnum);
-                for (int b = 0; b < tnum; ++b) rowmap[b] = score[b].second;
-                IMPDAR_HIP_CHECK(pl.d_rowmap.ensure((size_t)tnum * sizeof(int)));
-                IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_rowmap.p, rowmap.data(), (size_t)tnum * sizeof(int), hipMemcpyHostToDevice, st));
-                P.rowmap = pl.d_rowmap.as<int>();
-                pl.rm_state = 1;
-            }
-        }
-        return IMPDAR_OK;
-    };
+    if ((rc = ps_front<T>(pl, P, R, half_front, d_data, htaper, vtaper, st))) return rc;
     if ((rc = impdar_ctx_ktic(ctx))) return rc;
     impdar_trace("phaseshift: forward transforms enqueued");
-    bool mfma_done = false;
-    const char *mfma_kernel_name = "";
+    bool done = false;
+    const char *kernel = "";
     pl.mfma_instructions = -1.0;
-    int long_runs = 0;                       // runs of constant velocity longer than a smeared layer boundary (metrics)
-    if constexpr (sizeof(T) == 8) {
-        // float64 data at a constant velocity: the transform path (ps_nufft.h: a 14-point window in float64 arithmetic); a v(z)
-        // table keeps the vector kernels (the velocity noise inside its runs: ps_nufft.h)
-        const char *me = getenv("IMPDAR_PS_MFMA");
-        const int pref = me ? atoi(me) : 1;
-        if (!vlen && pref != 0 && std::isfinite(vconst) && vconst != 0.0) {
-            std::vector<PsMfmaRun> one{PsMfmaRun{vconst, 0, snum}};
-            if ((rc = ps_nufft_run<double>(pl, P, one, false, kx, w.data(), thr.data(), st, &mfma_done, nullptr, tk_out == nullptr))) return rc;
-            if (!mfma_done && (rc = leave_half_front())) return rc;
-            if (mfma_done) mfma_kernel_name = "ps_nufft_kernel";
+    for (const PsAttempt &a : R.attempts) {
+        // Only ps_nufft_kernel reads the half layout: a call it handed on gets the other one (SERIES never meets fhalf: its conditions exclude half_front's)
+        if (P.fhalf && a.kind != PS_NUFFT) {
+            impdar_trace("phaseshift: the transform path handed the call on: transforms repeated in the [k][w > 0] layout");
+            P.fhalf = 0;
+            P.fstride = R.fstride;
+            if ((rc = ps_front_full<T>(pl, P, R, d_data, htaper, vtaper, st))) return rc;
         }
-        // a v(z) table of up to 16 thick layers: the transform path with the runs' velocity noise (~4e-13, cut at 1e-11) as its
-        // first-order term (ps_nufft.h); 6 asks for it at any number of layers
-        if (vlen && P.sched && (pref == 1 || pref == 6)) {
-            std::vector<PsMfmaRun> mruns;
-            bool ok = true;
-            for (int i = 0; i < snum && ok; ++i) {
-                ok = std::isfinite(vmig[i]) && vmig[i] != 0.0;
-                if (sched[i]) mruns.push_back(PsMfmaRun{vmig[i], i, 0});
-                if (!mruns.empty()) mruns.back().len += 1;
-            }
-            int nlong = 0;
-            for (const PsMfmaRun &r : mruns) nlong += r.len > PM_SHORT;
-            long_runs = nlong;
-            if (ok && (pref == 6 || nufft_first)) {
-                if ((rc = ps_nufft_run<double>(pl, P, mruns, true, kx, w.data(), thr.data(), st, &mfma_done, vmig, tk_out == nullptr))) return rc;
-                if (!mfma_done && (rc = leave_half_front())) return rc;
-                if (mfma_done) mfma_kernel_name = "ps_nufft_kernel";
-            }
+        switch (a.kind) {
+        case PS_SERIES:
+            rc = ps_series_run<T>(pl, P, vmig, kx, R.w.data(), R.thr.data(), st, &done, a.alt, tk_out == nullptr);
+            kernel = "ps_series_kernel";
+            break;
+        case PS_NUFFT:      // (float64 v(z): the per-step velocities too -- the runs' rounding noise as a first-order term)
+            rc = ps_nufft_run<T>(pl, P, R.runs, vlen != 0, kx, R.w.data(), R.thr.data(), st, &done, R.kx_antisym, dbl && vlen ? vmig : nullptr,
+                                 tk_out == nullptr);
+            kernel = "ps_nufft_kernel";
+            break;
+        case PS_RUNS:
+            rc = ps_runs_run(pl, P, R.runs, kx, R.w.data(), R.thr.data(), st, &done);
+            kernel = "ps_runs_kernel";
+            break;
+        case PS_MFMA:
+            rc = ps_mfma_run(pl, P, R.runs, vlen != 0, kx, R.thr.data(), K.edge_overflow, st, &done, &kernel);
+            break;
+        case PS_SMOOTH:
+            if ((rc = ps_smooth_run<T>(pl, P, R, vmig, st, &done))) return rc;
+            if (done) kernel = t_ps_kernel;
+            break;
+        default:            // PS_VECTOR; with a schedule, the launch order of its runs kernels is made now
+            if (R.use_sched && (rc = ps_order_rows(pl, P, R, rowmap, kx, ws, vmig, dbl, st))) return rc;
+            if ((rc = ps_dispatch<T>(P, st))) return rc;
+            kernel = t_ps_kernel;
+            done = true;
         }
-        // any other v(z) profile -- a velocity that changes at every step, many layers: the series path (ps_series.h)
-        if (vlen && !mfma_done && (pref == 1 || pref == 7)) {
-            // (what would run otherwise: ps_smooth_kernel, 10.8e-6 ms per alive pair; the runs kernel ps_vz64_kernel
-            // -- 43 ms for the record + 0.09 per step that starts a run, at 8192^2 (4-row table 43, 41 rows 56, a firn column's
-            // 1960 changing steps 226; 4096^2: 14 / 121 per 8192 wavenumbers): profiles/r06_series.txt)
-            int nstarts = 0;
-            if (P.sched)
-                for (int i = 0; i < snum; ++i) nstarts += sched[i] != 0;
-            const double alt = pref == 7 ? 0.0 : (P.sched ? 43.0 * ((double)nf / 4096.0) * ((double)snum / 8192.0) + 0.09 * (double)nstarts * ((double)nf / 4096.0)
-                                                          : -SR_MS_PER_PAIR_F64);
-            if ((rc = ps_series_run<double>(pl, P, vmig, kx, w.data(), thr.data(), st, &mfma_done, alt, tk_out == nullptr))) return rc;
-            if (mfma_done) mfma_kernel_name = "ps_series_kernel";
+        if (rc) return rc;
+        if (done) {
+            ps_metrics(ctx, pl, P, R, kernel, a.kind <= PS_MFMA && pl.mfma_instructions >= 0.0, tk_out != nullptr);
+            break;
         }
     }
-    if constexpr (sizeof(T) == 4) {
-        // float32: the frequency sums on the matrix cores when the depth axis is a few long runs of constant velocity
-        std::vector<PsMfmaRun> mruns;
-        bool ok = true;
-        if (vlen) {
-            for (int i = 0; i < snum && ok; ++i) {
-                ok = std::isfinite(vmig[i]) && vmig[i] != 0.0;
-                if (sched[i]) mruns.push_back(PsMfmaRun{vmig[i], i, 0});
-                if (!mruns.empty()) mruns.back().len += 1;
-            }
-        } else {
-            mruns.push_back(PsMfmaRun{vconst, 0, snum});
-        }
-        // IMPDAR_PS_MFMA: 0 the vector kernels only; 2 / 3 only ps_mfma_kernel / only ps_runs_kernel of the matrix-core
-        // paths (A/B runs, tests).  By themselves: up to 3 thick layers -> ps_mfma_kernel (64-step tiles, phases from a table);
-        // more long runs -> ps_runs_kernel (8-step tiles, phases generated in the kernel); whichever declines
-        // (ps_mfma_kernel: rows mostly padding on short records) hands over to the other, then to the vector kernels.
-        const char *me = getenv("IMPDAR_PS_MFMA");
-        const int pref = me ? atoi(me) : 1;
-        int nlong = 0;
-        for (const PsMfmaRun &r : mruns) nlong += r.len > PM_SHORT;
-        long_runs = nlong;
-        const bool force_overflow = getenv("IMPDAR_PS_TEST_EDGE_OVERFLOW") != nullptr;
-        // (8192^2 device ms, equal layers, profiles/r05_ps_runs.txt: ps_mfma_kernel 12.9 / 15.7 / 16.0 / 19.7 / 26.8 at 3 / 4 / 5 / 7 /
-        // 11 long runs -- and 10.8 on the config-5 table; ps_runs_kernel, two wavenumbers per workgroup, 11.8 / 11.9 / 12.4 /
-        // 12.8 / 13.8 at 3 / 4 / 5 / 7 / 11 long runs, 15.3 at 21, 21.3 at 42, 12.0 on the config-5 table)
-        const bool runs_first = vlen != 0 && nlong > 3;
-        // ... 6: only the transform path (ps_nufft.h) ahead of them.  By itself: the transform path for a constant velocity and
-        // tables of up to 16 thick layers (8192^2 device ms at 3 / 5 / 7 / 11 / 16 / 21 long runs: 5.1 / 6.1 / 7.2 / 9.5 / 13.0 /
-        // 16.8 against ps_runs_kernel's 11.8 / 12.4 / 12.8 / 13.7 / 14.4 / 15.3; config 5: 4.5 against ps_mfma_kernel's 10.6,
-        // constant velocity 3.0 against 6.8 -- profiles/r05_ps_nufft.txt), then the matrix-core paths as before
-        // ... 7: only the series path (ps_series.h).  By itself: profiles without runs of constant velocity to live on
-        if (ok && vlen && (pref == 7 || (pref == 1 && !(P.sched && nufft_first) && (!P.sched || mruns.size() > 64))) && !force_overflow) {
-            // (what would run otherwise, at 8192^2: ps_smooth32_kernel 5.3e-6 ms per alive pair; ps_runs_kernel 8 ms + 0.036 per run,
-            // long or single step -- 41 / 81 / 161 table rows = 160 / 320 / 640 runs: 13.8 / 19.8 / 30.5 ms; a firn column's 1470: 70)
-            const double alt = pref == 7 ? 0.0 : (!P.sched ? -SR_MS_PER_PAIR_F32
-                                                           : 8.0 * ((double)nf / 4096.0) * ((double)snum / 8192.0) + 0.036 * (double)mruns.size() * ((double)nf / 4096.0));
-            if ((rc = ps_series_run<float>(pl, P, vmig, kx, w.data(), thr.data(), st, &mfma_done, alt, tk_out == nullptr))) return rc;
-            if (mfma_done) mfma_kernel_name = "ps_series_kernel";
-        }
-        if (ok && !mfma_done && (pref == 6 || (pref == 1 && (!vlen || (P.sched && nufft_first)))) && !force_overflow) {
-            if ((rc = ps_nufft_run<float>(pl, P, mruns, vlen != 0, kx, w.data(), thr.data(), st, &mfma_done, nullptr, tk_out == nullptr))) return rc;
-            if (!mfma_done && (rc = leave_half_front())) return rc;
-            if (mfma_done) mfma_kernel_name = "ps_nufft_kernel";
-        }
-        for (int turn = 0; turn < 2 && ok && !mfma_done && pref != 0 && pref != 7; ++turn) {
-            const bool use_runs = (turn == 0) == runs_first;
-            if (use_runs) {
-                if (pref == 2 || !vlen || force_overflow) continue;
-                if ((rc = ps_runs_run(pl, P, mruns, kx, w.data(), thr.data(), st, &mfma_done))) return rc;
-                if (mfma_done) mfma_kernel_name = "ps_runs_kernel";
-            } else {
-                if (pref == 3) continue;
-                const char *name = "";
-                if ((rc = ps_mfma_run(pl, P, mruns, vlen != 0, kx, thr.data(), st, &mfma_done, &name))) return rc;
-                if (mfma_done) mfma_kernel_name = name;
-            }
-        }
-    }
-    if (!mfma_done && (rc = leave_half_front())) return rc;         // (whatever the dispatch did: no other kernel reads P.fhalf)
-    // (made only when the runs kernels of the vector path are about to be launched: ~2 ms of host time with the GPU idle)
-    if (!mfma_done && P.sched && (rc = order_rows())) return rc;
-    bool smooth_done = false;
-    if (!mfma_done && vlen && !P.sched) {
-        // no runs of constant velocity to live on (the velocity changes in most 16-step tiles): ps_smooth_kernel
-        bool ok = true;
-        for (int i = 0; i < snum && ok; ++i) ok = std::isfinite(vmig[i]) && vmig[i] != 0.0 && thr[i] < 1e-10;
-        if (ok) {
-            // float32, the whole wavenumber axis with kx[tnum - k] = -kx[k]: rows k and tnum - k in one wave (ps_smooth.h)
-            bool sm_pairs = P.k0 == 0 && nk == tnum && tnum >= 2;
-            for (int k = 1; 2 * k < tnum && sm_pairs; ++k) sm_pairs = kx[k] == -kx[tnum - k];
-            P.sm_m = ps_smooth_m(dbl, sm_pairs);
-            P.sm_nchunks = ps_smooth_chunks(nf, P.sm_m);
-            const size_t part_bytes = P.sm_nchunks > 1 ? (size_t)P.sm_nchunks * nk * snum * sizeof(Cp<T>) : 0;
-            std::vector<double> &sm_step = pl.h_sm_step, &sm_tile = pl.h_sm_tile;     // (alive until the next call: async copies)
-            if (sizeof(T) == 4) ps_smooth_tables(vmig, thr.data(), snum, sm_step, sm_tile);
-            // (no room for the partial images: the per-step kernels below)
-            if (pl.d_sm.ensure((sm_step.size() + sm_tile.size()) * 8 + 64) == hipSuccess &&
-                (!part_bytes || pl.d_part.ensure(part_bytes) == hipSuccess)) {
-                if (sizeof(T) == 4) {
-                    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sm.p, sm_step.data(), sm_step.size() * 8, hipMemcpyHostToDevice, st));
-                    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sm.as<double>() + sm_step.size(), sm_tile.data(), sm_tile.size() * 8,
-                                                    hipMemcpyHostToDevice, st));
-                    P.sm_step = pl.d_sm.as<double>();
-                    P.sm_tile = pl.d_sm.as<double>() + sm_step.size();
-                }
-                P.sm_part = pl.d_part.p;
-                ps_smooth_launch<T>(P, st, sm_pairs);
-                IMPDAR_HIP_CHECK(hipGetLastError());
-                t_ps_kernel = sizeof(T) == 4 ? "ps_smooth32_kernel" : "ps_smooth_kernel";
-                smooth_done = true;
-            } else {
-                (void)hipGetLastError();
-                P.sm_nchunks = 1;
-            }
-        }
-    }
-    if (!mfma_done && !smooth_done && (rc = ps_dispatch<T>(P, st))) return rc;
-    ctx->m_entry = tk_out ? "impdar_phaseshift_tk_dev" : "impdar_phaseshift";
-    ctx->m_kernel = mfma_done ? mfma_kernel_name : t_ps_kernel;
-    ctx->m_kernel_ms = -1.f;                 // (bracketed by ktic / ktoc)
-    if (mfma_done && pl.mfma_instructions >= 0.0)      // (MFMA instructions the kernel issued, counted by the kernel: rounds and blocks it skips are not in it)
-        snprintf(ctx->m_extra, sizeof ctx->m_extra,
-                 "\"hermitian_walk\": %s, \"frequencies\": %d, \"transforms\": \"%s\", \"long_runs\": %d, \"mfma_instructions\": %.0f, \"flop_per_mfma\": %d",
-                 herm ? "true" : "false", nf, use_own ? "own" : "rocfft", long_runs, pl.mfma_instructions,
-                 strcmp(mfma_kernel_name, "ps_runs_kernel") == 0 ? 16384 : 32768);
-    else
-        snprintf(ctx->m_extra, sizeof ctx->m_extra, "\"hermitian_walk\": %s, \"frequencies\": %d, \"transforms\": \"%s\", \"long_runs\": %d, \"spectrum\": \"%s\"",
-                 herm ? "true" : "false", nf, use_own ? "own" : "rocfft", long_runs, P.fhalf ? "k >= 0, all frequencies" : "all k, frequencies walked");
-    if (herm)
-        for (int kz : k_zero)
-            if (kz >= k0 && kz < k0 + nk)
-                hipLaunchKernelGGL((ps_dc_kernel<T>), dim3((snum + 255) / 256), dim3(256), 0, st, pl.X.as<Cp<T>>(),
-                                   reinterpret_cast<Cp<T> *>(P.TK), kz, kz - k0, P.fstride, snum, w0 * dt);
-    if ((rc = impdar_ctx_ktoc(ctx))) return rc;
-    if (tk_out) {
-        IMPDAR_HIP_CHECK(hipGetLastError());
-        if ((rc = impdar_ctx_toc(ctx))) return rc;
-        IMPDAR_HIP_CHECK(hipStreamSynchronize(st));
-        return IMPDAR_OK;
-    }
-    if (pl.rows_form) {
-        // inverse over k on contiguous rows: TK [k][tau] -> [tau][k] (pl.X: the spectrum is not needed any more, and
-        // nt >= snum), transform, real part (:282) -- already (snum, tnum)
-        if (use_own && tnum >= 32) {
-            // (the real part is all that is kept: the Hermitian half of the sums goes through a real inverse transform of half
-            // the length -- ps_transpose_herm; until round 6 a full transpose and a complex transform that stored real parts:
-            // 175 + 314 us at 8192^2 float32)
-            const int hs = tnum / 2 + 1;
-            ps_launch_transpose_herm<T>(pl.TK.p, pl.X.p, tnum, snum, hs, st);
-            if ((rc = own_fft_launch<T>(OWN_C2R, tnum, (size_t)snum, pl.X.p, d_out, (size_t)hs, (size_t)tnum, 1.0 / tnum, pl.tw_trace, st))) return rc;
-        } else if (use_own) {
-            ps_launch_transpose<T>(pl.TK.p, pl.X.p, tnum, snum, st);
-            if ((rc = own_fft_launch<T>(OWN_C2C_INV_RE, tnum, (size_t)snum, pl.X.p, d_out, (size_t)tnum, (size_t)tnum, 1.0 / tnum, pl.tw_trace, st))) return rc;
-        } else {
-            ps_launch_transpose<T>(pl.TK.p, pl.X.p, tnum, snum, st);
-            if ((rc = pl.b_trace.exec(pl.X.p, nullptr))) return rc;
-            const size_t n = (size_t)snum * tnum;
-            hipLaunchKernelGGL((ps_real_part<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pl.X.as<Cp<T>>(), (T *)d_out, n);
-        }
-    } else {
-        if ((rc = pl.b_trace.exec(pl.TK.p, nullptr))) return rc;
-        dim3 bgrid((tnum + 63) / 64, (snum + 63) / 64);
-        hipLaunchKernelGGL((ps_real_transpose<T>), bgrid, dim3(256), 0, st, pl.TK.as<Cp<T>>(), (T *)d_out, snum, tnum);
-    }
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    if ((rc = impdar_ctx_toc(ctx))) return rc;
-    impdar_trace("phaseshift: all kernels enqueued");
-    // host staging vectors (w, thr) must outlive the async copies
+    if ((rc = ps_back<T>(ctx, pl, P, R, tk_out != nullptr, d_out))) return rc;
+    // host staging vectors (R.w, R.thr, the schedule, tap, rowmap) must outlive the async copies
     IMPDAR_HIP_CHECK(hipStreamSynchronize(st));
     return IMPDAR_OK;
 }

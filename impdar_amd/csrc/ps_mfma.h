@@ -49,6 +49,7 @@
 // step's own velocity, mig_python.py:456-485) take no part: they are listed per wavenumber and ps_edge_kernel walks
 // them over the whole depth axis in float64 afterwards, the way the reference does.
 #pragma once
+#include "ps_route.h"        // PsMfmaRun, PM_SHORT
 
 typedef _Float16 pm_half8 __attribute__((ext_vector_type(8)));
 typedef float pm_float16 __attribute__((ext_vector_type(16)));
@@ -68,13 +69,7 @@ constexpr int PM_WAVES = PM_NQ * PM_NP;
 constexpr int PM_RED_LD = 20;               // dwords per lane in the final reduction image (16 + 4: conflict-free b128)
 constexpr int PM_EMAX = 16;                 // boundary frequencies listed per wavenumber
 constexpr int PM_MAX_RUNS = 96;
-constexpr int PM_SHORT = 8;                 // runs of up to this many steps (the few steps a layer boundary is smeared over) get no row blocks: ps_trans_kernel
 constexpr size_t PM_LDS_BYTES = ((size_t)PM_NQ * PM_NRB * 2 + (size_t)PM_WAVES * 2) * PM_TILE * 4 + 64;
-
-struct PsMfmaRun {
-    double v;               // velocity of the run (v(z)); unused for constant velocity
-    int start, len;         // first depth step, number of steps
-};
 
 struct PsMfmaParams {
     PsParams P;

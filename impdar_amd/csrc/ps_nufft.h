@@ -27,15 +27,14 @@
 // grid points: the coefficients and the spreading cost per PIECE, frequencies x 8 window values, the FFT per grid point: long
 // pieces are the cheap ones; LDS by the call's longest piece, <= 126 KB, 159 KB for a pair).  The few single steps a layer boundary
 // is smeared over are summed directly (a sincos per frequency and step, block reduction in a fixed order): a seventh of a piece
-// each.  Which tables come here and which go to ps_runs_kernel: an estimate of both (ps_run, phaseshift.hip).  Frequencies on the
+// each.  Which tables come here and which go to ps_runs_kernel: an estimate of both (ps_route.h).  Frequencies on the
 // evanescent boundary of some run take no part and are listed for ps_edge_kernel, as in ps_mfma.h / ps_runs.h; for a constant
 // velocity the reference's own test decides them (:411-412).
 // Measured at 8192^2: round 5 (profiles/r05_ps_nufft.txt) config 5 3.7 ms (ps_mfma_kernel 9.1), constant velocity 1.6 ms (5.3);
 // round 6 with pairs (profiles/r06_transforms.txt) 1.64 and 0.90 ms; float64 data 6.7 and 4.0 ms.
 #pragma once
+#include "ps_route.h"        // PN_NFMAX, PN_SHORT
 
-constexpr int PN_NFMAX = 4096;              // frequencies per wavenumber this kernel takes (one workgroup holds them all)
-constexpr int PN_SHORT = 8;                 // runs of up to this many steps are summed directly
 // float32 data: a window of 8 grid points (3.5e-7 of the result in float32 arithmetic), 1024 threads;
 // float64 data: 14 points (5e-13 in float64 arithmetic; the stated bar against the reference is 1e-10), 512 threads.
 // A v(z) TABLE on float64 data: inside a "run" the interpolated velocity carries ~4e-13 of rounding noise (2 * gradient(z(t));
