@@ -7,7 +7,9 @@ three-step chain with and without residency), the horizontal filters (hfilt, ada
 hfilt at windows 10 and 1000), denoise (Wiener and median at several windows) and the horizontal frequency
 filters (hbp, lp, hp; float64, as constant_space hands them on) at the same size, resident, the sample-axis steps
 (nmo, pretrigger crop, elev_correct), the gains (rangegain, agc), the trace-axis steps (reverse, hcrop, restack) and
-winavg_hfilt beside a device-to-device copy of equal bytes,
+winavg_hfilt beside a device-to-device copy of equal bytes, and Stolt at the headline radargram's shape (4096 samples x 10000
+traces, no power of two: the library's own mixed-radix row transforms against rocFFT's plans, steady state and the first call
+of a fresh process),
 each through the product path on one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
@@ -25,8 +27,70 @@ import numpy as np
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.abspath(__file__)))
 
 
+FIELD = (4096, 10000)           # snum x tnum of the "stolt 4096 x 10000" line: the headline radargram's shape
+
+
+def stolt_first_call_child():
+    """`bench_paths.py --stolt-first-call`: a fresh process, as `impproc migrate file.mat` is -- import, context, the FIRST Stolt
+    call of the process on a host array under the IMPDAR_STOLT_FFT of the environment, a second call for contrast.  One JSON line."""
+    import contextlib
+    import ctypes
+    import io
+    from impdar_amd import _hip, synth
+    from impdar_amd.lib.RadarData import RadarData
+    snum, tnum = FIELD
+    geo = synth.geometry(snum, tnum)
+    x = np.random.default_rng(0).standard_normal((snum, tnum)).astype(np.float32)
+    _hip.load()
+    _hip.context()
+    walls = []
+    for _ in range(2):
+        d = RadarData(None)
+        d.data, d.snum, d.tnum = x, snum, tnum
+        d.travel_time, d.dist, d.trace_int, d.dt = geo['travel_time'], geo['dist'], geo['trace_int'], geo['dt']
+        t0 = time.perf_counter()
+        with contextlib.redirect_stdout(io.StringIO()):
+            d.migrate('stolt', vel=1.68e8, htaper=100, vtaper=1000)
+        walls.append((time.perf_counter() - t0) * 1e3)
+    buf = ctypes.create_string_buffer(1024)
+    _hip.check(_hip.load().impdar_ctx_last_metrics(_hip.context(), buf, len(buf)), 'metrics')
+    print(json.dumps({"first_call_ms": walls[0], "second_call_ms": walls[1], "kernel": json.loads(buf.value.decode())['kernel'],
+                      "finite": bool(np.isfinite(d.data).all())}))
+
+
+def stolt_first_calls(children=3):
+    """The first-call children of the "stolt 4096 x 10000" line, started before this process touches the GPU.  Per form
+    (the default route: the own mixed-radix transforms; IMPDAR_STOLT_FFT=rocfft: the plans) one process against an empty rocFFT
+    kernel database (`cold`), then `children` more against the database it left (`warm_cache`: what every later process pays)."""
+    import os
+    import subprocess
+    import tempfile
+    out = {}
+    for form, knob in (('mixed', None), ('rocfft', 'rocfft')):
+        with tempfile.TemporaryDirectory() as tmp:
+            env = dict(os.environ, HOME=tmp, XDG_CACHE_HOME=os.path.join(tmp, 'xdg'), ROCFFT_RTC_CACHE_PATH=os.path.join(tmp, 'rocfft_kernel_cache.db'))
+            env.pop('IMPDAR_STOLT_FFT', None)
+            if knob:
+                env['IMPDAR_STOLT_FFT'] = knob
+            recs = []
+            for _ in range(1 + children):
+                try:
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--stolt-first-call'], capture_output=True, text=True,
+                                       timeout=240, env=env)
+                    line = [l for l in r.stdout.splitlines() if l.startswith('{"first_call_ms"')]
+                    recs.append(json.loads(line[-1]) if line else {"error": (r.stderr or r.stdout)[-300:]})
+                except Exception as exc:
+                    recs.append({"error": "%s: %s" % (type(exc).__name__, exc)})
+            warm = [r['first_call_ms'] for r in recs[1:] if 'first_call_ms' in r]
+            out[form] = {"cold": recs[0], "warm_cache": recs[1:], "warm_cache_first_call_ms": warm,
+                         "warm_cache_median_ms": float(np.median(warm)) if warm else None,
+                         "warm_cache_spread_ms": (max(warm) - min(warm)) if warm else None}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--stolt-first-call', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--stolt', type=int, default=4096)
     ap.add_argument('--phsh', type=int, default=8192)
     ap.add_argument('--chain', type=str, default='4096x10000', help='snum x tnum of the band-pass / re-spacing lines')
@@ -34,6 +98,9 @@ def main():
     ap.add_argument('--skip', default='')
     ap.add_argument('--no-cpu', action='store_true')
     args = ap.parse_args()
+    if args.stolt_first_call:
+        return stolt_first_call_child()
+    field_first = stolt_first_calls() if 'field' not in args.skip else None        # (children first: this process has not opened the GPU yet)
     from impdar_amd import _hip, synth
     from impdar_amd.lib.RadarData import RadarData
     from impdar_amd.lib import migrationlib
@@ -80,6 +147,56 @@ def main():
                           "host_seconds": el, "traces_per_s": n / el, "finite": bool(np.isfinite(d.data).all()),
                           "algorithmic_bytes": 40 * n * n, "reference_seconds_same_size": 100.30,
                           "cpu_baseline": cb}), flush=True)
+    if 'field' not in args.skip:
+        # Stolt at the headline radargram's shape, resident: the default route (R2C / C2R of 10000 on the mixed-radix kernel, C2C of 4096
+        # on the power-of-two one) against IMPDAR_STOLT_FFT=rocfft (what ran at this size before), the calls alternated in this
+        # process after warm-up; device time from the HIP events of each call; bytes from config 2's pass model (40 B per sample)
+        import ctypes
+        import os
+        snum, tnum = FIELD
+        ctx, lib = _hip.context(), _hip.load()
+        geo = synth.geometry(snum, tnum)
+        xf = rng.standard_normal((snum, tnum)).astype(np.float32)
+        d_x = _hip.DeviceArray.from_host(ctx, xf)
+        d_o = _hip.DeviceArray(ctx, (snum, tnum), np.float32)
+        kx_keep, p_kx = _hip.as_dp(2. * np.pi * np.fft.fftfreq(tnum, d=float(np.mean(geo['trace_int']))))
+        ws_keep, p_ws = _hip.as_dp(2. * np.pi * np.fft.rfftfreq(snum, d=geo['dt']))       # (the arrays stay alive with the pointers)
+        buf = ctypes.create_string_buffer(1024)
+        saved = os.environ.pop('IMPDAR_STOLT_FFT', None)
+
+        def call(knob):
+            if knob:
+                os.environ['IMPDAR_STOLT_FFT'] = knob
+            else:
+                os.environ.pop('IMPDAR_STOLT_FFT', None)
+            _hip.check(lib.impdar_stolt_dev(ctx, d_x.ptr, _hip.F32, snum, tnum, p_kx, p_ws, 1.68e8, 100., 1000., d_o.ptr), 'impdar_stolt_dev')
+            _hip.check(lib.impdar_ctx_last_metrics(ctx, buf, len(buf)), 'metrics')
+            return json.loads(buf.value.decode())
+
+        forms = (('mixed', None), ('rocfft', 'rocfft'))
+        images, kernels, ms = {}, {}, {'mixed': [], 'rocfft': []}
+        for form, knob in forms:                     # warm-up: code objects, rocFFT's plans, buffers
+            for _ in range(2):
+                kernels[form] = call(knob)['kernel']
+            images[form] = d_o.to_host().astype(np.float64)
+        for _ in range(max(10, args.reps)):
+            for form, knob in forms:
+                ms[form].append(call(knob)['device_ms'])
+        if saved is not None:
+            os.environ['IMPDAR_STOLT_FFT'] = saved
+        d_x.free()
+        d_o.free()
+        algo = 40 * snum * tnum
+        rec = {"path": "stolt 4096 x 10000 float32", "config": "%dx%d float32, resident (snum x tnum: the headline radargram's shape)" % (snum, tnum),
+               "algorithmic_bytes": algo, "rel_l2_mixed_vs_rocfft": float(np.linalg.norm(images['mixed'] - images['rocfft']) / np.linalg.norm(images['rocfft'])),
+               "finite": bool(np.isfinite(images['mixed']).all()), "first_call": field_first}
+        for form, _ in forms:
+            t = float(np.median(ms[form]))
+            rec[form] = {"kernel": kernels[form], "device_ms": t, "device_ms_spread": max(ms[form]) - min(ms[form]), "device_ms_all": ms[form],
+                         "ns_per_sample": t * 1e6 / (snum * tnum),
+                         "roofline": {"bound": "hbm", "achieved": algo / t / 1e6, "peak": 8000.0, "unit": "GB/s", "frac": algo / t / 1e6 / 8000.0}}
+        rec["power_of_two_record_ns_per_sample"] = 0.27e6 / 4096 ** 2         # config 2: 0.27 ms at 4096 x 4096
+        print(json.dumps(rec), flush=True)
     if 'phsh' not in args.skip:
         n = args.phsh
         geo = synth.geometry(n, n)

@@ -7,7 +7,9 @@
 // migrate` is one process per call, so the first call IS the call).  These kernels are part of the library's own code
 // object -- nothing to compile, nothing to look up, no plan to make -- and run within 0.03 ms of rocFFT's plans at 8192^2
 // (level at Stolt 4096^2), so power-of-two sizes use them on every call (IMPDAR_STOLT_FFT / IMPDAR_PS_FFT = rocfft ask for
-// the plans; other sizes keep rocFFT).
+// the plans).  Lengths 2^a 3^b 5^c 7^d that are no power of two -- what field records have -- run on the mixed-radix kernel
+// of own_fft_mixed.h, under the same contract: own_fft_launch sends them there.  Stolt takes that route (stolt.hip); the
+// phase shift keeps rocFFT at those sizes, as does every length with a prime factor above 7 or beyond the LDS.
 //
 // Reference semantics (numpy.fft, mig_python.py:159,202,270,282): unnormalised forward transforms with e^{-2 pi i k n / N},
 // inverse with e^{+...} and no 1/N (the caller passes the scale, as with the rocFFT plans).
@@ -253,6 +255,8 @@ struct OwnTwiddles {
     }
 };
 
+#include "own_fft_mixed.h"
+
 // mode: OWN_*; n = the transform length (complex length for C2C, real length for R2C / C2R); dists in elements of the
 // respective side (complex for complex rows, real for real rows)
 template <typename T>
@@ -260,6 +264,9 @@ static int own_fft_launch(int mode, int n, size_t batch, const void *in, void *o
                           const OwnTwiddles &tw, hipStream_t st, const double *wcol = nullptr, const double *wrow = nullptr, int wfirst = 0)
 {
     const int M = (mode == OWN_R2C || mode == OWN_C2R) ? n / 2 : n;
+    // (a power of two stays on own_fft_rows; any other length the mixed-radix plan takes goes to own_fft_rows_mixed)
+    if ((n & (n - 1)) != 0 && own_fft_mixed_len_ok(M))
+        return own_fft_mixed_launch<T>(mode, n, batch, in, out, in_dist, out_dist, scale, tw, st, wcol, wrow, wfirst);
     int logm = 0;
     while ((1 << logm) < M) ++logm;
     if (!own_fft_len_ok(M) || (1 << logm) != M || tw.nt != n || tw.dbl != (sizeof(T) == 8)) {

@@ -63,12 +63,19 @@ std::mutex &impdar_fft_plan_mutex()
     return mu;
 }
 
-extern "C" int impdar_fft_rows_dev(impdar_ctx *ctx, int mode, int dtype, int n, int batch, const void *d_in, void *d_out, double scale)
+// any: lengths 2^a 3^b 5^c 7^d too (impdar_fft_rows_any_dev)
+static int fft_rows_dev(impdar_ctx *ctx, bool any, int mode, int dtype, int n, int batch, const void *d_in, void *d_out, double scale)
 {
     IMPDAR_ARG_CHECK(ctx && d_in && d_out, "null argument");
     IMPDAR_ARG_CHECK(mode >= 0 && mode <= 4 && (dtype == IMPDAR_F32 || dtype == IMPDAR_F64) && batch >= 1, "bad mode / dtype / batch");
-    const int M = (mode == OWN_R2C || mode == OWN_C2R) ? n / 2 : n;
-    IMPDAR_ARG_CHECK(n >= 2 && (n & (n - 1)) == 0 && own_fft_len_ok(M), "length %d is not a power of two in range", n);
+    const bool real = mode == OWN_R2C || mode == OWN_C2R;
+    const int M = real ? n / 2 : n;
+    const bool pow2 = n >= 2 && (n & (n - 1)) == 0 && own_fft_len_ok(M);
+    if (any)
+        IMPDAR_ARG_CHECK(pow2 || (n >= 2 && !(real && n % 2) && own_fft_mixed_len_ok(M)),
+                         "length %d: the complex length must be 16 .. 8192 with no prime factor above 7 (a real length even)", n);
+    else
+        IMPDAR_ARG_CHECK(pow2, "length %d is not a power of two in range", n);
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     OwnTwiddles tw;
     int rc;
@@ -84,6 +91,16 @@ extern "C" int impdar_fft_rows_dev(impdar_ctx *ctx, int mode, int dtype, int n, 
     if (rc) return rc;
     IMPDAR_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // (the table is this call's)
     return impdar_ctx_mark_produced(ctx);
+}
+
+extern "C" int impdar_fft_rows_dev(impdar_ctx *ctx, int mode, int dtype, int n, int batch, const void *d_in, void *d_out, double scale)
+{
+    return fft_rows_dev(ctx, false, mode, dtype, n, batch, d_in, d_out, scale);
+}
+
+extern "C" int impdar_fft_rows_any_dev(impdar_ctx *ctx, int mode, int dtype, int n, int batch, const void *d_in, void *d_out, double scale)
+{
+    return fft_rows_dev(ctx, true, mode, dtype, n, batch, d_in, d_out, scale);
 }
 
 template <typename T> struct Cx { T x, y; };
@@ -296,6 +313,7 @@ struct StoltPlan {
     FftPlan r2c, c2c_f, c2c_b, c2r;     // separate passes (IMPDAR_STOLT_FFT=1d)
     FftPlan fwd2d, inv2d;               // the same two pairs as 2-D real transforms (default)
     bool use2d = true, no_own = false;
+    int route = -1;                     // StoltRoute of the call the plans and buffers were made for
     DevBuf X, F, K, Y, d_kx, d_ws;
     DevBuf d_taper;                     // [tnum + snum] float64 taper weights (the transform over the traces taken first)
     std::vector<double> h_taper;        // ... on the host (alive until the next call: async copy), and what they were made from
@@ -327,6 +345,33 @@ void impdar_stolt_forget(const impdar_ctx *ctx)
     }
 }
 
+// Which transforms a call runs on.  Both forms of the own transforms need snum even.
+//   rows ("traces first", seven passes): R2C / C2R over the traces (complex length tnum / 2) and C2C of snum over time, on the
+//     wavenumbers k = 0 .. tnum / 2 alone, which holds the other half through kx[k] == -kx[tnum - k]; tnum >= 64
+//   [w][kx] (ten passes): R2C / C2R over time (complex length snum / 2), C2C of tnum over the traces; tnum may be odd
+// Power-of-two sizes keep the gate they had (the [w][kx] lengths decide, the rows form where snum fits too).  Any other size
+// takes the own transforms where the mixed-radix kernel has the lengths of a form (own_fft_mixed_plan.h), the rows form first --
+// by default only where rocFFT would compile kernels at run time (a length above 1024); IMPDAR_STOLT_FFT=mixed: wherever
+// the lengths allow.
+enum StoltRoute { STOLT_ROCFFT = 0, STOLT_OWN_WKX = 1, STOLT_OWN_ROWS = 2 };
+static inline bool stolt_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
+static StoltRoute stolt_route(int snum, int tnum, const double *kx, bool want_mixed)
+{
+    if (snum % 2) return STOLT_ROCFFT;
+    if (stolt_pow2(snum) && stolt_pow2(tnum)) {
+        if (!(own_fft_len_ok(snum / 2) && own_fft_len_ok(tnum))) return STOLT_ROCFFT;
+        return own_fft_len_ok(snum) && tnum >= 64 ? STOLT_OWN_ROWS : STOLT_OWN_WKX;
+    }
+    if (!(want_mixed || snum > 1024 || tnum > 1024)) return STOLT_ROCFFT;
+    auto len_ok = [](int M) { return own_fft_len_ok(M) || own_fft_mixed_len_ok(M); };
+    if (tnum % 2 == 0 && tnum >= 64 && len_ok(tnum / 2) && len_ok(snum)) {
+        bool antisym = true;
+        for (int k = 1; k < tnum / 2 && antisym; ++k) antisym = kx[k] == -kx[tnum - k];
+        if (antisym) return STOLT_OWN_ROWS;
+    }
+    return len_ok(snum / 2) && len_ok(tnum) ? STOLT_OWN_WKX : STOLT_ROCFFT;
+}
+
 template <typename T>
 static int stolt_run(impdar_ctx *ctx, StoltPlan &pl, const void *d_data, int snum, int tnum, const double *kx,
                      const double *ws, double vel, double htaper, double vtaper, void *d_out)
@@ -334,19 +379,23 @@ static int stolt_run(impdar_ctx *ctx, StoltPlan &pl, const void *d_data, int snu
     const int m = snum / 2 + 1, nz = snum / 2, nout = 2 * (snum / 2);
     hipStream_t st = ctx->stream;
     const bool dbl = sizeof(T) == 8;
-    bool want2d = true, no_own = false;
+    bool want2d = true, no_own = false, want_mixed = false;
     {
         // tuning knob: "1d" = four 1-D rocFFT passes; "rocfft" = rocFFT's 2-D real plans also where the own transforms apply;
-        // "own" = the default, spelled out (tests that pin one implementation)
+        // "own" = the default, spelled out (tests that pin one implementation); "mixed" = the own mixed-radix transforms at
+        // every size they take, not only where rocFFT has kernels to compile
         const char *e = getenv("IMPDAR_STOLT_FFT");
         want2d = !(e && !strcmp(e, "1d"));
         no_own = e && !strcmp(e, "rocfft");
+        want_mixed = e && !strcmp(e, "mixed");
     }
     // power-of-two sizes run on the library's own row transforms (own_fft.h), every call: 0.35 ms at 4096^2 against 0.37 on
     // rocFFT's 2-D plans (round 5: the stretch on the frequency-major spectrum, two transposes fewer), nothing compiled at
     // run time, no plan to make (rocFFT: 0.3-3 s per process for lengths above 1024)
-    const bool own_ok = want2d && !no_own && snum % 2 == 0 && own_fft_len_ok(snum / 2) && own_fft_len_ok(tnum);
-    if (pl.owner != ctx || pl.dtype != (dbl ? IMPDAR_F64 : IMPDAR_F32) || pl.snum != snum || pl.tnum != tnum || pl.use2d != want2d || pl.no_own != no_own) {
+    const StoltRoute route = want2d && !no_own ? stolt_route(snum, tnum, kx, want_mixed) : STOLT_ROCFFT;
+    const bool own_ok = route != STOLT_ROCFFT;
+    if (pl.owner != ctx || pl.dtype != (dbl ? IMPDAR_F64 : IMPDAR_F32) || pl.snum != snum || pl.tnum != tnum || pl.use2d != want2d || pl.no_own != no_own ||
+        pl.route != route) {
         pl.own_calls = 0;
         pl.plans_ready = false;
         pl.dtype = -1;
@@ -358,6 +407,7 @@ static int stolt_run(impdar_ctx *ctx, StoltPlan &pl, const void *d_data, int snu
         int rc;
         pl.use2d = want2d;
         pl.no_own = no_own;
+        pl.route = route;
         // rfft2(axes=(1,0)) (:159) = real transform over time (contiguous here), complex over the traces (rows);
         // irfft2 (:202) = complex inverse over the traces, then C2R over time.  rocFFT's 2-D real plans do
         // exactly these two passes each, with its own blocked column kernels instead of a strided batch.
@@ -422,7 +472,9 @@ static int stolt_run(impdar_ctx *ctx, StoltPlan &pl, const void *d_data, int snu
     // (both signs of the frequency: stolt_stretch_rows); C2C back over time; transpose -> [snum][hs]; C2R over x straight into the
     // output: seven passes instead of ten (no transposes of the real arrays at either end, two half-size transposes instead of two
     // whole ones)
-    const bool use_rows = use_own && own_fft_len_ok(snum) && tnum >= 64 && nout == snum;
+    const bool use_rows = route == STOLT_OWN_ROWS;
+    // (the metrics line says when a transform of the call ran on the mixed-radix kernel)
+    const bool mixed = use_own && !(stolt_pow2(snum) && stolt_pow2(tnum));
     if (use_rows && do_taper && !(pl.h_taper.size() == (size_t)tnum + snum && pl.taper_h == htaper && pl.taper_v == vtaper && pl.d_taper.p)) {
         std::vector<double> &taps = pl.h_taper;
         taps.resize((size_t)tnum + snum);
@@ -448,7 +500,8 @@ static int stolt_run(impdar_ctx *ctx, StoltPlan &pl, const void *d_data, int snu
         IMPDAR_HIP_CHECK(hipGetLastError());
         impdar_trace("stolt: all kernels enqueued (traces first)");
         ctx->m_entry = "impdar_stolt";
-        ctx->m_kernel = "stolt_stretch_rows (+ the library's own row transforms, traces first)";
+        ctx->m_kernel = mixed ? "stolt_stretch_rows (+ the library's own row transforms, traces first, mixed radix)"
+                              : "stolt_stretch_rows (+ the library's own row transforms, traces first)";
         ctx->m_kernel_ms = -1.f;
         ctx->ktimed = false;
         ctx->m_extra[0] = 0;
@@ -492,7 +545,8 @@ static int stolt_run(impdar_ctx *ctx, StoltPlan &pl, const void *d_data, int snu
     IMPDAR_HIP_CHECK(hipGetLastError());
     impdar_trace("stolt: all kernels enqueued");
     ctx->m_entry = "impdar_stolt";
-    ctx->m_kernel = use_own ? "stolt_stretch (+ the library's own row transforms)" : "stolt_stretch (+ rocFFT 2-D real transforms)";
+    ctx->m_kernel = use_own ? (mixed ? "stolt_stretch (+ the library's own row transforms, mixed radix)" : "stolt_stretch (+ the library's own row transforms)")
+                            : "stolt_stretch (+ rocFFT 2-D real transforms)";
     ctx->m_kernel_ms = -1.f;
     ctx->ktimed = false;
     ctx->m_extra[0] = 0;

@@ -175,7 +175,11 @@ long long impdar_kirch_count_pairs(const impdar_kirch_plan *plan, int xlo, int x
  * data (snum,tnum) of dtype already tapered-cast by the caller? NO: the taper
  * (mig_python.py:152-157) runs on the device.  kx has tnum entries, ws has
  * snum/2+1 entries (host shim restates :161-168).  out has 2*(snum/2) rows,
- * same dtype as data. */
+ * same dtype as data.
+ * Sizes with a length above 1024 whose lengths have no prime factor above 7 run on the library's own row transforms
+ * (IMPDAR_STOLT_FFT=mixed: every such size).  Their "traces first" form keeps the wavenumbers k = 0 .. tnum/2 alone and
+ * therefore needs kx[k] == -kx[tnum - k] exactly for 1 <= k < tnum/2 -- what 2 pi fftfreq(tnum, dx) gives; the host checks
+ * it at sizes that are no power of two, and any other kx takes the form that keeps all wavenumbers (or rocFFT). */
 int impdar_stolt(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum,
                  const double *kx, const double *ws, double vel, double htaper,
                  double vtaper, void *out);
@@ -195,6 +199,10 @@ int impdar_stolt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, i
  * mode 4: complex inverse, real parts only -- d_in [batch][n] complex, d_out [batch][n] real (mig_python.py:282).
  * n a power of two; complex length (n, or n/2 for the real modes) 16 .. 8192.  dtype IMPDAR_F32 / IMPDAR_F64. */
 int impdar_fft_rows_dev(impdar_ctx *ctx, int mode, int dtype, int n, int batch, const void *d_in, void *d_out, double scale);
+/* The same at any length whose complex length (n, or n/2 for the real modes; a real n must be even) is 16 .. 8192 with
+ * no prime factor above 7: a power of two runs as above, any other such length on the mixed-radix kernel
+ * (csrc/own_fft_mixed.h) -- 10000 traces are real rows of 5000 complex numbers. */
+int impdar_fft_rows_any_dev(impdar_ctx *ctx, int mode, int dtype, int n, int batch, const void *d_in, void *d_out, double scale);
 
 /* ---- phase shift / Gazdag (mig_python.py:211-287, :361-493) ------------
  * vmig_len == 0: constant velocity `vconst`; vmig_len == snum: 1-D v(z).
