@@ -28,6 +28,7 @@
 #include <cmath>
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <thread>
 
 
@@ -565,14 +566,6 @@ struct TableQParams {
     int ps;                         // bytes per 32-row piece of the LDS image (kq_piece_bytes)
 };
 
-// Row stride of the step-block pick table in 16-byte entries.  Not snum: with snum a power of two a chunk's
-// slice of consecutive rows (256 entries out of every snum) lands on 1/16 of the L2's sets (and of whatever else
-// indexes by address bits); the odd number of 256-byte lines of padding walks the slice over all of them.
-#ifndef KQ_TKB_PAD
-#define KQ_TKB_PAD 272       // entries (4352 bytes)
-#endif
-__host__ __device__ static inline size_t kq_tkb_stride(int snum) { return (size_t)snum + KQ_TKB_PAD; }
-
 // byte offset of half 0 of ring row r in the quad kernel's LDS image (layout: see kirch_quad_kernel)
 __host__ __device__ static inline unsigned kq_row_offset(int r, int ps)
 {
@@ -807,30 +800,7 @@ __global__ __launch_bounds__(KF_THREADS, OCC) void kirch_tab_kernel(FastParams P
 // The DMA keeps the image linear and applies the swap on its per-lane SOURCE address; the pick table
 // holds the byte offset of half 0 of the picked row, half 1 is that offset ^ 16.
 // ---------------------------------------------------------------------------
-#define KQ_GS 1056          // bytes between the trace groups inside a piece (32 rows x 32 B + spare row)
 #define KQ_ZERO 1024        // byte offset of the all-zero row (spare row of piece 0, group 0; + g * KQ_GS)
-// ring slots for an XB-trace output tile (XB + 15 traces are live, in whole 8-trace groups) and bytes per
-// 32-row piece: the groups + pad to a multiple of 256 B (rows of neighbouring pieces then keep distinct
-// banks inside one ds_read_b128 lane group)
-__host__ __device__ constexpr int kq_ring_slots(int xb) { return ((xb + 15 + 7) / 8) * 8; }
-__host__ __device__ constexpr int kq_piece_bytes(int xb) { return ((kq_ring_slots(xb) / 8 * KQ_GS + 255) / 256) * 256; }
-// ... and with LK extra ring groups (deeper staging lookahead, see kirch_quad_kernel)
-__host__ __device__ constexpr int kq_piece_bytes_lk(int xb, int lk) { return (((kq_ring_slots(xb) / 8 + lk) * KQ_GS + 255) / 256) * 256; }
-static_assert(kq_piece_bytes_lk(40, 0) == 7424 && kq_piece_bytes_lk(40, 1) == 8448 && kq_piece_bytes_lk(24, 0) == 5376, "");
-static_assert(kq_ring_slots(24) == 40 && kq_piece_bytes(24) == 5376 && kq_ring_slots(32) == 48 && kq_piece_bytes(32) == 6400 &&
-              kq_ring_slots(40) == 56 && kq_piece_bytes(40) == 7424, "");
-#ifndef KQ_DEFAULT_NH
-#define KQ_DEFAULT_NH 1     // output tiles per workgroup of the quad kernel (IMPDAR_KIRCH_NH overrides)
-#endif
-#ifndef KD_DEFAULT_NH
-#define KD_DEFAULT_NH 1     // the same for the float64 ring kernel (IMPDAR_KIRCH_NHD), with tiles of KD_DEFAULT_XB2 traces
-#endif
-#ifndef KD_DEFAULT_XB2
-#define KD_DEFAULT_XB2 16
-#endif
-#ifndef KQ_DEFAULT_LK
-#define KQ_DEFAULT_LK 0     // extra ring groups / blocks of staging lookahead with NH >= 2 (IMPDAR_KIRCH_LK overrides)
-#endif
 #ifndef KQ_PER
 #define KQ_PER 4            // quads per interleave slice (1..7 all measure within 2 %; 4 keeps 97 VGPRs)
 #endif
@@ -1297,9 +1267,6 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
 // The kernel is bound by the float64 vector rate (20 v_fma_f64 + ~10 for the weight per lane and step against
 // 11 ds_read_b128), not by the LDS port.
 // ---------------------------------------------------------------------------
-__host__ __device__ constexpr int kd_ring_slots(int xb) { return ((xb + 7 + 3) / 4) * 4; }     // XB + 2 S - 1 live traces, whole groups
-__host__ __device__ constexpr int kd_piece_bytes(int xb) { return ((kd_ring_slots(xb) / 4 * KQ_GS + 255) / 256) * 256; }
-static_assert(kd_ring_slots(20) == 28 && kd_piece_bytes(20) == 7424 && kd_ring_slots(16) == 24 && kd_piece_bytes(16) == 6400, "");
 typedef double kd_d2 __attribute__((ext_vector_type(2)));
 
 // picks for the dquad kernel: rows of FOUR offsets, n = 4 (r - mrow0) + 1 + s, 16 bits each (see kirch_tableq_kernel)
@@ -1668,15 +1635,202 @@ __global__ __launch_bounds__(256) void kirch_combine_kernel(const T *__restrict_
 // ===========================================================================
 // host side
 // ===========================================================================
-// set by mig_kirch_loop around its plan creation: the time limit t > t_max drops a pair at (mig_python.py:52) is the
-// caller's argument there, not max(tt)
-static thread_local const double *g_tmax_override = nullptr;
+// What is decided on the host -- the analysis of the axes, the choice of kernel, the host tables -- is kirch_route.h: pure
+// code, tested without a device.  Here: the stages that allocate and upload for it, and the launches.
 
-extern "C" int impdar_kirch_plan_create(impdar_ctx *ctx, int dtype, int snum, int tnum,
-                                        const double *dist_m, const double *tt_sec, double vel,
-                                        int nearfield, int grad_uniform, double grad_h,
-                                        const double *ga, const double *gb, const double *gc,
-                                        int mode, int nranks, impdar_kirch_plan **out)
+// the axes every table / per-pair parameter struct carries
+template <typename P>
+static void kirch_fill_axes(P &T, const impdar_kirch_plan *p)
+{
+    T.zs = p->d_zs.as<double>();
+    T.zs2 = p->d_zs2.as<double>();
+    T.tt = p->d_tt.as<double>();
+    T.vel = p->vel;
+    T.tmax = p->tmax;
+    T.inv_dt = 1.0 / p->dt;
+    T.tt0 = p->tt0;
+    T.snum = p->snum;
+}
+
+// ... and the images and the output block of the global-memory kernels' structs
+template <typename P>
+static void kirch_fill_io(P &T, const impdar_kirch_plan *p, void *d_out, int xlo, int xhi)
+{
+    T.GT = img_row0(p, p->GT[p->buf]);
+    T.DT = p->nearfield ? img_row0(p, p->DT[p->buf]) : nullptr;
+    T.out = d_out;
+    T.ldo = xhi - xlo;
+    T.snum = p->snum;
+    T.tnum = p->tnum;
+    T.xlo = xlo;
+    T.xhi = xhi;
+}
+
+static int kirch_alloc_images(impdar_kirch_plan *p)
+{
+    const size_t img = (size_t)(p->tnum_pad + 2 * KF_PAD_ROWS) * p->snum * impdar_dtype_size(p->dtype);   // zero rows on both sides
+    for (int b = 0; b < 2; ++b) {
+        if (p->GT[b].ensure(img) != hipSuccess || (p->nearfield && p->DT[b].ensure(img) != hipSuccess)) {
+            impdar_set_error("hipMalloc of %zu-byte image failed", img);
+            return IMPDAR_ERR_HIP;
+        }
+        (void)hipMemsetAsync(p->GT[b].p, 0, img, p->ctx->stream);
+        if (p->nearfield) (void)hipMemsetAsync(p->DT[b].p, 0, img, p->ctx->stream);
+    }
+    (void)hipStreamSynchronize(p->ctx->stream);
+    return IMPDAR_OK;
+}
+
+// the gradient coefficients, dist, tt and the depth tables zs = v t / 2, zs^2 (mig_python.py:101-102) or the caller's own
+static int kirch_upload_axes(impdar_kirch_plan *p, const double *dist_m, const double *tt_sec, const double *ga, const double *gb,
+                             const double *gc, const double *zs_own, const double *zs2_own)
+{
+    const int snum = p->snum, tnum = p->tnum;
+    int rc;
+    if (!p->grad_uniform) {
+        if ((rc = upload(p->d_ga, ga, snum * 8)) || (rc = upload(p->d_gb, gb, snum * 8)) || (rc = upload(p->d_gc, gc, snum * 8)))
+            return rc;
+    }
+    std::vector<double> zs(snum), zs2(snum);
+    for (int k = 0; k < snum; ++k) {
+        zs[k] = p->vel * tt_sec[k] / 2.0;
+        zs2[k] = zs[k] * zs[k];
+    }
+    std::vector<double> dpad(dist_m, dist_m + tnum);
+    dpad.resize((size_t)tnum + 64, dist_m[tnum - 1]);      // kirch_gen_kernel reads up to 31 entries past a tile's end
+    if ((rc = upload(p->d_dist, dpad.data(), dpad.size() * 8)) || (rc = upload(p->d_tt, tt_sec, (size_t)snum * 8)) ||
+        (rc = upload(p->d_zs, zs_own ? zs_own : zs.data(), (size_t)snum * 8)) ||
+        (rc = upload(p->d_zs2, zs2_own ? zs2_own : zs2.data(), (size_t)snum * 8)))
+        return rc;
+    if (p->uniform) p->h_half = kirch_half_widths(*p, tt_sec, snum);
+    return IMPDAR_OK;
+}
+
+// the picks that rounding noise decides (kirch_tiescan_kernel), and what their number does to the route
+static int kirch_tie_scan(impdar_kirch_plan *p)
+{
+    constexpr int TIE_CAP = 1 << 20;
+    static_assert(sizeof(KirchTie) == sizeof(int2), "the tie list is downloaded as it lies");
+    hipStream_t st = p->ctx->stream;
+    int hg = 0, rc;
+    for (int k = 0; k < p->snum; ++k) hg = std::max(hg, p->h_half[k] + 1);
+    hg = std::min(hg, p->tnum) + 1;
+    DevBuf d_flag, d_list;
+    if (d_flag.ensure(64) != hipSuccess || d_list.ensure((size_t)TIE_CAP * sizeof(int2)) != hipSuccess) {
+        impdar_set_error("hipMalloc failed");
+        return IMPDAR_ERR_HIP;
+    }
+    (void)hipMemsetAsync(d_flag.p, 0, 64, st);
+    TableXParams T;
+    T.XK = nullptr;
+    T.XW = T.XW2 = nullptr;
+    kirch_fill_axes(T, p);
+    T.dx = p->dx;
+    T.ntab = hg;
+    T.near = 0;
+    hipLaunchKernelGGL(kirch_tiescan_kernel, dim3((p->snum + 255) / 256, hg), dim3(256), 0, st, T, p->xnoise, d_flag.as<int>(),
+                       d_list.as<int2>(), TIE_CAP);
+    int count = 0;
+    if (hipMemcpyAsync(&count, d_flag.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        impdar_set_error("tie scan failed: %s", hipGetErrorString(hipGetLastError()));
+        return IMPDAR_ERR_HIP;
+    }
+    kirch_route_after_ties(*p, count, TIE_CAP);
+    if (!p->want_tie_groups) return IMPDAR_OK;
+    std::vector<KirchTie> list(count);
+    if (hipMemcpy(list.data(), d_list.p, (size_t)count * sizeof(int2), hipMemcpyDeviceToHost) != hipSuccess) {
+        impdar_set_error("tie list download failed");
+        return IMPDAR_ERR_HIP;
+    }
+    const KirchTieGroups G = kirch_group_ties(list);
+    p->ntie_groups = (int)G.g_ti.size();
+    if ((rc = upload(p->d_tie_ti, G.g_ti.data(), G.g_ti.size() * 4)) || (rc = upload(p->d_tie_off, G.g_off.data(), G.g_off.size() * 4)) ||
+        (rc = upload(p->d_tie_n, G.g_n.data(), G.g_n.size() * 4)))
+        return rc;
+    return IMPDAR_OK;
+}
+
+static int kirch_upload_gen_tables(impdar_kirch_plan *p, const double *dist_m, const double *tt_sec)
+{
+    KirchGenTables T = kirch_gen_tables(*p, tt_sec, p->snum, p->vel, p->genW);
+    p->nchunks = (int)T.alo2.size();
+    p->h_zs2min.swap(T.zs2min);
+    p->h_dist.assign(dist_m, dist_m + p->tnum);
+    int rc;
+    if ((rc = upload(p->d_ga32, T.a.data(), p->snum * 4)) || (rc = upload(p->d_ga2_32, T.a2.data(), p->snum * 4)) ||
+        (rc = upload(p->d_alo2, T.alo2.data(), p->nchunks * 4)))
+        return rc;
+    return IMPDAR_OK;
+}
+
+// the per-sample factors, the pick table's allocation and the staging windows of quad / dquad / tab
+static int kirch_upload_ring_tables(impdar_kirch_plan *p, const double *tt_sec)
+{
+    const int snum = p->snum;
+    const bool ring = p->quad || p->dquad;
+    int rc;
+    if (p->dquad) {
+        const KirchFactors<double> F = kirch_factors<double>(*p, tt_sec, snum, p->vel);
+        if ((rc = upload(p->d_c1d, F.c1.data(), snum * 8)) || (rc = upload(p->d_c2d, F.c2.data(), snum * 8)) ||
+            (rc = upload(p->d_find, F.fin.data(), snum * 8)))
+            return rc;
+    } else {
+        const KirchFactors<float> F = kirch_factors<float>(*p, tt_sec, snum, p->vel);
+        if ((rc = upload(p->d_c1, F.c1.data(), snum * 4)) || (rc = upload(p->d_c2, F.c2.data(), snum * 4)) ||
+            (rc = upload(p->d_fin, F.fin.data(), snum * 4)))
+            return rc;
+    }
+    KirchRingTables T = kirch_ring_tables(*p, *p, tt_sec, snum, p->tnum, p->h_half);
+    p->nchunks = T.nchunks;
+    p->nb = T.nb;
+    p->ntab = T.ntab;
+    p->mrow0 = T.mrow0;
+    p->nrows = T.nrows;
+    if (T.tkbytes >= ((size_t)1 << 31)) {      // the kernels address it as one raw buffer
+        impdar_set_error("fast Kirchhoff pick table of %zu bytes exceeds 2 GiB; use the exact mode", T.tkbytes);
+        return IMPDAR_ERR_UNSUPPORTED;
+    }
+    const size_t ent = (size_t)p->ntab * snum;
+    bool ok = true;
+    for (int b = 0; b < 2; ++b) {
+        ok = ok && p->d_TK[b].ensure(T.tkbytes) == hipSuccess;
+        if (!ring) ok = ok && p->d_TW[b].ensure(ent * 4) == hipSuccess;
+        if (!ring && p->nearfield) ok = ok && p->d_TW2[b].ensure(ent * 4) == hipSuccess;
+    }
+    if (!ok) {
+        impdar_set_error("hipMalloc of the %zu-byte pick table failed", T.tkbytes);
+        return IMPDAR_ERR_HIP;
+    }
+    if (ring && (rc = upload(p->d_WIN, T.win.data(), T.win.size() * 4))) return rc;
+    if ((rc = upload(p->d_hmax, T.hmax.data(), T.nchunks * 4)) || (rc = upload(p->d_klo, T.klo.data(), T.klo.size() * 4)) ||
+        (rc = upload(p->d_khi, T.khi.data(), T.khi.size() * 4)))
+        return rc;
+    p->h_hmax.swap(T.hmax);
+    return IMPDAR_OK;
+}
+
+static int kirch_create_events(impdar_kirch_plan *p)
+{
+    bool ok = true;
+    for (int s = 0; s < impdar_kirch_plan::NSLOT; ++s)
+        for (int i = 0; i < 6; ++i) ok = ok && hipEventCreate(&p->evs[s][i]) == hipSuccess;
+    for (hipEvent_t *e : {&p->ev_ready[0], &p->ev_ready[1], &p->ev_free[0], &p->ev_free[1]})
+        ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (!ok) impdar_set_error("hipEventCreate failed");
+    return ok ? IMPDAR_OK : IMPDAR_ERR_HIP;
+}
+
+// What mig_kirch_loop hands over with its call: the time limit t > t_max drops a pair at (mig_python.py:52) is the caller's
+// argument there, not max(tt); `standard`: the depth tables are what the plan computes itself, bit for bit.
+struct KirchCallerTables {
+    double tmax;
+    const double *zs, *zs2;
+    bool standard;
+};
+
+static int kirch_plan_create_impl(impdar_ctx *ctx, int dtype, int snum, int tnum, const double *dist_m, const double *tt_sec, double vel,
+                                  int nearfield, int grad_uniform, double grad_h, const double *ga, const double *gb, const double *gc,
+                                  int mode, int nranks, const KirchKnobs &knobs, const KirchCallerTables *caller, impdar_kirch_plan **out)
 {
     IMPDAR_ARG_CHECK(ctx && out, "null context/plan pointer");
     IMPDAR_ARG_CHECK(dtype == IMPDAR_F32 || dtype == IMPDAR_F64, "dtype must be 0 (f32) or 1 (f64)");
@@ -1686,514 +1840,57 @@ extern "C" int impdar_kirch_plan_create(impdar_ctx *ctx, int dtype, int snum, in
     IMPDAR_ARG_CHECK(nranks >= 1, "nranks must be >= 1");
     IMPDAR_ARG_CHECK(grad_uniform || (ga && gb && gc), "non-uniform gradient needs ga/gb/gc");
 
-    // (the geometry analysis and the kernel choice below are pure host code and run before the first HIP call,
-    // so their argument errors do not need a device: tests/test_sanitizer.py drives them under ASan/UBSan)
-    impdar_kirch_plan *p = new impdar_kirch_plan();
+    // (the geometry analysis and the kernel choice are pure host code and run before the first HIP call, so their
+    // argument errors do not need a device: tests/test_sanitizer.py drives them under ASan/UBSan)
+    const KirchGeometry G = kirch_geometry(snum, tnum, dist_m, tt_sec, vel, caller ? &caller->tmax : nullptr);
+    IMPDAR_ARG_CHECK(G.increasing, "travel_time must be strictly increasing");
+    const KirchRoute R = kirch_route(G, dtype, snum, tnum, nranks, nearfield, mode, knobs, caller && !caller->standard);
+    if (R.status != IMPDAR_OK) {
+        impdar_set_error("the float32 Kirchhoff kernels need float32 data on a uniform travel_time axis and either a "
+                         "uniform dist with moveout 2dx/(v dt) <= %.1f samples per trace (got %.2f) or a sorted dist "
+                         "whose 32-trace windows span <= 760 samples of moveout",
+                         R.err_limit, R.err_sa);
+        return R.status;
+    }
+    std::unique_ptr<impdar_kirch_plan> p(new impdar_kirch_plan());
+    static_cast<KirchGeometry &>(*p) = G;
+    static_cast<KirchRoute &>(*p) = R;
+    p->knobs = knobs;
     p->ctx = ctx;
     p->dtype = dtype;
     p->snum = snum;
     p->tnum = tnum;
     p->nranks = nranks;
-    // equal input shards of whole 8-row groups (the grouped image layout keeps a shard contiguous)
-    p->tnum_pad = ((tnum + 8 * nranks - 1) / (8 * nranks)) * 8 * nranks;
     p->nearfield = nearfield ? 1 : 0;
     p->grad_uniform = grad_uniform;
     p->grad_h = grad_h;
     p->vel = vel;
 
-    // ---- geometry analysis ------------------------------------------------
-    double tmax = tt_sec[0];
-    bool increasing = true;
-    for (int k = 1; k < snum; ++k) {
-        tmax = std::max(tmax, tt_sec[k]);
-        if (!(tt_sec[k] > tt_sec[k - 1])) increasing = false;
-    }
-    if (g_tmax_override) tmax = *g_tmax_override;      // mig_kirch_loop: the caller's own time limit (see there)
-    p->tmax = tmax;
-    if (!increasing) {
-        delete p;
-        impdar_set_error("travel_time must be strictly increasing");
-        return IMPDAR_ERR_ARG;
-    }
-    const double dt = (tt_sec[snum - 1] - tt_sec[0]) / (snum - 1);
-    bool uni_t = dt > 0;
-    for (int k = 0; k < snum && uni_t; ++k)
-        if (std::fabs(tt_sec[k] - (tt_sec[0] + k * dt)) > 1e-9 * dt) uni_t = false;
-    double dx = 1.0;
-    bool uni_x = true;
-    if (tnum >= 2) {
-        dx = (dist_m[tnum - 1] - dist_m[0]) / (tnum - 1);
-        uni_x = dx > 0;
-        for (int j = 0; j < tnum && uni_x; ++j)
-            if (std::fabs(dist_m[j] - (dist_m[0] + j * dx)) > 1e-9 * dx) uni_x = false;
-    }
-    p->dist_sorted = true;
-    for (int j = 1; j < tnum; ++j)
-        if (!(dist_m[j] >= dist_m[j - 1])) p->dist_sorted = false;
-    // position noise of a pair's dist[j] - dist[xi] against n * dx, in units of dx, measured on the profile: twice the
-    // largest deviation from the fitted grid plus the rounding of the largest |dist| (never less than 4.5e-16 tnum)
-    {
-        double dev = 0.0, amax = 0.0;
-        for (int j = 0; j < tnum; ++j) {
-            dev = std::max(dev, std::fabs(dist_m[j] - (dist_m[0] + j * dx)));
-            amax = std::max(amax, std::fabs(dist_m[j]));
-        }
-        p->xnoise = std::max(4.5e-16 * (double)tnum, (2.0 * dev + 4.5e-16 * amax) / (dx > 0 ? dx : 1.0));
-    }
-    p->dt = dt;
-    p->dx = dx;
-    p->tt0 = tt_sec[0];
-    p->uniform = uni_t && uni_x;
-    const double sa = 2.0 * dx / (vel * dt);       // samples of moveout per trace at far offset
-    p->alpha = sa * sa;
-    // fast kernels need the moveout 2dx/(v dt) (samples per trace) small enough for their
-    // LDS windows: quad (sample-major ring, 24 traces x 8-step blocks, up to ~6.7 samples/trace)
-    // or, for steeper moveout, tab (trace-major ring of 16 traces, 512-sample slots)
-    // quad kernel's output-trace tile: 24 traces (40-slot ring, three workgroups per CU) or 40 traces
-    // (56-slot ring, two workgroups per CU).  The wider tile stages and picks 40 % less per pair and is
-    // 2.5-5 % faster on a whole radargram (same-box A/B at config 3; 32 traces: 1.3 %); with the short
-    // launches of a many-rank run (under ~2000 output traces per rank) its fewer, longer workgroups
-    // balance worse (-7 % at 8 ranks), so those keep 24.  IMPDAR_KIRCH_XB = 24 / 32 / 40 overrides.
-    int xbq = 24;
-    {
-        auto rows_for = [&](int xb) { return ((KF_THREADS + (int)std::ceil(sa * (xb + 8 - 2)) + 8 + 31) / 32) * 32; };
-        const char *xe = getenv("IMPDAR_KIRCH_XB");
-        if (xe && (atoi(xe) == 24 || atoi(xe) == 32 || atoi(xe) == 40))
-            xbq = atoi(xe);
-        else if ((size_t)(rows_for(40) / 32) * kq_piece_bytes(40) <= 80 * 1024)
-            xbq = 40;       // (round 1 kept 24 for the short launches of a many-rank run; with the balanced tile map and
-                            // the work queues 40 is ahead there too: 1.31 vs 1.41 ms for an 8-rank block of config 3)
-    }
-    // Whole radargrams by default: TWO tiles of 32 traces per workgroup on one ring (kirch_quad_kernel, NH = 2),
-    // when that ring fits half a CU's LDS: two workgroups of 8 waves per CU (four waves per SIMD at 128 VGPRs)
-    // instead of two of 4.  Same-box A/B at config 3: 2 % faster than one 40-trace tile per workgroup (the same
-    // tile pair with one workgroup per CU, 40 x 2, is 1 % slower), and the fabric traffic roughly halves.
-    bool pair32 = false;
-    // (a rank's block of under ~8000 traces gives the 64-trace workgroup tiles too few items per slot: 40 x 1 there;
-    // emulated per-rank steps at config 3, profiles/r02_rank_steps_tiles.txt: 4.28 / 2.32 / 1.31 ms at 2 / 4 / 8 ranks
-    // against 4.33 / 2.39 / 1.65 with the tile pair)
-    if (!getenv("IMPDAR_KIRCH_XB") && !getenv("IMPDAR_KIRCH_NH") && !nearfield && xbq == 40 &&
-        (long long)tnum >= 8000LL * nranks) {
-        const int rows = ((KF_THREADS + (int)std::ceil(sa * (32 * 2 + 8 - 2)) + 8 + 31) / 32) * 32;
-        if ((size_t)(rows / 32) * kq_piece_bytes(32) <= 80 * 1024 && (size_t)(rows / 32) * kq_piece_bytes(32) > 65535) {
-            pair32 = true;
-            xbq = 32;
-        }
-    }
-    int kq_ps = kq_piece_bytes(xbq);
-    // tiles per workgroup on one ring (see kirch_quad_kernel, NH): the staging window grows by the moveout over
-    // the (nh - 1) xb traces the later tiles lag behind; one workgroup per CU then (up to the whole 160 KB)
-    int nhq = 1;
-    {
-        const char *ne = getenv("IMPDAR_KIRCH_NH");         // tuning knob: 1 | 2 | 3
-        const int want = ne ? atoi(ne) : (pair32 ? 2 : KQ_DEFAULT_NH);
-        auto rows_nh = [&](int nh) { return ((KF_THREADS + (int)std::ceil(sa * (xbq * nh + 8 - 2)) + 8 + 31) / 32) * 32; };
-        if ((want == 2 || want == 3) && (xbq == 40 || (xbq == 32 && want == 2)) && !nearfield &&
-            (ne || pair32) &&
-            (size_t)(rows_nh(want) / 32) * kq_ps <= 160 * 1024 && (size_t)(rows_nh(want) / 32) * kq_ps > 65535)
-            nhq = want;
-    }
-    p->nh = nhq;
-    int lkq = 0;
-    {
-        const char *le = getenv("IMPDAR_KIRCH_LK");         // tuning knob: 0 | 1
-        const int want = le ? atoi(le) : KQ_DEFAULT_LK;
-        const int rows = ((KF_THREADS + (int)std::ceil(sa * (xbq * nhq + 8 - 2)) + 8 + 31) / 32) * 32;
-        // every wave must own at least one DMA piece per block (the in-order wait counts on it)
-        if (want == 1 && nhq >= 2 && rows / 32 >= 4 * nhq && (size_t)(rows / 32) * kq_piece_bytes_lk(xbq, 1) <= 160 * 1024)
-            lkq = 1;
-    }
-    p->lk = lkq;
-    kq_ps = kq_piece_bytes_lk(xbq, lkq);
-    const int wq = ((KF_THREADS + (int)std::ceil(sa * (xbq * nhq + 8 - 2)) + 8 + 31) / 32) * 32;   // whole 32-row pieces
-    // (two workgroups per CU: 80 KB of LDS each; table entries are 16-bit byte offsets up to 12 pieces,
-    // 16-byte units beyond)
-    const bool quad_ok = (size_t)(wq / 32) * kq_ps <= (nhq > 1 ? 160 : 80) * 1024;
-    const bool tab_ok = (KF_THREADS + sa * (16 - 1) + 8.0) <= (double)KF_W;
-    const bool window_ok = quad_ok || tab_ok;
-    // aperture half width in traces (upper bound): below 65536 (the kernel squares trace offsets in 32
-    // bits), and the span of image groups one workgroup walks must stay inside its 2 GiB raw buffer
-    const double hest = std::min(std::fabs(tmax / dt) / sa + 2.0, (double)tnum + 128.0);
-    const bool span_ok = (2.0 * hest + 400.0) / 8.0 * (double)snum * 32.0 < 2147483648.0;
-    const bool fast_ok = dtype == IMPDAR_F32 && p->uniform && window_ok && snum < 65536 &&
-                         std::fabs(tmax / dt) / sa < 65000.0 && span_ok;
-
-    // float32 data on a profile whose spacing is NOT uniform (mig_python.py:44 takes any dist[]): kirch_gen_kernel
-    // computes every pair's pick from the positions.  It needs a uniform time axis, a sorted dist[] (the staging windows
-    // and the input range of a tile come from bisections) and, per 32 consecutive output traces, a moveout that fits
-    // its LDS slots: W >= 264 + (extent of the 32 traces in samples).  IMPDAR_KIRCH_IMPL=gen takes it on uniform
-    // profiles too (A/B against the ring kernels).
-    int gen_w = 0;
-    bool gen_ok = false;
-    bool uni_t11 = uni_t;          // the float64 re-decision of a pick takes tt[k] = tt[0] + k dt: to 1e-11 dt here
-    for (int k = 0; k < snum && uni_t11; ++k)
-        if (std::fabs(tt_sec[k] - (tt_sec[0] + k * dt)) > 1e-11 * dt) uni_t11 = false;
-    if (dtype == IMPDAR_F32 && uni_t11 && p->dist_sorted && tnum >= 2 && snum >= 4 && snum < (1 << 22) && !g_tmax_override &&
-        (double)tnum * snum * 4.0 < 2147483648.0) {
-        double ext = 0.0;
-        for (int j = 0; j < tnum; ++j) ext = std::max(ext, dist_m[std::min(j + 31, tnum - 1)] - dist_m[j]);
-        const double need = 264.0 + std::ceil(ext * 2.0 / (vel * dt));
-        if (need <= 1024.0) {
-            gen_w = ((int)need + 255) / 256 * 256;
-            if (gen_w < 512) gen_w = 512;
-            gen_ok = true;
-        }
-    }
-    const char *impl_env = getenv("IMPDAR_KIRCH_IMPL");
-    const bool gen_forced = gen_ok && impl_env && !strcmp(impl_env, "gen") && mode != IMPDAR_KIRCH_EXACT;
-    const int requested_mode = mode;
-    const bool gen = gen_forced || (gen_ok && !fast_ok && mode != IMPDAR_KIRCH_EXACT);
-    if (mode == IMPDAR_KIRCH_AUTO) mode = (fast_ok || gen) ? IMPDAR_KIRCH_FAST : IMPDAR_KIRCH_EXACT;
-    if (mode == IMPDAR_KIRCH_FAST && !fast_ok && !gen) {
-        delete p;
-        impdar_set_error("the float32 Kirchhoff kernels need float32 data on a uniform travel_time axis and either a "
-                         "uniform dist with moveout 2dx/(v dt) <= %.1f samples per trace (got %.2f) or a sorted dist "
-                         "whose 32-trace windows span <= 760 samples of moveout",
-                         (KF_W - KF_THREADS - 8.0) / 15.0, sa);
-        return IMPDAR_ERR_UNSUPPORTED;
-    }
-    p->mode = mode;
-    p->gen = gen && mode == IMPDAR_KIRCH_FAST;
-    p->genW = gen_w;
-    {
-        // One full-aperture walk of a shallow chunk takes ~1.2 ms at config 3 -- as long as the whole step of a rank of
-        // an 8-GPU run should be, and such a rank's block has fewer items than the chip has workgroup slots.  Plans
-        // of 4+ ranks cut every walk in 2, of 8+ ranks in 4 pieces (kirch_quad_kernel); the pieces are summed in a
-        // fixed order, so launches stay bit-reproducible (against whole walks the sum differs by rounding).
-        const char *pe = getenv("IMPDAR_KIRCH_PARTS");      // tuning knob: 1 | 2 | 4
-        const int parts = pe ? atoi(pe) : (nranks >= 8 ? 4 : (nranks >= 4 ? 2 : 1));
-        p->walk_parts_log2 = parts == 4 ? 2 : (parts == 2 ? 1 : 0);
-    }
-    {
-        const char *ie = getenv("IMPDAR_KIRCH_IMPL");       // tuning knob: "tab" forces the b32 ring
-        p->quadW = wq;
-        p->quadSH = ((size_t)(wq / 32) * kq_ps <= 65535) ? 0 : 4;
-        p->quad = (mode == IMPDAR_KIRCH_FAST) && !p->gen && quad_ok && !(ie && !strcmp(ie, "tab") && tab_ok);
-        p->xb = p->gen ? 32 : (p->quad ? xbq : 16);
-    }
-    // float64 data in exact mode on uniform grids: the same ring in float64 (20 or 16 output traces per lane,
-    // step blocks of 4) when its window fits; otherwise (and for IMPDAR_KIRCH_EXACT_IMPL = tab | pair) the
-    // global-memory kernels
-    // The table-driven float64 kernels weight a pair by its trace OFFSET (n dx); the reference by dist[j] - dist[xi].
-    // On a profile whose positions are noisy against the grid (a first trace tens of kilometres along the line:
-    // ulp(dist) / dx ~ 1e-10; 100000 traces from 0: 4.5e-11) the two weights differ by that much relative, and the
-    // result differs from the reference's by up to ~0.03 xnoise of the image maximum (measured 2.5e-12 at 1e-10 with
-    // the near-field term).  Rounds 2-3 sent every profile with xnoise > 3e-11 to the per-pair kernel to hold a flat
-    // 1e-12 -- 45-100x slower on ordinary long traverses.  The ring (and the tabulated kernel) now stay; the stated bar
-    // of the float64 path is  max(1e-12, 0.1 xnoise)  of the image maximum (impdar_kirch_plan_xnoise reports xnoise;
-    // picks are not affected: every pick within the noise of a tie is re-done pair by pair, kirch_tiefix_kernel).
-    // IMPDAR_KIRCH_EXACT_IMPL=pair still forces the reference's arithmetic pair by pair.
-    if (mode == IMPDAR_KIRCH_EXACT && dtype == IMPDAR_F64 && p->uniform && snum < 65536 &&
-        std::fabs(tmax / dt) / sa < 65000.0 && (2.0 * hest + 400.0) / 4.0 * (double)snum * 32.0 < 2147483648.0 &&
-        !getenv("IMPDAR_KIRCH_EXACT_IMPL")) {
-        auto rows_for = [&](int xb, int nh) { return ((KF_THREADS + (int)std::ceil(sa * (xb * nh + 4 - 2)) + 8 + 31) / 32) * 32; };
-        auto fits = [&](int xb, int nh) {
-            const size_t b = (size_t)(rows_for(xb, nh) / 32) * kd_piece_bytes(xb);
-            return b <= 80 * 1024 && (nh == 1 || b > 65535);
-        };
-        // Whole radargrams: TWO tiles of 20 traces per workgroup on one ring when that ring fits half a CU's LDS, as the
-        // float32 kernel does (round 4, same-box A/B at config 3: 17.71 -> 16.91 ms; two tiles of 16: 19.2; a rank's
-        // block of under ~8000 traces keeps one tile, as there)
-        const char *ne = getenv("IMPDAR_KIRCH_NHD");        // tuning knob: tiles per workgroup, 1 | 2
-        const char *xe = getenv("IMPDAR_KIRCH_XBD");        // tuning knob: 16 | 20
-        int nhd = ne ? atoi(ne) : ((!xe && fits(20, 2) && (long long)tnum >= 8000LL * nranks) ? 2 : KD_DEFAULT_NH);
-        if (nhd != 2 || nearfield) nhd = 1;
-        int xbd = (xe && atoi(xe) == 16) ? 16 : ((xe && atoi(xe) == 20) ? 20 : ((nhd == 2 && ne) ? KD_DEFAULT_XB2 : 20));
-        if (nhd == 2 && !fits(xbd, 2)) nhd = 1;
-        if (!fits(xbd, nhd)) xbd = 16;
-        if (fits(xbd, nhd)) {
-            p->dquad = true;
-            p->xb = xbd;
-            p->nh = nhd;
-            p->quadW = rows_for(xbd, nhd);
-            p->quadSH = ((size_t)(p->quadW / 32) * kd_piece_bytes(xbd) <= 65535) ? 0 : 4;
-        }
-    }
-
-    int rc = IMPDAR_OK;
-    auto fail = [&](int code) {
-        delete p;
-        return code;
-    };
     if (hipSetDevice(ctx->device) != hipSuccess) {
         impdar_set_error("hipSetDevice(%d) failed: %s", ctx->device, hipGetErrorString(hipGetLastError()));
-        return fail(IMPDAR_ERR_HIP);
+        return IMPDAR_ERR_HIP;
     }
-    const size_t esz = impdar_dtype_size(dtype);
-    const size_t img = (size_t)(p->tnum_pad + 2 * KF_PAD_ROWS) * snum * esz;   // zero rows on both sides
-    for (int b = 0; b < 2; ++b) {
-        if (p->GT[b].ensure(img) != hipSuccess || (p->nearfield && p->DT[b].ensure(img) != hipSuccess)) {
-            impdar_set_error("hipMalloc of %zu-byte image failed", img);
-            return fail(IMPDAR_ERR_HIP);
-        }
-        (void)hipMemsetAsync(p->GT[b].p, 0, img, ctx->stream);
-        if (p->nearfield) (void)hipMemsetAsync(p->DT[b].p, 0, img, ctx->stream);
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (!grad_uniform) {
-        if ((rc = upload(p->d_ga, ga, snum * 8)) || (rc = upload(p->d_gb, gb, snum * 8)) ||
-            (rc = upload(p->d_gc, gc, snum * 8)))
-            return fail(rc);
-    }
-    // exact-kernel tables (also used by count_pairs)
-    {
-        std::vector<double> zs(snum), zs2(snum);
-        for (int k = 0; k < snum; ++k) {
-            zs[k] = vel * tt_sec[k] / 2.0;          // mig_python.py:101
-            zs2[k] = zs[k] * zs[k];                 // :102
-        }
-        std::vector<double> dpad(dist_m, dist_m + tnum);
-        dpad.resize((size_t)tnum + 64, dist_m[tnum - 1]);      // kirch_gen_kernel reads up to 31 entries past a tile's end
-        if ((rc = upload(p->d_dist, dpad.data(), dpad.size() * 8)) || (rc = upload(p->d_tt, tt_sec, (size_t)snum * 8)) ||
-            (rc = upload(p->d_zs, zs.data(), (size_t)snum * 8)) || (rc = upload(p->d_zs2, zs2.data(), (size_t)snum * 8)))
-            return fail(rc);
-    }
-    // aperture half width per sample (uniform grids): largest n with t <= tmax
-    if (p->uniform) {
-        p->h_half.resize(snum);
-        const double um = tmax / dt;
-        for (int k = 0; k < snum; ++k) {
-            const double a = tt_sec[k] / dt;
-            const double rem = um * um - a * a;
-            p->h_half[k] = rem < 0 ? -1 : (int)std::floor(std::sqrt(rem / p->alpha) + 1e-12);
-        }
-    }
-    // ---- picks that rounding noise decides (see kirch_tiescan_kernel): the table-driven kernels would break those
-    // ties one way per offset, the reference breaks them pair by pair
-    // (kirch_gen_kernel needs no list, on a uniform profile either: it re-does every pair on a half-way point in the
-    // reference's own arithmetic by itself, kg_ref_upper; rounds 3-4 sent uniform profiles with ties to the float64 kernels)
-    if (p->uniform && !p->gen && (mode == IMPDAR_KIRCH_FAST || p->dquad || !getenv("IMPDAR_KIRCH_EXACT_IMPL") ||
-                                  strcmp(getenv("IMPDAR_KIRCH_EXACT_IMPL"), "pair"))) {
-        int hg = 0;
-        for (int k = 0; k < snum; ++k) hg = std::max(hg, p->h_half[k] + 1);
-        hg = std::min(hg, tnum) + 1;
-        constexpr int TIE_CAP = 1 << 20;
-        DevBuf d_flag, d_list;
-        if (d_flag.ensure(64) != hipSuccess || d_list.ensure((size_t)TIE_CAP * sizeof(int2)) != hipSuccess) {
-            impdar_set_error("hipMalloc failed");
-            return fail(IMPDAR_ERR_HIP);
-        }
-        (void)hipMemsetAsync(d_flag.p, 0, 64, ctx->stream);
-        TableXParams T;
-        T.XK = nullptr;
-        T.XW = T.XW2 = nullptr;
-        T.zs = p->d_zs.as<double>();
-        T.zs2 = p->d_zs2.as<double>();
-        T.tt = p->d_tt.as<double>();
-        T.dx = dx;
-        T.vel = vel;
-        T.tmax = tmax;
-        T.inv_dt = 1.0 / dt;
-        T.tt0 = tt_sec[0];
-        T.snum = snum;
-        T.ntab = hg;
-        T.near = 0;
-        const double xnoise = p->xnoise;     // position noise of a pair's dist[j] - dist[xi] in units of dx, from the profile itself
-        hipLaunchKernelGGL(kirch_tiescan_kernel, dim3((snum + 255) / 256, hg), dim3(256), 0, ctx->stream, T, xnoise,
-                           d_flag.as<int>(), d_list.as<int2>(), TIE_CAP);
-        int count = 0;
-        if (hipMemcpyAsync(&count, d_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            impdar_set_error("tie scan failed: %s", hipGetErrorString(hipGetLastError()));
-            return fail(IMPDAR_ERR_HIP);
-        }
-        const bool no_fix = getenv("IMPDAR_KIRCH_TIEFIX") && !strcmp(getenv("IMPDAR_KIRCH_TIEFIX"), "0");   // diagnostic
-        if (count > 0 && count <= TIE_CAP && !no_fix) {
-            // group the flagged offsets by sample (sorted: the correction adds them in a fixed order)
-            std::vector<int2> list(count);
-            if (hipMemcpy(list.data(), d_list.p, (size_t)count * sizeof(int2), hipMemcpyDeviceToHost) != hipSuccess) {
-                impdar_set_error("tie list download failed");
-                return fail(IMPDAR_ERR_HIP);
-            }
-            std::sort(list.begin(), list.end(), [](const int2 &a, const int2 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); });
-            std::vector<int> g_ti, g_off, g_n(count);
-            for (int i = 0; i < count; ++i) {
-                if (i == 0 || list[i].x != list[i - 1].x) {
-                    g_ti.push_back(list[i].x);
-                    g_off.push_back(i);
-                }
-                g_n[i] = list[i].y;
-            }
-            g_off.push_back(count);
-            p->ntie_groups = (int)g_ti.size();
-            if ((rc = upload(p->d_tie_ti, g_ti.data(), g_ti.size() * 4)) || (rc = upload(p->d_tie_off, g_off.data(), g_off.size() * 4)) ||
-                (rc = upload(p->d_tie_n, g_n.data(), g_n.size() * 4)))
-                return fail(rc);
-        }
-        p->tie_ambiguous = count > TIE_CAP || (count > 0 && no_fix);
-        if (p->tie_ambiguous) {
-            // more ties than the list holds (or the correction switched off): the float32 ring kernels stay available
-            // when asked for by name; everything the library chooses itself goes per pair
-            if (mode == IMPDAR_KIRCH_FAST && requested_mode == IMPDAR_KIRCH_AUTO) {
-                mode = p->mode = IMPDAR_KIRCH_EXACT;
-                p->quad = false;
-                p->xb = 16;
-            }
-            p->dquad = false;
-            p->xtab_off = true;
-        }
-    }
-    if (p->gen) {
-        // per-sample float32 factors, the squared half-way radii of the float64 re-decision, per-chunk bounds
-        const int nch = (snum + KF_THREADS - 1) / KF_THREADS;
-        p->nchunks = nch;
-        std::vector<float> a(snum), a2(snum), alo2(nch, 3.0e38f);
-        p->h_zs2min.assign(nch, 1e300);
-        for (int k = 0; k < snum; ++k) {
-            const double ak = tt_sec[k] / dt;
-            a[k] = (float)ak;
-            a2[k] = (float)(ak * ak / ((double)(gen_w - 1) * (double)(gen_w - 1)));    // normalised to the slot (kirch_gen_kernel)
-            alo2[k / KF_THREADS] = std::min(alo2[k / KF_THREADS], (float)(ak * ak) * (1.0f - 1.0e-6f));
-            const double zs = vel * tt_sec[k] / 2.0;
-            p->h_zs2min[k / KF_THREADS] = std::min(p->h_zs2min[k / KF_THREADS], zs * zs);
-        }
-        p->h_dist.assign(dist_m, dist_m + tnum);
-        if ((rc = upload(p->d_ga32, a.data(), snum * 4)) || (rc = upload(p->d_ga2_32, a2.data(), snum * 4)) ||
-            (rc = upload(p->d_alo2, alo2.data(), nch * 4)))
-            return fail(rc);
-    }
-    const int ringS = p->dquad ? 4 : 8;            // steps per block of the ring kernels (traces per 32-byte row)
-    if ((mode == IMPDAR_KIRCH_FAST && !p->gen) || p->dquad) {
-        const int nch = (snum + KF_THREADS - 1) / KF_THREADS;
-        p->nchunks = nch;
-        std::vector<int> hmax(nch, 0);
-        if (p->dquad) {
-            // float64 per-sample factors, from the reference's own zs = v t / 2 (mig_python.py:101):
-            //   cos(theta) = zs / sqrt(zs^2 + (n dx)^2) = sign(zs) * rsqrt(1 + c1 n^2),   c1 = (dx / zs)^2
-            //   far field  : cos / (2 pi v)     = fin * |cos|,           fin = sign(zs) / (2 pi v)
-            //   near field : cos / (2 pi rs^2)  = fin * c2 * |cos|^3,    c2 = v / zs^2
-            // zs = 0: the whole output row is 0 (cos = 0 off the apex, the apex is 0/0 and dropped): fin = 0
-            std::vector<double> c1(snum), c2(snum), fin(snum);
-            for (int k = 0; k < snum; ++k) {
-                const double zs = vel * tt_sec[k] / 2.0;
-                if (zs == 0.0) {
-                    c1[k] = c2[k] = fin[k] = 0.0;
-                    continue;
-                }
-                c1[k] = std::min((dx / zs) * (dx / zs), 1e300);
-                c2[k] = std::min(vel / (zs * zs), 1e300);
-                fin[k] = (zs > 0 ? 1.0 : -1.0) / (2.0 * M_PI * vel);
-            }
-            if ((rc = upload(p->d_c1d, c1.data(), snum * 8)) || (rc = upload(p->d_c2d, c2.data(), snum * 8)) ||
-                (rc = upload(p->d_find, fin.data(), snum * 8)))
-                return fail(rc);
-        } else {
-            // with a = tt/dt (samples) and rs = half * sqrt(a^2 + alpha n^2):
-            //   cos(theta)        = a / sqrt(a^2 + alpha n^2) = sign(a) * rsq(1 + c1 n^2),  c1 = alpha / a^2
-            //   far-field weight  = cos / (2 pi v)            = fin * |cos|,                 fin = sign(a) / (2 pi v)
-            //   near-field weight = cos / (2 pi rs^2)         = fin * c2 * |cos|^3,          c2 = v / (half a)^2
-            // a = 0 (a sample at t = 0): cos = 0 for every n != 0 and the apex is 0/0 (dropped) -> fin = 0
-            std::vector<float> c1(snum), c2(snum), fin(snum);
-            const double half = vel * dt / 2.0;         // metres per sample of two-way time
-            for (int k = 0; k < snum; ++k) {
-                const double a = tt_sec[k] / dt;
-                if (a == 0.0) {
-                    c1[k] = c2[k] = fin[k] = 0.f;
-                    continue;
-                }
-                c1[k] = (float)std::min(p->alpha / (a * a), 1e30);
-                c2[k] = (float)std::min(vel / (half * half * a * a), 1e30);
-                fin[k] = (float)((a > 0 ? 1.0 : -1.0) / (2.0 * M_PI * vel));
-            }
-            if ((rc = upload(p->d_c1, c1.data(), snum * 4)) || (rc = upload(p->d_c2, c2.data(), snum * 4)) ||
-                (rc = upload(p->d_fin, fin.data(), snum * 4)))
-                return fail(rc);
-        }
-        int hglob = 0;
-        std::vector<double> cmin(nch), cmax(nch);
-        for (int c = 0; c < nch; ++c) {
-            double amin = 1e300, amax = 0;
-            int h = 0;
-            for (int k = c * KF_THREADS; k < std::min(snum, (c + 1) * KF_THREADS); ++k) {
-                const double a = tt_sec[k] / dt;
-                amin = std::min(amin, a * a);
-                amax = std::max(amax, a * a);
-                h = std::max(h, p->h_half[k] + 1);
-            }
-            hmax[c] = h;
-            hglob = std::max(hglob, h);
-            cmin[c] = amin;
-            cmax[c] = amax;
-        }
-        // offsets beyond the profile length can only meet traces outside the profile (zero
-        // rows), so the tables need not extend past tnum even when the aperture does
-        hglob = std::min(hglob, tnum + 128);
-        for (int c = 0; c < nch; ++c) hmax[c] = std::min(hmax[c], hglob);
-        const int nb = hglob + 64;
-        p->nb = nb;
-        p->ntab = hglob + 1;       // offsets 0..hglob-1 (hmax carries a guard) + one all-zero row
-        // ring kernels: tables by step block, row r <-> offsets n = S (r - mrow0) + 1 .. + S
-        p->mrow0 = hglob / ringS + 8;
-        p->nrows = 2 * (hglob / ringS) + 64;
-        {
-            const size_t tkbytes = (p->quad || p->dquad) ? (size_t)p->nrows * kq_tkb_stride(snum) * 2 * ringS
-                                                         : (size_t)p->ntab * snum * 2;
-            if (tkbytes >= ((size_t)1 << 31)) {      // the kernels address it as one raw buffer
-                impdar_set_error("fast Kirchhoff pick table of %zu bytes exceeds 2 GiB; use the exact mode", tkbytes);
-                return fail(IMPDAR_ERR_UNSUPPORTED);
-            }
-            const size_t ent = (size_t)p->ntab * snum;
-            bool ok = true;
-            for (int b = 0; b < 2; ++b) {
-                ok = ok && p->d_TK[b].ensure(tkbytes) == hipSuccess;
-                if (!p->quad && !p->dquad) ok = ok && p->d_TW[b].ensure(ent * 4) == hipSuccess;
-                if (!p->quad && !p->dquad && p->nearfield) ok = ok && p->d_TW2[b].ensure(ent * 4) == hipSuccess;
-            }
-            if (!ok) {
-                impdar_set_error("hipMalloc of the %zu-byte pick table failed", tkbytes);
-                return fail(IMPDAR_ERR_HIP);
-            }
-        }
-        // staging windows: smallest / largest sample index any lane of chunk c
-        // can pick at offset |n| (one guard sample each side)
-        std::vector<int> klo((size_t)nch * nb), khi((size_t)nch * nb);
-        const double u0 = tt_sec[0] / dt;
-        for (int c = 0; c < nch; ++c)
-            for (int n = 0; n < nb; ++n) {
-                const double bn = p->alpha * (double)n * (double)n;
-                const double ulo = std::sqrt(cmin[c] + bn) - u0, uhi = std::sqrt(cmax[c] + bn) - u0;
-                klo[(size_t)c * nb + n] = std::max(0, (int)std::floor(ulo) - 1);
-                khi[(size_t)c * nb + n] = std::min(snum - 1, (int)std::ceil(uhi) + 1);
-            }
-        if (p->quad || p->dquad) {
-            // the S traces block r adds are read by the steps n = S (r - mrow0) + 1 .. + XB + S - 2 (they enter
-            // the XB-trace window of a lane at its last slot and leave it XB - 1 steps later)
-            std::vector<int> win((size_t)nch * p->nrows * 2);
-            for (int r = 0; r < p->nrows; ++r) {
-                // (with nh tiles on one ring the later tiles read the same traces (nh - 1) xb offsets earlier)
-                const long long nz = (long long)ringS * (r - p->mrow0) + 1 + p->xb + ringS - 2;
-                const long long na = (long long)ringS * (r - p->mrow0) + 1 - (long long)((p->quad || p->dquad) ? p->nh - 1 : 0) * p->xb;
-                const long long lo = (na <= 0 && nz >= 0) ? 0 : std::min(std::llabs(na), std::llabs(nz));
-                const long long hi = std::max(std::llabs(na), std::llabs(nz));
-                for (int c = 0; c < nch; ++c) {
-                    const int kmin = klo[(size_t)c * nb + std::min<long long>(lo, nb - 1)];
-                    const int kmax = khi[(size_t)c * nb + std::min<long long>(hi, nb - 1)];
-                    win[((size_t)c * p->nrows + r) * 2 + 0] = kmin | ((kmin % p->quadW) << 16);
-                    win[((size_t)c * p->nrows + r) * 2 + 1] = kmax;
-                }
-            }
-            if ((rc = upload(p->d_WIN, win.data(), win.size() * 4))) return fail(rc);
-        }
-        p->h_hmax = hmax;
-        if ((rc = upload(p->d_hmax, hmax.data(), nch * 4)) || (rc = upload(p->d_klo, klo.data(), klo.size() * 4)) ||
-            (rc = upload(p->d_khi, khi.data(), khi.size() * 4)))
-            return fail(rc);
-    }
-    for (int s = 0; s < impdar_kirch_plan::NSLOT; ++s)
-        for (int i = 0; i < 6; ++i)
-            if (hipEventCreate(&p->evs[s][i]) != hipSuccess) {
-                impdar_set_error("hipEventCreate failed");
-                return fail(IMPDAR_ERR_HIP);
-            }
-    if (hipEventCreateWithFlags(&p->ev_ready[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_ready[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_free[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_free[1], hipEventDisableTiming) != hipSuccess) {
-        impdar_set_error("hipEventCreate failed");
-        return fail(IMPDAR_ERR_HIP);
-    }
-    *out = p;
+    const bool own = caller && !caller->standard;
+    int rc;
+    if ((rc = kirch_alloc_images(p.get())) ||
+        (rc = kirch_upload_axes(p.get(), dist_m, tt_sec, ga, gb, gc, own ? caller->zs : nullptr, own ? caller->zs2 : nullptr)) ||
+        (p->want_tie_scan && (rc = kirch_tie_scan(p.get()))) ||
+        (p->gen && (rc = kirch_upload_gen_tables(p.get(), dist_m, tt_sec))) ||
+        (((p->mode == IMPDAR_KIRCH_FAST && !p->gen) || p->dquad) && (rc = kirch_upload_ring_tables(p.get(), tt_sec))) ||
+        (rc = kirch_create_events(p.get())))
+        return rc;
+    *out = p.release();
     return IMPDAR_OK;
+}
+
+extern "C" int impdar_kirch_plan_create(impdar_ctx *ctx, int dtype, int snum, int tnum,
+                                        const double *dist_m, const double *tt_sec, double vel,
+                                        int nearfield, int grad_uniform, double grad_h,
+                                        const double *ga, const double *gb, const double *gc,
+                                        int mode, int nranks, impdar_kirch_plan **out)
+{
+    return kirch_plan_create_impl(ctx, dtype, snum, tnum, dist_m, tt_sec, vel, nearfield, grad_uniform, grad_h, ga, gb, gc, mode, nranks,
+                                  KirchKnobs::from_env(), nullptr, out);
 }
 
 extern "C" void impdar_kirch_plan_destroy(impdar_kirch_plan *p)
@@ -2208,16 +1905,86 @@ extern "C" void impdar_kirch_plan_destroy(impdar_kirch_plan *p)
 extern "C" int impdar_kirch_plan_mode(const impdar_kirch_plan *p) { return p ? p->mode : IMPDAR_ERR_ARG; }
 extern "C" double impdar_kirch_plan_xnoise(const impdar_kirch_plan *p) { return p ? p->xnoise : -1.0; }
 extern "C" int impdar_kirch_plan_tnum_pad(const impdar_kirch_plan *p) { return p ? p->tnum_pad : IMPDAR_ERR_ARG; }
+extern "C" int impdar_kirch_plan_kernel(const impdar_kirch_plan *p) { return p ? p->kernel() : IMPDAR_ERR_ARG; }
 
-extern "C" int impdar_kirch_plan_kernel(const impdar_kirch_plan *p)
+// gradient + transpose of column block [jlo, jlo + nloc) into buffer set b
+static int prep_image(impdar_kirch_plan *p, const void *d_data, int ld, int jlo, int nloc, int precomputed, int b, hipStream_t st)
 {
-    if (!p) return IMPDAR_ERR_ARG;
-    if (p->gen) return IMPDAR_KERNEL_GEN;
-    if (p->mode == IMPDAR_KIRCH_FAST) return p->quad ? IMPDAR_KERNEL_QUAD : IMPDAR_KERNEL_TAB;
-    if (p->dquad) return IMPDAR_KERNEL_DQUAD;
-    const char *e = getenv("IMPDAR_KIRCH_EXACT_IMPL");
-    if (p->uniform && !p->xtab_off && !(e && !strcmp(e, "pair"))) return IMPDAR_KERNEL_EXACT_TAB;
-    return IMPDAR_KERNEL_EXACT_PAIR;
+    PrepParams P;
+    P.data = d_data;
+    P.ld = ld;
+    P.snum = p->snum;
+    P.nloc = nloc;
+    P.jlo = jlo;
+    P.GT = img_row0(p, p->GT[b]);
+    P.DT = p->nearfield ? img_row0(p, p->DT[b]) : nullptr;
+    P.grad_uniform = p->grad_uniform;
+    P.precomputed = precomputed;
+    P.grad_h = p->grad_h;
+    P.ga = p->d_ga.as<double>();
+    P.gb = p->d_gb.as<double>();
+    P.gc = p->d_gc.as<double>();
+    P.clean = (p->mode == IMPDAR_KIRCH_FAST) ? 1 : (p->dquad ? 2 : 0);
+    P.i8 = (p->quad || p->dquad) ? 1 : 0;
+    dim3 grid((nloc + 63) / 64, (p->snum + 63) / 64);
+    if (p->dtype == IMPDAR_F32 && P.i8)
+        hipLaunchKernelGGL((kirch_prep_direct_kernel<float, 8>), dim3((nloc + 255) / 256, p->snum), dim3(256), 0, st, P);
+    else if (p->dquad)
+        hipLaunchKernelGGL((kirch_prep_direct_kernel<double, 4>), dim3((nloc + 255) / 256, p->snum), dim3(256), 0, st, P);
+    else if (p->dtype == IMPDAR_F32)
+        hipLaunchKernelGGL((kirch_prep_kernel<float, float>), grid, dim3(256), 0, st, P);
+    else
+        hipLaunchKernelGGL((kirch_prep_kernel<double, double>), grid, dim3(256), 0, st, P);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
+}
+
+// The pick table of the ring kernels depends on the plan's geometry only (like an FFT plan's twiddles): it is built by the
+// first prep into each of the two buffer sets and kept.  (Round 1 rebuilt it with every prep -- 0.06-0.13 ms on the producer
+// stream, hidden behind a whole-radargram diffraction sum but a tenth of the step of an 8-rank block.)
+static int prep_table_ring(impdar_kirch_plan *p, int b, hipStream_t st)
+{
+    if (p->table_built[b]) return IMPDAR_OK;
+    p->table_built[b] = true;
+    ++p->diag_tables_built;
+    TableQParams T;
+    T.TKB = p->d_TK[b].as<uint4>();
+    kirch_fill_axes(T, p);
+    T.dx = p->dx;
+    T.nrows = p->nrows;
+    T.mrow0 = p->mrow0;
+    T.nmax = p->ntab - 1;
+    T.wmod = p->quadW;
+    T.sh = p->quadSH;
+    T.ps = p->dquad ? kd_piece_bytes(p->xb) : kq_piece_bytes_lk(p->xb, p->lk);
+    // rows a + mrow0 (a >= 0) and mrow0 - a - 1: a runs over the larger of the two sides
+    const int na = std::max(p->nrows - p->mrow0, p->mrow0);
+    if (p->dquad)
+        hipLaunchKernelGGL(kirch_tabled_kernel, dim3((p->snum + 255) / 256, na), dim3(256), 0, st, T);
+    else
+        hipLaunchKernelGGL(kirch_tableq_kernel, dim3((p->snum + 255) / 256, na), dim3(256), 0, st, T);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
+}
+
+// kirch_tab_kernel: geometry-only pick/weight table, rebuilt with every prep (counted in prep time)
+static int prep_table_tab(impdar_kirch_plan *p, int b, hipStream_t st)
+{
+    TableParams T;
+    T.TK = p->d_TK[b].as<unsigned short>();
+    T.TW = p->d_TW[b].as<float>();
+    T.TW2 = p->d_TW2[b].as<float>();
+    kirch_fill_axes(T, p);
+    T.dx = p->dx;
+    T.ntab = p->ntab;
+    T.near = p->nearfield;
+    T.wmod = KF_W;
+    T.kscale = 4;
+    T.sentinel = 0;
+    T.write_w = 1;
+    hipLaunchKernelGGL(kirch_table_kernel, dim3((p->snum + 255) / 256, p->ntab), dim3(256), 0, st, T);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
 }
 
 // `more`: further input traces of the radargram whose first traces an earlier prep took, AFTER a migrate that reads
@@ -2255,90 +2022,13 @@ static int kirch_prep_impl(impdar_kirch_plan *p, const void *d_data, int ld, int
         IMPDAR_HIP_CHECK(hipStreamWaitEvent(st, p->ev_free[p->last_out_buf], 0));
     hipEvent_t *ev = p->evs[p->slot];
     if (!p->haves[p->slot][0]) IMPDAR_HIP_CHECK(hipEventRecord(ev[0], st));
-    if (nloc > 0) {
-        PrepParams P;
-        P.data = d_data;
-        P.ld = ld;
-        P.snum = p->snum;
-        P.nloc = nloc;
-        P.jlo = jlo;
-        P.GT = img_row0(p, p->GT[b]);
-        P.DT = p->nearfield ? img_row0(p, p->DT[b]) : nullptr;
-        P.grad_uniform = p->grad_uniform;
-        P.precomputed = precomputed;
-        P.grad_h = p->grad_h;
-        P.ga = p->d_ga.as<double>();
-        P.gb = p->d_gb.as<double>();
-        P.gc = p->d_gc.as<double>();
-        P.clean = (p->mode == IMPDAR_KIRCH_FAST) ? 1 : (p->dquad ? 2 : 0);
-        P.i8 = (p->quad || p->dquad) ? 1 : 0;
-        dim3 grid((nloc + 63) / 64, (p->snum + 63) / 64);
-        if (p->dtype == IMPDAR_F32 && P.i8)
-            hipLaunchKernelGGL((kirch_prep_direct_kernel<float, 8>), dim3((nloc + 255) / 256, p->snum), dim3(256), 0, st, P);
-        else if (p->dquad)
-            hipLaunchKernelGGL((kirch_prep_direct_kernel<double, 4>), dim3((nloc + 255) / 256, p->snum), dim3(256), 0, st, P);
-        else if (p->dtype == IMPDAR_F32)
-            hipLaunchKernelGGL((kirch_prep_kernel<float, float>), grid, dim3(256), 0, st, P);
-        else
-            hipLaunchKernelGGL((kirch_prep_kernel<double, double>), grid, dim3(256), 0, st, P);
-        IMPDAR_HIP_CHECK(hipGetLastError());
-    }
-    // The pick table depends on the plan's geometry only (like an FFT plan's twiddles): it is built by the first prep
-    // into each of the two buffer sets and kept.  (Round 1 rebuilt it with every prep -- 0.06-0.13 ms on the producer
-    // stream, hidden behind a whole-radargram diffraction sum but a tenth of the step of an 8-rank block.)
-    if (((p->mode == IMPDAR_KIRCH_FAST && p->quad) || p->dquad) && p->table_built[b]) {
-        // this buffer set's table is in place
-    } else if ((p->mode == IMPDAR_KIRCH_FAST && p->quad) || p->dquad) {
-        p->table_built[b] = true;
-        ++p->diag_tables_built;
-        TableQParams T;
-        T.TKB = p->d_TK[b].as<uint4>();
-        T.zs = p->d_zs.as<double>();
-        T.zs2 = p->d_zs2.as<double>();
-        T.tt = p->d_tt.as<double>();
-        T.dx = p->dx;
-        T.vel = p->vel;
-        T.tmax = p->tmax;
-        T.inv_dt = 1.0 / p->dt;
-        T.tt0 = p->tt0;
-        T.snum = p->snum;
-        T.nrows = p->nrows;
-        T.mrow0 = p->mrow0;
-        T.nmax = p->ntab - 1;
-        T.wmod = p->quadW;
-        T.sh = p->quadSH;
-        T.ps = p->dquad ? kd_piece_bytes(p->xb) : kq_piece_bytes_lk(p->xb, p->lk);
-        // rows a + mrow0 (a >= 0) and mrow0 - a - 1: a runs over the larger of the two sides
-        const int na = std::max(p->nrows - p->mrow0, p->mrow0);
-        if (p->dquad)
-            hipLaunchKernelGGL(kirch_tabled_kernel, dim3((p->snum + 255) / 256, na), dim3(256), 0, st, T);
-        else
-            hipLaunchKernelGGL(kirch_tableq_kernel, dim3((p->snum + 255) / 256, na), dim3(256), 0, st, T);
-        IMPDAR_HIP_CHECK(hipGetLastError());
-    } else if (p->mode == IMPDAR_KIRCH_FAST && !p->gen) {
-        // geometry-only pick/weight table, rebuilt with every prep (counted in prep time)
-        TableParams T;
-        T.TK = p->d_TK[b].as<unsigned short>();
-        T.TW = p->d_TW[b].as<float>();
-        T.TW2 = p->d_TW2[b].as<float>();
-        T.zs = p->d_zs.as<double>();
-        T.zs2 = p->d_zs2.as<double>();
-        T.tt = p->d_tt.as<double>();
-        T.dx = p->dx;
-        T.vel = p->vel;
-        T.tmax = p->tmax;
-        T.inv_dt = 1.0 / p->dt;
-        T.tt0 = p->tt0;
-        T.snum = p->snum;
-        T.ntab = p->ntab;
-        T.near = p->nearfield;
-        T.wmod = KF_W;
-        T.kscale = 4;
-        T.sentinel = 0;
-        T.write_w = 1;
-        hipLaunchKernelGGL(kirch_table_kernel, dim3((p->snum + 255) / 256, p->ntab), dim3(256), 0, st, T);
-        IMPDAR_HIP_CHECK(hipGetLastError());
-    }
+    int rc;
+    if (nloc > 0 && (rc = prep_image(p, d_data, ld, jlo, nloc, precomputed, b, st))) return rc;
+    if ((p->mode == IMPDAR_KIRCH_FAST && p->quad) || p->dquad)
+        rc = prep_table_ring(p, b, st);
+    else
+        rc = (p->mode == IMPDAR_KIRCH_FAST && !p->gen) ? prep_table_tab(p, b, st) : IMPDAR_OK;
+    if (rc) return rc;
     IMPDAR_HIP_CHECK(hipEventRecord(ev[1], st));
     IMPDAR_HIP_CHECK(hipEventRecord(p->ev_ready[b], st));
     p->haves[p->slot][0] = true;
@@ -2355,55 +2045,17 @@ int impdar_kirch_prep_precomputed(impdar_kirch_plan *p, const void *d_grad, int 
     return kirch_prep_impl(p, d_grad, ld, jlo, nloc, 1);
 }
 
-// Which output tile a workgroup takes: blocks are dealt round-robin over the 8 XCDs (block b -> XCD b & 7), so slot
-// q of chunk c on XCD x is block ((c * tiles_per_xcd + q) * 8 + x).  The arithmetic rule (groups of G adjacent tiles
-// per XCD in turn) leaves the XCDs up to +-3 % apart in work at config 3: tiles near the ends of the profile walk
-// clipped apertures, and which XCD gets them depends on the tile count.  Here the groups of G adjacent tiles (they
-// share staging lines in the XCD's L2) are handed out per chunk, longest first, each to the XCD with the least
-// accumulated walk so far (steps rounded up to ring revolutions, plus a prologue's worth).  -1 = empty slot.
+// The tile map of a launch (kirch_tilemap, kirch_route.h), kept with the plan under the key it was built for.
 static int build_tilemap(impdar_kirch_plan *p, FastParams &P, int tile_w, int align_mask, int ring_blocks, int step_block,
                          hipStream_t st)
 {
     P.tilemap = nullptr;
-    if ((int)p->h_hmax.size() != P.nchunks) return IMPDAR_OK;
     const int key[5] = {P.xlo, P.xhi, tile_w, P.G, P.tiles_per_xcd};
     const size_t n = (size_t)P.nchunks * P.tiles_per_xcd * 8;
     if (memcmp(key, p->tm_key, sizeof(key)) != 0 || p->h_tilemap.size() != n) {
-        std::vector<short> map(n, (short)-1);
-        const int x00 = P.xlo & ~align_mask;
-        const int G = P.G, units = (P.nxt + G - 1) / G, cap = P.tiles_per_xcd / G;
-        std::vector<double> load(8, 0.0);
-        std::vector<std::pair<double, int>> cost(units);
-        for (int c = 0; c < P.nchunks; ++c) {
-            const int hm = p->h_hmax[c];
-            for (int u = 0; u < units; ++u) {
-                double w = 0;
-                for (int t = u * G; t < std::min((u + 1) * G, P.nxt); ++t) {
-                    const int x0 = x00 + t * tile_w;
-                    const int nlo = std::max(-hm, -(x0 + tile_w - 1)), nhi = std::min(hm, p->tnum - 1 - x0);
-                    const int blocks = std::max(0, nhi - nlo + step_block) / step_block;
-                    w += ((blocks + ring_blocks - 1) / ring_blocks) * ring_blocks + 8;
-                }
-                cost[u] = {w, u};
-            }
-            std::sort(cost.begin(), cost.end(), [](const std::pair<double, int> &a, const std::pair<double, int> &b) {
-                return a.first > b.first || (a.first == b.first && a.second < b.second);
-            });
-            int used[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (const auto &cu : cost) {
-                int best = -1;
-                for (int x = 0; x < 8; ++x)
-                    if (used[x] < cap && (best < 0 || load[x] < load[best])) best = x;
-                if (best < 0) return IMPDAR_OK;          // cannot happen (8 cap >= units); keep the arithmetic rule
-                for (int g = 0; g < G; ++g) {
-                    const int t = cu.second * G + g;
-                    map[((size_t)c * P.tiles_per_xcd + (size_t)used[best] * G + g) * 8 + best] = (short)(t < P.nxt ? t : -1);
-                }
-                ++used[best];
-                load[best] += cu.first;
-            }
-        }
-        if (P.nxt > 32767) return IMPDAR_OK;
+        std::vector<short> map = kirch_tilemap(p->h_hmax, p->tnum, P.xlo, P.xhi, tile_w, align_mask, ring_blocks, step_block, P.G,
+                                               P.tiles_per_xcd, P.nchunks);
+        if (map.empty()) return IMPDAR_OK;
         p->h_tilemap.swap(map);
         memcpy(p->tm_key, key, sizeof(key));
         IMPDAR_HIP_CHECK(p->d_tilemap.ensure(n * sizeof(short)));
@@ -2432,156 +2084,97 @@ static int kirch_reserved_slots(const impdar_kirch_plan *p)
     return std::min(std::max(r, 0), 256);
 }
 
-template <int XB, int OCC, int SH, int NH = 1, int LK = 0>
-static int launch_quad(impdar_kirch_plan *p, const FastParams &P0, int nx, hipStream_t st)
+// the pieces of every walk of a many-rank plan, summed in piece order
+template <typename T>
+static void kirch_launch_combine(const FastParams &P, hipStream_t st)
 {
-    FastParams P = P0;
-    const int ntiles = (P.xhi - (P.xlo & ~7) + XB * NH - 1) / (XB * NH);      // workgroup tiles start at a multiple of 8
-    P.nxt = ntiles;
-    {
-        // groups of 4 adjacent tiles per XCD share staging lines in L2 (same-box A/B at config 3: 1.2-1.6 %
-        // faster than 1, L2 misses -36 %; 6 / 8 / 12 are slower), but the XCDs only stay balanced when each gets many
-        // groups: with the 45-70 tiles of an 8-rank block groups of 4 leave half of the XCDs with twice the work (-16 %).
-        P.G = ntiles >= 256 ? 4 : 1;
-    }
-    const int per = 8 * P.G;
-    const int nxt_pad = ((ntiles + per - 1) / per) * per;
-    P.tiles_per_xcd = nxt_pad / 8;
-    const int nblk = P.nchunks * nxt_pad;
-    const int W = p->quadW;
-    {
-        const int trc = build_tilemap(p, P, XB * NH, 7, (kq_ring_slots(XB) + 8 * LK) / 8, 8, st);
-        if (trc) return trc;
-    }
-    const size_t shmem = (size_t)(W / 32) * kq_piece_bytes_lk(XB, LK) * (p->nearfield ? 2 : 1) + 16;   // + the item slot
-    if (p->nearfield) {
-        auto k = kirch_quad_kernel<XB, true, 1, SH, 1, 0>;
-        IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        hipLaunchKernelGGL(k, dim3(nblk), dim3(KF_THREADS), shmem, st, P, W);
-    } else {
-        auto k = kirch_quad_kernel<XB, false, OCC, SH, NH, LK>;
-        IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        int grid = nblk;
-        if (P.tilemap) {
-            // persistent workgroups: as many as are resident at once, each pulling items from the per-XCD queues
-            if (p->slots <= 0) {        // resident workgroups of this plan's kernel on this device: asked once
-                int per_cu = 0, ncu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, KF_THREADS * NH, shmem) == hipSuccess &&
-                    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->ctx->device) == hipSuccess &&
-                    per_cu > 0 && ncu > 0)
-                    p->slots = per_cu * ncu;
-                else
-                    (void)hipGetLastError();
-            }
-            // many-rank plans: every walk in 2 or 4 pieces with partial images of their own (p->walk_parts_log2)
-            const int pl2 = NH == 1 ? p->walk_parts_log2 : 0;
-            const size_t nout = (size_t)P.snum * P.ldo, esz = impdar_dtype_size(p->dtype);
-            const bool pieces = pl2 > 0 && p->slots > 0 && p->d_partial.ensure((nout << pl2) * esz) == hipSuccess;
-            if (p->slots > 0 && (p->slots < nblk || pieces) && p->d_queue.ensure(8 * 64) == hipSuccess) {
-                IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_queue.p, 0, 8 * 64, st));
-                P.queue = p->d_queue.as<int>();
-                if (pieces) {
-                    P.parts_log2 = pl2;
-                    P.partial = p->d_partial.p;
-                    P.part_stride = nout;
-                    // a piece no workgroup reaches (tiles beyond the block's end) must read as zero
-                    IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_partial.p, 0, (nout << pl2) * esz, st));
-                }
-                grid = (int)std::min<long long>(std::max(p->slots - kirch_reserved_slots(p), 1), (long long)nblk << P.parts_log2);
-            }
-        }
-        hipLaunchKernelGGL(k, dim3(grid), dim3(KF_THREADS * NH), shmem, st, P, W);
-        if (P.parts_log2) {
-            const size_t nout = (size_t)P.snum * P.ldo;
-            const dim3 cg((unsigned)((nout + 255) / 256));
-            if (p->dtype == IMPDAR_F32) {
-                if (P.parts_log2 == 2)
-                    hipLaunchKernelGGL((kirch_combine_kernel<float, 4>), cg, dim3(256), 0, st, (const float *)P.partial, (float *)P.out, nout);
-                else
-                    hipLaunchKernelGGL((kirch_combine_kernel<float, 2>), cg, dim3(256), 0, st, (const float *)P.partial, (float *)P.out, nout);
-            } else {
-                if (P.parts_log2 == 2)
-                    hipLaunchKernelGGL((kirch_combine_kernel<double, 4>), cg, dim3(256), 0, st, (const double *)P.partial, (double *)P.out, nout);
-                else
-                    hipLaunchKernelGGL((kirch_combine_kernel<double, 2>), cg, dim3(256), 0, st, (const double *)P.partial, (double *)P.out, nout);
-            }
-        }
-    }
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    return IMPDAR_OK;
+    const size_t nout = (size_t)P.snum * P.ldo;
+    const dim3 cg((unsigned)((nout + 255) / 256));
+    if (P.parts_log2 == 2)
+        hipLaunchKernelGGL((kirch_combine_kernel<T, 4>), cg, dim3(256), 0, st, (const T *)P.partial, (T *)P.out, nout);
+    else
+        hipLaunchKernelGGL((kirch_combine_kernel<T, 2>), cg, dim3(256), 0, st, (const T *)P.partial, (T *)P.out, nout);
 }
 
-template <int XB, int SH, int NH = 1>
-static int launch_dquad(impdar_kirch_plan *p, const FastParams &P0, hipStream_t st)
+// What launch_ring needs of a ring kernel's instantiation: the kernel in its near-field (one tile per workgroup, one
+// workgroup per CU) and far-field forms, where tiles may start, and the ring as the tile map's cost model sees it.
+template <int XB_, int OCC, int SH, int NH_ = 1, int LK = 0>
+struct RingF32 {
+    static constexpr int XB = XB_, NH = NH_;
+    static constexpr int align_mask = 7, step_block = 8, ring_blocks = (kq_ring_slots(XB) + 8 * LK) / 8, piece_bytes = kq_piece_bytes_lk(XB, LK);
+    static auto near_kernel() { return kirch_quad_kernel<XB, true, 1, SH, 1, 0>; }
+    static auto far_kernel() { return kirch_quad_kernel<XB, false, OCC, SH, NH, LK>; }
+};
+template <int XB_, int SH, int NH_ = 1>
+struct RingF64 {
+    static constexpr int XB = XB_, NH = NH_;
+    static constexpr int align_mask = 3, step_block = 4, ring_blocks = kd_ring_slots(XB) / 4, piece_bytes = kd_piece_bytes(XB);
+    static auto near_kernel() { return kirch_dquad_kernel<XB, true, 1, SH, 1>; }
+    static auto far_kernel() { return kirch_dquad_kernel<XB, false, (NH > 1 ? 4 : 2), SH, NH>; }
+};
+
+template <typename K>
+static int launch_ring(impdar_kirch_plan *p, const FastParams &P0, hipStream_t st)
 {
+    constexpr int XB = K::XB, NH = K::NH;
     FastParams P = P0;
-    const int ntiles = (P.xhi - (P.xlo & ~3) + XB * NH - 1) / (XB * NH);      // workgroup tiles start at a multiple of 4
+    const int ntiles = (P.xhi - (P.xlo & ~K::align_mask) + XB * NH - 1) / (XB * NH);      // workgroup tiles start at a multiple of 8 (4)
     P.nxt = ntiles;
-    {
-        P.G = ntiles >= 256 ? 4 : 1;
-    }
+    // groups of 4 adjacent tiles per XCD share staging lines in L2 (same-box A/B at config 3: 1.2-1.6 %
+    // faster than 1, L2 misses -36 %; 6 / 8 / 12 are slower), but the XCDs only stay balanced when each gets many
+    // groups: with the 45-70 tiles of an 8-rank block groups of 4 leave half of the XCDs with twice the work (-16 %).
+    P.G = ntiles >= 256 ? 4 : 1;
     const int per = 8 * P.G;
     const int nxt_pad = ((ntiles + per - 1) / per) * per;
     P.tiles_per_xcd = nxt_pad / 8;
     const int nblk = P.nchunks * nxt_pad;
     const int W = p->quadW;
     {
-        const int trc = build_tilemap(p, P, XB * NH, 3, kd_ring_slots(XB) / 4, 4, st);
+        const int trc = build_tilemap(p, P, XB * NH, K::align_mask, K::ring_blocks, K::step_block, st);
         if (trc) return trc;
     }
-    const size_t shmem = (size_t)(W / 32) * kd_piece_bytes(XB) * (p->nearfield ? 2 : 1) + 16;      // + the item slot
+    const size_t shmem = (size_t)(W / 32) * K::piece_bytes * (p->nearfield ? 2 : 1) + 16;   // + the item slot
     if (p->nearfield) {
-        auto k = kirch_dquad_kernel<XB, true, 1, SH, 1>;
+        auto k = K::near_kernel();
         IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
         hipLaunchKernelGGL(k, dim3(nblk), dim3(KF_THREADS), shmem, st, P, W);
-    } else {
-        auto k = kirch_dquad_kernel<XB, false, (NH > 1 ? 4 : 2), SH, NH>;
-        IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        int grid = nblk;
-        if (P.tilemap) {
-            if (p->slots <= 0) {        // resident workgroups of this plan's kernel on this device: asked once
-                int per_cu = 0, ncu = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, KF_THREADS * NH, shmem) == hipSuccess &&
-                    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->ctx->device) == hipSuccess &&
-                    per_cu > 0 && ncu > 0)
-                    p->slots = per_cu * ncu;
-                else
-                    (void)hipGetLastError();
-            }
-            // many-rank plans: every walk in 2 or 4 pieces with partial images of their own (p->walk_parts_log2)
-            const int pl2 = NH == 1 ? p->walk_parts_log2 : 0;
-            const size_t nout = (size_t)P.snum * P.ldo, esz = impdar_dtype_size(p->dtype);
-            const bool pieces = pl2 > 0 && p->slots > 0 && p->d_partial.ensure((nout << pl2) * esz) == hipSuccess;
-            if (p->slots > 0 && (p->slots < nblk || pieces) && p->d_queue.ensure(8 * 64) == hipSuccess) {
-                IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_queue.p, 0, 8 * 64, st));
-                P.queue = p->d_queue.as<int>();
-                if (pieces) {
-                    P.parts_log2 = pl2;
-                    P.partial = p->d_partial.p;
-                    P.part_stride = nout;
-                    // a piece no workgroup reaches (tiles beyond the block's end) must read as zero
-                    IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_partial.p, 0, (nout << pl2) * esz, st));
-                }
-                grid = (int)std::min<long long>(std::max(p->slots - kirch_reserved_slots(p), 1), (long long)nblk << P.parts_log2);
-            }
+        IMPDAR_HIP_CHECK(hipGetLastError());
+        return IMPDAR_OK;
+    }
+    auto k = K::far_kernel();
+    IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    int grid = nblk;
+    if (P.tilemap) {
+        // persistent workgroups: as many as are resident at once, each pulling items from the per-XCD queues
+        if (p->slots <= 0) {        // resident workgroups of this plan's kernel on this device: asked once
+            int per_cu = 0, ncu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k, KF_THREADS * NH, shmem) == hipSuccess &&
+                hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->ctx->device) == hipSuccess &&
+                per_cu > 0 && ncu > 0)
+                p->slots = per_cu * ncu;
+            else
+                (void)hipGetLastError();
         }
-        hipLaunchKernelGGL(k, dim3(grid), dim3(KF_THREADS * NH), shmem, st, P, W);
-        if (P.parts_log2) {
-            const size_t nout = (size_t)P.snum * P.ldo;
-            const dim3 cg((unsigned)((nout + 255) / 256));
-            if (p->dtype == IMPDAR_F32) {
-                if (P.parts_log2 == 2)
-                    hipLaunchKernelGGL((kirch_combine_kernel<float, 4>), cg, dim3(256), 0, st, (const float *)P.partial, (float *)P.out, nout);
-                else
-                    hipLaunchKernelGGL((kirch_combine_kernel<float, 2>), cg, dim3(256), 0, st, (const float *)P.partial, (float *)P.out, nout);
-            } else {
-                if (P.parts_log2 == 2)
-                    hipLaunchKernelGGL((kirch_combine_kernel<double, 4>), cg, dim3(256), 0, st, (const double *)P.partial, (double *)P.out, nout);
-                else
-                    hipLaunchKernelGGL((kirch_combine_kernel<double, 2>), cg, dim3(256), 0, st, (const double *)P.partial, (double *)P.out, nout);
+        // many-rank plans: every walk in 2 or 4 pieces with partial images of their own (p->walk_parts_log2)
+        const int pl2 = NH == 1 ? p->walk_parts_log2 : 0;
+        const size_t nout = (size_t)P.snum * P.ldo, esz = impdar_dtype_size(p->dtype);
+        const bool pieces = pl2 > 0 && p->slots > 0 && p->d_partial.ensure((nout << pl2) * esz) == hipSuccess;
+        if (p->slots > 0 && (p->slots < nblk || pieces) && p->d_queue.ensure(8 * 64) == hipSuccess) {
+            IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_queue.p, 0, 8 * 64, st));
+            P.queue = p->d_queue.as<int>();
+            if (pieces) {
+                P.parts_log2 = pl2;
+                P.partial = p->d_partial.p;
+                P.part_stride = nout;
+                // a piece no workgroup reaches (tiles beyond the block's end) must read as zero
+                IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_partial.p, 0, (nout << pl2) * esz, st));
             }
+            grid = (int)std::min<long long>(std::max(p->slots - kirch_reserved_slots(p), 1), (long long)nblk << P.parts_log2);
         }
     }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(KF_THREADS * NH), shmem, st, P, W);
+    if (P.parts_log2 && p->dtype == IMPDAR_F32) kirch_launch_combine<float>(P, st);
+    if (P.parts_log2 && p->dtype != IMPDAR_F32) kirch_launch_combine<double>(P, st);
     IMPDAR_HIP_CHECK(hipGetLastError());
     return IMPDAR_OK;
 }
@@ -2612,6 +2205,183 @@ static int launch_tab(impdar_kirch_plan *p, const FastParams &P0, int nx, hipStr
     return IMPDAR_OK;
 }
 
+// the LDS-ring kernels: quad, dquad and tab, by the plan's route
+static int migrate_ring(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st)
+{
+    const int b = p->buf, nx = xhi - xlo;
+    FastParams P;
+    P.GT = reinterpret_cast<const float *>(img_row0(p, p->GT[b]));
+    P.DT = p->nearfield ? reinterpret_cast<const float *>(img_row0(p, p->DT[b])) : nullptr;
+    P.out = reinterpret_cast<float *>(d_out);
+    P.ldo = nx;
+    P.snum = p->snum;
+    P.tnum = p->tnum;
+    P.xlo = xlo;
+    P.xhi = xhi;
+    P.hmax = p->d_hmax.as<int>();
+    P.klo = p->d_klo.as<int>();
+    P.khi = p->d_khi.as<int>();
+    P.nb = p->nb;
+    P.zero_row = p->tnum_pad;          // first zero row after the data rows
+    P.nchunks = p->nchunks;
+    P.TK = p->d_TK[b].as<unsigned short>();
+    P.TW = p->d_TW[b].as<float>();
+    P.TW2 = p->d_TW2[b].as<float>();
+    P.ntab = p->ntab;
+    P.c1 = p->d_c1.as<float>();
+    P.c2 = p->d_c2.as<float>();
+    P.fin = p->d_fin.as<float>();
+    P.c1d = p->d_c1d.as<double>();
+    P.c2d = p->d_c2d.as<double>();
+    P.find = p->d_find.as<double>();
+    P.TKB = p->d_TK[b].p;
+    P.WIN = p->d_WIN.as<int2>();
+    P.nrows = p->nrows;
+    P.mrow0 = p->mrow0;
+    P.tilemap = nullptr;
+    P.queue = nullptr;
+    P.parts_log2 = 0;
+    P.partial = nullptr;
+    P.part_stride = 0;
+    if (p->dquad && p->nh == 2 && p->quadSH == 4)
+        return p->xb == 20 ? launch_ring<RingF64<20, 4, 2>>(p, P, st) : launch_ring<RingF64<16, 4, 2>>(p, P, st);
+    if (p->dquad)
+        return p->quadSH == 0 ? (p->xb == 20 ? launch_ring<RingF64<20, 0>>(p, P, st) : launch_ring<RingF64<16, 0>>(p, P, st))
+                              : (p->xb == 20 ? launch_ring<RingF64<20, 4>>(p, P, st) : launch_ring<RingF64<16, 4>>(p, P, st));
+    if (p->quad && p->quadSH == 0)
+        return p->xb == 40 ? launch_ring<RingF32<40, 2, 0>>(p, P, st)
+               : p->xb == 32 ? launch_ring<RingF32<32, 2, 0>>(p, P, st)
+                             : launch_ring<RingF32<24, 3, 0>>(p, P, st);
+    if (p->quad && p->nh == 2 && p->xb == 32)
+        return launch_ring<RingF32<32, 4, 4, 2, 0>>(p, P, st);      // 70 KB of LDS: two workgroups of 8 waves per CU
+    if (p->quad && p->nh == 2 && p->xb == 40)
+        return p->lk ? launch_ring<RingF32<40, 2, 4, 2, 1>>(p, P, st) : launch_ring<RingF32<40, 2, 4, 2, 0>>(p, P, st);
+    if (p->quad && p->nh == 3 && p->xb == 40)
+        return p->lk ? launch_ring<RingF32<40, 3, 4, 3, 1>>(p, P, st) : launch_ring<RingF32<40, 3, 4, 3, 0>>(p, P, st);
+    if (p->quad)
+        return p->xb == 40 ? launch_ring<RingF32<40, 2, 4>>(p, P, st)
+               : p->xb == 32 ? launch_ring<RingF32<32, 2, 4>>(p, P, st)
+                             : launch_ring<RingF32<24, 2, 4>>(p, P, st);      // steep moveout: two workgroups per CU
+    return launch_tab<16, 4, 4>(p, P, nx, st);
+}
+
+// the float64 pick / weight tables of kirch_exact_tab_kernel, built at the first migrate
+static int build_exact_tables(impdar_kirch_plan *p, hipStream_t st)
+{
+    const int nch = (p->snum + 255) / 256;
+    int hg = 0;
+    std::vector<int> hm(nch, 0);
+    for (int k = 0; k < p->snum; ++k) {
+        hm[k / 256] = std::max(hm[k / 256], p->h_half[k] + 1);
+        hg = std::max(hg, p->h_half[k] + 1);
+    }
+    hg = std::min(hg, p->tnum) + 1;
+    const size_t ent = (size_t)hg * p->snum;
+    if (p->d_XK.ensure(ent * 4) != hipSuccess || p->d_XW.ensure(ent * 8) != hipSuccess ||
+        (p->nearfield && p->d_XW2.ensure(ent * 8) != hipSuccess) || p->d_xhmax.ensure((size_t)nch * 4) != hipSuccess) {
+        impdar_set_error("hipMalloc of the %zu-entry exact pick/weight table failed", ent);
+        return IMPDAR_ERR_HIP;
+    }
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(p->d_xhmax.p, hm.data(), (size_t)nch * 4, hipMemcpyHostToDevice, st));
+    IMPDAR_HIP_CHECK(hipStreamSynchronize(st));          // hm is a stack vector
+    TableXParams T;
+    T.XK = p->d_XK.as<int>();
+    T.XW = p->d_XW.as<double>();
+    T.XW2 = p->d_XW2.as<double>();
+    kirch_fill_axes(T, p);
+    T.dx = p->dx;
+    T.ntab = hg;
+    T.near = p->nearfield;
+    hipLaunchKernelGGL(kirch_tablex_kernel, dim3(nch, hg), dim3(256), 0, st, T);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    p->xntab = hg;
+    p->xtab_ready = true;
+    return IMPDAR_OK;
+}
+
+// exact arithmetic on uniform grids: tabulated fp64 picks / weights, one gather + FMA per pair
+static int migrate_exact_tab(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st)
+{
+    int rc;
+    if (!p->xtab_ready && (rc = build_exact_tables(p, st))) return rc;
+    ExactTabParams P;
+    kirch_fill_io(P, p, d_out, xlo, xhi);
+    P.XK = p->d_XK.as<int>();
+    P.XW = p->d_XW.as<double>();
+    P.XW2 = p->d_XW2.as<double>();
+    P.hmax = p->d_xhmax.as<int>();
+    P.ntab = p->xntab;
+#ifndef KX_XE
+#define KX_XE 16
+#endif
+    constexpr int XE = KX_XE;
+    dim3 grid((p->snum + 255) / 256, (xhi - xlo + XE - 1) / XE);
+    if (p->dtype == IMPDAR_F32) {
+        if (p->nearfield)
+            hipLaunchKernelGGL((kirch_exact_tab_kernel<float, true, XE>), grid, dim3(256), 0, st, P);
+        else
+            hipLaunchKernelGGL((kirch_exact_tab_kernel<float, false, XE>), grid, dim3(256), 0, st, P);
+    } else {
+        if (p->nearfield)
+            hipLaunchKernelGGL((kirch_exact_tab_kernel<double, true, XE>), grid, dim3(256), 0, st, P);
+        else
+            hipLaunchKernelGGL((kirch_exact_tab_kernel<double, false, XE>), grid, dim3(256), 0, st, P);
+    }
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
+}
+
+// the reference's arithmetic pair by pair: any geometry
+static int migrate_exact_pair(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st)
+{
+    ExactParams P;
+    kirch_fill_io(P, p, d_out, xlo, xhi);
+    kirch_fill_axes(P, p);
+    P.dist = p->d_dist.as<double>();
+    const double rlim = p->vel * p->tmax / 2.0;
+    P.r2lim = rlim * rlim * (1.0 + 1e-9);
+    P.dist_sorted = p->dist_sorted ? 1 : 0;
+    dim3 grid((p->snum + 255) / 256, xhi - xlo);
+    if (p->dtype == IMPDAR_F32) {
+        if (p->nearfield)
+            hipLaunchKernelGGL((kirch_exact_kernel<float, true>), grid, dim3(256), 0, st, P);
+        else
+            hipLaunchKernelGGL((kirch_exact_kernel<float, false>), grid, dim3(256), 0, st, P);
+    } else {
+        if (p->nearfield)
+            hipLaunchKernelGGL((kirch_exact_kernel<double, true>), grid, dim3(256), 0, st, P);
+        else
+            hipLaunchKernelGGL((kirch_exact_kernel<double, false>), grid, dim3(256), 0, st, P);
+    }
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
+}
+
+// the (sample, offset) entries whose pick rounding noise decides, pair by pair (kirch_tiefix_kernel)
+static int migrate_tiefix(impdar_kirch_plan *p, int kern, void *d_out, int xlo, int xhi, hipStream_t st)
+{
+    TieFixParams F;
+    kirch_fill_io(F, p, d_out, xlo, xhi);
+    kirch_fill_axes(F, p);
+    F.grp = kern == IMPDAR_KERNEL_QUAD ? 8 : (kern == IMPDAR_KERNEL_DQUAD ? 4 : 0);
+    F.near = p->nearfield;
+    F.dist = p->d_dist.as<double>();
+    F.dx = p->dx;
+    F.g_ti = p->d_tie_ti.as<int>();
+    F.g_off = p->d_tie_off.as<int>();
+    F.g_n = p->d_tie_n.as<int>();
+    const bool xtab = kern == IMPDAR_KERNEL_EXACT_TAB;
+    F.hmax = xtab ? p->d_xhmax.as<int>() : p->d_hmax.as<int>();
+    F.nmax = xtab ? p->xntab : p->ntab - 1;
+    const dim3 grid((xhi - xlo + 255) / 256, p->ntie_groups);
+    if (p->dtype == IMPDAR_F32)
+        hipLaunchKernelGGL(kirch_tiefix_kernel<float>, grid, dim3(256), 0, st, F);
+    else
+        hipLaunchKernelGGL(kirch_tiefix_kernel<double>, grid, dim3(256), 0, st, F);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return IMPDAR_OK;
+}
+
 extern "C" int impdar_kirch_migrate(impdar_kirch_plan *p, void *d_out, int xlo, int xhi)
 {
     IMPDAR_ARG_CHECK(p && d_out, "null plan/output");
@@ -2623,209 +2393,17 @@ extern "C" int impdar_kirch_migrate(impdar_kirch_plan *p, void *d_out, int xlo, 
     const int b = p->buf;
     IMPDAR_HIP_CHECK(hipStreamWaitEvent(st, p->ev_ready[b], 0));      // image + table of this radargram
     if (!p->haves[p->slot][2]) IMPDAR_HIP_CHECK(hipEventRecord(ev[4], st));
-    const int nx = xhi - xlo;
-    if (nx > 0 && p->gen) {
-        const int grc = kirch_launch_gen(p, d_out, xlo, xhi, st);
-        if (grc) return grc;
-    } else if (nx > 0 && (p->mode == IMPDAR_KIRCH_FAST || p->dquad)) {
-        FastParams P;
-        P.GT = reinterpret_cast<const float *>(img_row0(p, p->GT[b]));
-        P.DT = p->nearfield ? reinterpret_cast<const float *>(img_row0(p, p->DT[b])) : nullptr;
-        P.out = reinterpret_cast<float *>(d_out);
-        P.ldo = nx;
-        P.snum = p->snum;
-        P.tnum = p->tnum;
-        P.xlo = xlo;
-        P.xhi = xhi;
-        P.hmax = p->d_hmax.as<int>();
-        P.klo = p->d_klo.as<int>();
-        P.khi = p->d_khi.as<int>();
-        P.nb = p->nb;
-        P.zero_row = p->tnum_pad;          // first zero row after the data rows
-        P.nchunks = p->nchunks;
-        P.TK = p->d_TK[b].as<unsigned short>();
-        P.TW = p->d_TW[b].as<float>();
-        P.TW2 = p->d_TW2[b].as<float>();
-        P.ntab = p->ntab;
-        P.c1 = p->d_c1.as<float>();
-        P.c2 = p->d_c2.as<float>();
-        P.fin = p->d_fin.as<float>();
-        P.c1d = p->d_c1d.as<double>();
-        P.c2d = p->d_c2d.as<double>();
-        P.find = p->d_find.as<double>();
-        P.TKB = p->d_TK[b].p;
-        P.WIN = p->d_WIN.as<int2>();
-        P.nrows = p->nrows;
-        P.mrow0 = p->mrow0;
-        P.tilemap = nullptr;
-        P.queue = nullptr;
-        P.parts_log2 = 0;
-        P.partial = nullptr;
-        P.part_stride = 0;
-        int rc;
-        if (p->dquad && p->nh == 2 && p->quadSH == 4)
-            rc = p->xb == 20 ? launch_dquad<20, 4, 2>(p, P, st) : launch_dquad<16, 4, 2>(p, P, st);
-        else if (p->dquad)
-            rc = p->quadSH == 0 ? (p->xb == 20 ? launch_dquad<20, 0>(p, P, st) : launch_dquad<16, 0>(p, P, st))
-                                : (p->xb == 20 ? launch_dquad<20, 4>(p, P, st) : launch_dquad<16, 4>(p, P, st));
-        else if (p->quad && p->quadSH == 0)
-            rc = p->xb == 40 ? launch_quad<40, 2, 0>(p, P, nx, st)
-                 : p->xb == 32 ? launch_quad<32, 2, 0>(p, P, nx, st)
-                               : launch_quad<24, 3, 0>(p, P, nx, st);
-        else if (p->quad && p->nh == 2 && p->xb == 32)
-            rc = launch_quad<32, 4, 4, 2, 0>(p, P, nx, st);      // 70 KB of LDS: two workgroups of 8 waves per CU
-        else if (p->quad && p->nh == 2 && p->xb == 40)
-            rc = p->lk ? launch_quad<40, 2, 4, 2, 1>(p, P, nx, st) : launch_quad<40, 2, 4, 2, 0>(p, P, nx, st);
-        else if (p->quad && p->nh == 3 && p->xb == 40)
-            rc = p->lk ? launch_quad<40, 3, 4, 3, 1>(p, P, nx, st) : launch_quad<40, 3, 4, 3, 0>(p, P, nx, st);
-        else if (p->quad)
-            rc = p->xb == 40 ? launch_quad<40, 2, 4>(p, P, nx, st)
-                 : p->xb == 32 ? launch_quad<32, 2, 4>(p, P, nx, st)
-                             : launch_quad<24, 2, 4>(p, P, nx, st);      // steep moveout: two workgroups per CU
-        else
-            rc = launch_tab<16, 4, 4>(p, P, nx, st);
+    const int kern = p->kernel();
+    if (xhi > xlo) {
+        const int rc = kern == IMPDAR_KERNEL_GEN          ? kirch_launch_gen(p, d_out, xlo, xhi, st)
+                       : kern == IMPDAR_KERNEL_EXACT_TAB  ? migrate_exact_tab(p, d_out, xlo, xhi, st)
+                       : kern == IMPDAR_KERNEL_EXACT_PAIR ? migrate_exact_pair(p, d_out, xlo, xhi, st)
+                                                          : migrate_ring(p, d_out, xlo, xhi, st);
         if (rc) return rc;
-    } else if (nx > 0 && p->uniform && !p->xtab_off && !(getenv("IMPDAR_KIRCH_EXACT_IMPL") &&
-                                                          !strcmp(getenv("IMPDAR_KIRCH_EXACT_IMPL"), "pair"))) {
-        // exact arithmetic on uniform grids: tabulated fp64 picks / weights, one gather + FMA per pair
-        const int nch = (p->snum + 255) / 256;
-        if (!p->xtab_ready) {
-            int hg = 0;
-            std::vector<int> hm(nch, 0);
-            for (int k = 0; k < p->snum; ++k) {
-                hm[k / 256] = std::max(hm[k / 256], p->h_half[k] + 1);
-                hg = std::max(hg, p->h_half[k] + 1);
-            }
-            hg = std::min(hg, p->tnum) + 1;
-            const size_t ent = (size_t)hg * p->snum;
-            if (p->d_XK.ensure(ent * 4) != hipSuccess || p->d_XW.ensure(ent * 8) != hipSuccess ||
-                (p->nearfield && p->d_XW2.ensure(ent * 8) != hipSuccess) || p->d_xhmax.ensure((size_t)nch * 4) != hipSuccess) {
-                impdar_set_error("hipMalloc of the %zu-entry exact pick/weight table failed", ent);
-                return IMPDAR_ERR_HIP;
-            }
-            IMPDAR_HIP_CHECK(hipMemcpyAsync(p->d_xhmax.p, hm.data(), (size_t)nch * 4, hipMemcpyHostToDevice, st));
-            IMPDAR_HIP_CHECK(hipStreamSynchronize(st));          // hm is a stack vector
-            TableXParams T;
-            T.XK = p->d_XK.as<int>();
-            T.XW = p->d_XW.as<double>();
-            T.XW2 = p->d_XW2.as<double>();
-            T.zs = p->d_zs.as<double>();
-            T.zs2 = p->d_zs2.as<double>();
-            T.tt = p->d_tt.as<double>();
-            T.dx = p->dx;
-            T.vel = p->vel;
-            T.tmax = p->tmax;
-            T.inv_dt = 1.0 / p->dt;
-            T.tt0 = p->tt0;
-            T.snum = p->snum;
-            T.ntab = hg;
-            T.near = p->nearfield;
-            hipLaunchKernelGGL(kirch_tablex_kernel, dim3(nch, hg), dim3(256), 0, st, T);
-            IMPDAR_HIP_CHECK(hipGetLastError());
-            p->xntab = hg;
-            p->xtab_ready = true;
+        if (p->ntie_groups > 0 && kern != IMPDAR_KERNEL_EXACT_PAIR) {
+            const int frc = migrate_tiefix(p, kern, d_out, xlo, xhi, st);
+            if (frc) return frc;
         }
-        ExactTabParams P;
-        P.GT = img_row0(p, p->GT[b]);
-        P.DT = p->nearfield ? img_row0(p, p->DT[b]) : nullptr;
-        P.out = d_out;
-        P.ldo = nx;
-        P.snum = p->snum;
-        P.tnum = p->tnum;
-        P.xlo = xlo;
-        P.xhi = xhi;
-        P.XK = p->d_XK.as<int>();
-        P.XW = p->d_XW.as<double>();
-        P.XW2 = p->d_XW2.as<double>();
-        P.hmax = p->d_xhmax.as<int>();
-        P.ntab = p->xntab;
-#ifndef KX_XE
-#define KX_XE 16
-#endif
-        constexpr int XE = KX_XE;
-        dim3 grid(nch, (nx + XE - 1) / XE);
-        if (p->dtype == IMPDAR_F32) {
-            if (p->nearfield)
-                hipLaunchKernelGGL((kirch_exact_tab_kernel<float, true, XE>), grid, dim3(256), 0, st, P);
-            else
-                hipLaunchKernelGGL((kirch_exact_tab_kernel<float, false, XE>), grid, dim3(256), 0, st, P);
-        } else {
-            if (p->nearfield)
-                hipLaunchKernelGGL((kirch_exact_tab_kernel<double, true, XE>), grid, dim3(256), 0, st, P);
-            else
-                hipLaunchKernelGGL((kirch_exact_tab_kernel<double, false, XE>), grid, dim3(256), 0, st, P);
-        }
-        IMPDAR_HIP_CHECK(hipGetLastError());
-    } else if (nx > 0) {
-        ExactParams P;
-        P.GT = img_row0(p, p->GT[b]);
-        P.DT = p->nearfield ? img_row0(p, p->DT[b]) : nullptr;
-        P.out = d_out;
-        P.ldo = nx;
-        P.snum = p->snum;
-        P.tnum = p->tnum;
-        P.xlo = xlo;
-        P.xhi = xhi;
-        P.dist = p->d_dist.as<double>();
-        P.zs = p->d_zs.as<double>();
-        P.zs2 = p->d_zs2.as<double>();
-        P.tt = p->d_tt.as<double>();
-        P.vel = p->vel;
-        P.tmax = p->tmax;
-        const double rlim = p->vel * p->tmax / 2.0;
-        P.r2lim = rlim * rlim * (1.0 + 1e-9);
-        P.inv_dt = 1.0 / p->dt;
-        P.tt0 = p->tt0;
-        P.dist_sorted = p->dist_sorted ? 1 : 0;
-        dim3 grid((p->snum + 255) / 256, nx);
-        if (p->dtype == IMPDAR_F32) {
-            if (p->nearfield)
-                hipLaunchKernelGGL((kirch_exact_kernel<float, true>), grid, dim3(256), 0, st, P);
-            else
-                hipLaunchKernelGGL((kirch_exact_kernel<float, false>), grid, dim3(256), 0, st, P);
-        } else {
-            if (p->nearfield)
-                hipLaunchKernelGGL((kirch_exact_kernel<double, true>), grid, dim3(256), 0, st, P);
-            else
-                hipLaunchKernelGGL((kirch_exact_kernel<double, false>), grid, dim3(256), 0, st, P);
-        }
-        IMPDAR_HIP_CHECK(hipGetLastError());
-    }
-    if (nx > 0 && p->ntie_groups > 0 && impdar_kirch_plan_kernel(p) != IMPDAR_KERNEL_EXACT_PAIR) {
-        // the (sample, offset) entries whose pick rounding noise decides, pair by pair (kirch_tiefix_kernel)
-        const int kern = impdar_kirch_plan_kernel(p);
-        TieFixParams F;
-        F.GT = img_row0(p, p->GT[b]);
-        F.DT = p->nearfield ? img_row0(p, p->DT[b]) : nullptr;
-        F.out = d_out;
-        F.ldo = nx;
-        F.snum = p->snum;
-        F.tnum = p->tnum;
-        F.xlo = xlo;
-        F.xhi = xhi;
-        F.grp = kern == IMPDAR_KERNEL_QUAD ? 8 : (kern == IMPDAR_KERNEL_DQUAD ? 4 : 0);
-        F.near = p->nearfield;
-        F.dist = p->d_dist.as<double>();
-        F.zs = p->d_zs.as<double>();
-        F.zs2 = p->d_zs2.as<double>();
-        F.tt = p->d_tt.as<double>();
-        F.dx = p->dx;
-        F.vel = p->vel;
-        F.tmax = p->tmax;
-        F.inv_dt = 1.0 / p->dt;
-        F.tt0 = p->tt0;
-        F.g_ti = p->d_tie_ti.as<int>();
-        F.g_off = p->d_tie_off.as<int>();
-        F.g_n = p->d_tie_n.as<int>();
-        const bool xtab = kern == IMPDAR_KERNEL_EXACT_TAB;
-        F.hmax = xtab ? p->d_xhmax.as<int>() : p->d_hmax.as<int>();
-        F.nmax = xtab ? p->xntab : p->ntab - 1;
-        const dim3 grid((nx + 255) / 256, p->ntie_groups);
-        if (p->dtype == IMPDAR_F32)
-            hipLaunchKernelGGL(kirch_tiefix_kernel<float>, grid, dim3(256), 0, st, F);
-        else
-            hipLaunchKernelGGL(kirch_tiefix_kernel<double>, grid, dim3(256), 0, st, F);
-        IMPDAR_HIP_CHECK(hipGetLastError());
     }
     IMPDAR_HIP_CHECK(hipEventRecord(ev[5], st));
     IMPDAR_HIP_CHECK(hipEventRecord(p->ev_free[b], st));
@@ -2968,7 +2546,7 @@ struct KirchOneShot {
     int dtype = -1, snum = 0, tnum = 0, nearfield = 0, grad_uniform = 0, mode = 0;
     double vel = 0, grad_h = 0;
     std::vector<double> dist, tt, ga, gb, gc;
-    std::string knobs;       // the IMPDAR_KIRCH_* settings the plan was built under
+    KirchKnobs knobs;        // the IMPDAR_KIRCH_* settings the plan was built under
     void drop()
     {
         if (plan) impdar_kirch_plan_destroy(plan);
@@ -2985,20 +2563,6 @@ struct KirchOneShot {
 std::mutex g_k1_mu;
 KirchOneShot *g_k1 = nullptr;
 thread_local bool t_k1_busy = false, t_hook_busy = false;     // this thread is inside impdar_kirchhoff / mig_kirch_loop
-
-std::string kirch_knobs()
-{
-    static const char *names[] = {"IMPDAR_KIRCH_EXACT_IMPL", "IMPDAR_KIRCH_IMPL", "IMPDAR_KIRCH_LK", "IMPDAR_KIRCH_NH",
-                                  "IMPDAR_KIRCH_NHD", "IMPDAR_KIRCH_PARTS", "IMPDAR_KIRCH_TIEFIX", "IMPDAR_KIRCH_XB",
-                                  "IMPDAR_KIRCH_XBD", "IMPDAR_KIRCH_MODE"};
-    std::string k;
-    for (const char *n : names) {
-        const char *v = getenv(n);
-        k += v ? v : "";
-        k += ';';
-    }
-    return k;
-}
 
 bool same_vec(const std::vector<double> &have, const double *p, size_t n)
 {
@@ -3035,7 +2599,7 @@ extern "C" int impdar_kirchhoff(impdar_ctx *ctx, const void *data, int dtype, in
     KirchOneShot &c = *g_k1;
     const char *ce = getenv("IMPDAR_KIRCH_ONESHOT_CACHE");
     const bool keep = !(ce && ce[0] == '0');
-    const std::string knobs = kirch_knobs();
+    const KirchKnobs knobs = KirchKnobs::from_env();
     const bool hit = c.plan && c.owner == ctx && c.dtype == dtype && c.snum == snum && c.tnum == tnum && c.vel == vel &&
                      c.nearfield == nearfield && c.grad_uniform == grad_uniform && c.grad_h == grad_h && c.mode == mode &&
                      dist_m && tt_sec && same_vec(c.dist, dist_m, (size_t)tnum) && same_vec(c.tt, tt_sec, (size_t)snum) &&
@@ -3044,8 +2608,8 @@ extern "C" int impdar_kirchhoff(impdar_ctx *ctx, const void *data, int dtype, in
     int rc;
     if (!hit) {
         c.drop();
-        if ((rc = impdar_kirch_plan_create(ctx, dtype, snum, tnum, dist_m, tt_sec, vel, nearfield, grad_uniform, grad_h,
-                                           ga, gb, gc, mode, 1, &c.plan))) {
+        if ((rc = kirch_plan_create_impl(ctx, dtype, snum, tnum, dist_m, tt_sec, vel, nearfield, grad_uniform, grad_h,
+                                         ga, gb, gc, mode, 1, knobs, nullptr, &c.plan))) {
             c.plan = nullptr;
             return rc;
         }
@@ -3220,7 +2784,7 @@ struct KirchHook {
     double vel = 0, tmax = 0;
     bool standard = false;
     std::vector<double> dist, tt, zs, zs2;
-    std::string knobs;
+    KirchKnobs knobs;
     void drop()
     {
         if (plan) impdar_kirch_plan_destroy(plan);
@@ -3276,32 +2840,18 @@ extern "C" void mig_kirch_loop(double *migdata, int tnum, int snum, double *dist
         standard = standard && zs[k] == vel * tt_sec[k] / 2.0 && zs2[k] == zs[k] * zs[k];     // mig_python.py:101-102
     }
     standard = standard && std::fabs(max_travel_time - ttmax) <= 1e-6 * std::fabs(ttmax);
-    const std::string knobs = kirch_knobs();
+    const KirchKnobs knobs = KirchKnobs::from_env();
     const bool hit = c.plan && c.snum == snum && c.tnum == tnum && c.vel == vel && c.tmax == max_travel_time &&
                      c.standard == standard && same_vec(c.dist, dist, (size_t)tnum) && same_vec(c.tt, tt_sec, (size_t)snum) &&
                      same_vec(c.zs, zs, (size_t)snum) && same_vec(c.zs2, zs2, (size_t)snum) && c.knobs == knobs;
     if (!hit) {
         c.drop();
-        g_tmax_override = standard ? &max_travel_time : nullptr;
-        const int rc = impdar_kirch_plan_create(ctx, IMPDAR_F64, snum, tnum, dist, tt_sec, vel, 0, 1, 1.0, nullptr, nullptr,
-                                                nullptr, IMPDAR_KIRCH_EXACT, 1, &c.plan);
-        g_tmax_override = nullptr;
-        if (rc) {
+        // (the caller's own tables: per-pair kernel -- the table-driven ones derive picks and apertures from the plan's tables)
+        const KirchCallerTables own{max_travel_time, zs, zs2, standard};
+        if (kirch_plan_create_impl(ctx, IMPDAR_F64, snum, tnum, dist, tt_sec, vel, 0, 1, 1.0, nullptr, nullptr, nullptr,
+                                   IMPDAR_KIRCH_EXACT, 1, knobs, &own, &c.plan)) {
             c.plan = nullptr;
             return fail(impdar_last_error());
-        }
-        if (!standard) {
-            // the caller's own tables: per-pair kernel (the table-driven ones derive picks and apertures from the
-            // plan's tables)
-            c.plan->tmax = max_travel_time;
-            c.plan->xtab_off = true;
-            c.plan->dquad = false;
-            c.plan->ntie_groups = 0;
-            if (hipMemcpy(c.plan->d_zs.p, zs, (size_t)snum * 8, hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(c.plan->d_zs2.p, zs2, (size_t)snum * 8, hipMemcpyHostToDevice) != hipSuccess) {
-                c.drop();
-                return fail("upload of the depth tables failed");
-            }
         }
         c.snum = snum, c.tnum = tnum, c.vel = vel, c.tmax = max_travel_time, c.standard = standard;
         c.dist.assign(dist, dist + tnum);

@@ -126,7 +126,8 @@ int impdar_kirchhoff(impdar_ctx *ctx, const void *data, int dtype, int snum, int
  * one; the first prep after a migrate starts a new radargram (switches buffer set).  prep waits
  * (on the device) for whatever the *_dev entry points and impdar_dev_memset have enqueued on the
  * compute stream before it, so a resident chain filter -> prep needs no host synchronisation;
- * impdar_dev_upload is blocking. */
+ * impdar_dev_upload is blocking.  The IMPDAR_KIRCH_* plan knobs are read when the plan is created; prep and
+ * migrate go by what the plan was created under. */
 int impdar_kirch_plan_create(impdar_ctx *ctx, int dtype, int snum, int tnum,
                              const double *dist_m, const double *tt_sec, double vel,
                              int nearfield, int grad_uniform, double grad_h,
