@@ -706,6 +706,92 @@ def main():
                               "cpu_baseline": cb}), flush=True)
         d_x.free()
 
+    if 'quadpol' not in args.skip:
+        # the quad-pol chain at a field acquisition's size, resident: device time per step and for the three together
+        # (host clock around a device synchronise, `reps` calls each: least, median, most), bytes / time against HBM,
+        # and a device copy that moves the same number of bytes, timed the same way
+        import ctypes
+        from impdar_amd import quadpol as qpm
+        n, n_thetas, nrange, ntheta = 19000, 100, 476, 11
+        ctx, lib = _hip.context(), _hip.load()
+        qrng = np.random.default_rng(11)
+        amp = 10. ** (-3. * np.arange(n) / n)
+        shh = amp * (qrng.standard_normal(n) + 1j * qrng.standard_normal(n))
+        svv = shh * np.exp(0.03j * np.arange(n)) + 0.3 * amp * (qrng.standard_normal(n) + 1j * qrng.standard_normal(n))
+        shv = 0.05 * amp * (qrng.standard_normal(n) + 1j * qrng.standard_normal(n) + (2. + 2.j))
+        svh = shv + 0.01 * amp * (qrng.standard_normal(n) + 1j * qrng.standard_normal(n))
+        thetas = np.linspace(0, np.pi, n_thetas)
+        factors = (np.cos(thetas)**2., np.sin(thetas) * np.cos(thetas), np.sin(thetas)**2)
+        grad = qpm.gradient_coefficients(np.arange(n) * 0.21)
+        d_vec = [_hip.DeviceArray.from_host(ctx, v) for v in (shh, shv, svh, svv)]
+
+        def spread(fn, reps=10):
+            fn()
+            ms = []
+            for _ in range(reps):
+                lib.impdar_ctx_sync(ctx)
+                t0 = time.perf_counter()
+                fn()
+                lib.impdar_ctx_sync(ctx)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            ms.sort()
+            return {"min": ms[0], "median": ms[len(ms) // 2], "max": ms[-1]}
+
+        def free(ds):
+            for d in ds:
+                d.free()
+
+        def qp_chain():
+            im = qpm.rotate_dev(d_vec, *factors)
+            c = qpm.coherence_dev(im[0], im[3], nrange, ntheta)
+            g = qpm.phase_gradient_dev(c, grad)
+            lib.impdar_ctx_sync(ctx)
+            free(list(im) + [c, g])
+
+        def qp_copy(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+
+            def call():
+                b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+                lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8))
+                lib.impdar_ctx_sync(ctx)
+                b.free()
+            ms = spread(call)
+            a.free()
+            return ms
+        images = qpm.rotate_dev(d_vec, *factors)
+        d_c = qpm.coherence_dev(images[0], images[3], nrange, ntheta)
+        el = n * n_thetas
+        bytes_of = {"rotation": 4 * n * 16 + 4 * el * 16, "coherence": 3 * el * 16, "phase_gradient": el * 16 + el * 8}
+        def step(make):
+            def call():
+                o = make()
+                lib.impdar_ctx_sync(ctx)
+                free(o if isinstance(o, tuple) else [o])
+            return spread(call)
+        steps = {"rotation": step(lambda: qpm.rotate_dev(d_vec, *factors)),
+                 "coherence": step(lambda: qpm.coherence_dev(images[0], images[3], nrange, ntheta)),
+                 "phase_gradient": step(lambda: qpm.phase_gradient_dev(d_c, grad))}
+        algo = sum(bytes_of.values())
+        whole = spread(qp_chain)
+        cms = qp_copy(algo)
+        print(json.dumps({"path": "quadpol chain %d x %d complex128" % (n, n_thetas),
+                          "config": "nrange %d, ntheta %d, resident" % (nrange, ntheta),
+                          "device_ms": whole["median"], "device_ms_spread": whole,
+                          "steps_ms": steps, "algorithmic_bytes": algo, "algorithmic_bytes_per_step": bytes_of,
+                          "hbm_frac_per_step": {k: bytes_of[k] / steps[k]["median"] / 1e6 / 8000.0 for k in steps},
+                          "copy_same_bytes_ms": cms, "time_over_copy": whole["median"] / cms["median"],
+                          "roofline": {"bound": "hbm", "achieved": algo / whole["median"] / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                       "frac": algo / whole["median"] / 1e6 / 8000.0,
+                                       "note": "time per call (host clock around a device synchronise), with the output "
+                                               "allocations and table uploads; the copy is timed with the same allocation, "
+                                               "synchronise and free.  Bytes: every input read once, every product written "
+                                               "once; the coherence's window sums (32 B per element written and re-read "
+                                               "about 2 nrange / bk + bk times from cache) are not counted"}}), flush=True)
+        free(d_vec + list(images) + [d_c])
+
 
 if __name__ == '__main__':
     main()

@@ -109,12 +109,23 @@ SIGNATURES = {
     'impdar_restack_dev': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'impdar_reverse_dev': (_i, [_p, _p, _i, _i, _i]),
     'impdar_hcrop_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    'impdar_qp_rotate': (_i, [_p, _dp, _dp, _dp, _dp, _i, _dp, _dp, _dp, _i, _dp, _dp, _dp, _dp]),
+    'impdar_qp_rotate_dev': (_i, [_p, _p, _p, _p, _p, _i, _dp, _dp, _dp, _i, _p, _p, _p, _p]),
+    'impdar_qp_coherence': (_i, [_p, _dp, _dp, _i, _i, _i, _i, _i, _dp]),
+    'impdar_qp_coherence_dev': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    'impdar_qp_phase_gradient': (_i, [_p, _dp, _i, _i, _i, _d, _dp, _dp, _dp, _dp, _dp, _i, _dp, _dp]),
+    'impdar_qp_phase_gradient_dev': (_i, [_p, _p, _i, _i, _i, _d, _dp, _dp, _dp, _dp, _dp, _i, _dp, _p]),
     'impdar_comm_unique_id': (_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),
     'impdar_comm_size': (_i, [_p]),
     'impdar_comm_info': (_i, [_p, _ip, _ip, _ip, _ip]),
     'impdar_comm_barrier': (_i, [_p]),
+}
+
+# the reference's native hooks that carry no prefix of this library (mig_kirch_loop is listed above)
+HOOKS = {
+    'coherence2d': (None, [_dp, _dp, _dp, _i, _i, _i, _i]),
 }
 
 
@@ -132,7 +143,7 @@ def load():
             lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
         except OSError as exc:
             raise HipUnavailableError('cannot load %s: %s' % (LIB_PATH, exc))
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(HOOKS.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -177,6 +177,7 @@ void impdar_hpass_forget(impdar_ctx *ctx);         // hpass.hip
 void impdar_vaxis_forget(impdar_ctx *ctx);         // vaxis.hip
 void impdar_gain_forget(impdar_ctx *ctx);          // gain.hip
 void impdar_taxis_forget(impdar_ctx *ctx);         // taxis.hip
+void impdar_quadpol_forget(impdar_ctx *ctx);       // quadpol.hip
 
 void impdar_kirch_trim();    // kirchhoff.hip
 void impdar_stolt_trim();    // stolt.hip
@@ -618,6 +619,7 @@ extern "C" void impdar_ctx_destroy(impdar_ctx *ctx)
     impdar_vaxis_forget(ctx);
     impdar_gain_forget(ctx);
     impdar_taxis_forget(ctx);
+    impdar_quadpol_forget(ctx);
     impdar_devcache_trim(ctx->device);
     pinned_adopt(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);

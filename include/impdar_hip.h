@@ -4,11 +4,13 @@
  * This is the drop-in boundary for the migration hot path of dlilien/ImpDAR
  * (reference paths are relative to the ImpDAR source tree):
  *
- *   - the reference's only native hook is
+ *   - the reference's only native hook of the migrations is
  *       src/impdar/lib/migrationlib/mig_cython.h:11   (mig_kirch_loop)
  *     bound by src/impdar/lib/migrationlib/_mig_cython.pyx:19-20 and selected
  *     in src/impdar/lib/migrationlib/__init__.py:16-19.  That exact symbol is
- *     exported below.
+ *     exported below, and so is its other native hook,
+ *       src/impdar/lib/ApresData/coherence.h:13       (coherence2d)
+ *     bound by src/impdar/lib/ApresData/_coherence.pyx.
  *   - Stolt / phase-shift / T-K have no native hook in the reference; their
  *     boundary is the Python function (mig_python.py:126, :211, :290).  The
  *     impdar_* entry points below are what a ctypes binding of those
@@ -418,6 +420,56 @@ int impdar_restack(impdar_ctx *ctx, const void *data, int dtype, int snum, int t
 int impdar_restack_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int traces, double *d_out);
 int impdar_reverse_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum);
 int impdar_hcrop_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int lo, int hi, void *d_out);
+
+/* ---- quad-polarised ApRES (csrc/quadpol.hip) --------------------------------
+ * The reference's second native hook (src/impdar/lib/ApresData/coherence.h:13,
+ * called at _QuadPolProcessing.py:139-146): the hhvv coherence of two padded
+ * (range_bins, azimuth_bins) complex128 images, written into columns
+ * ntheta ... azimuth_bins - ntheta - 1 of chhvv; the other columns are left as
+ * they are.  Pointers are to (re, im) pairs of doubles, layout-compatible with
+ * `double complex`.  Host arrays, device 0.  On anything it cannot do (no GPU,
+ * a size below 1, a null pointer, no memory) those columns come back NaN and
+ * one line goes to stderr. */
+void coherence2d(double *chhvv, double *HH, double *VV, int nrange, int ntheta,
+                 int range_bins, int azimuth_bins);
+
+/* All arrays complex128 as interleaved (re, im) doubles, row-major.
+ * impdar_qp_rotate: _QuadPolProcessing.py:87-99.  shh, shv, svh, svv: n values;
+ * cos2, sincos, sin2: n_thetas host doubles, cos^2, sin cos and sin^2 of every
+ * azimuth; HH, HV, VH, VV: (n, n_thetas).
+ * impdar_qp_coherence: (:153-165)  chhvv[j, i] = S(HH conj(VV)) /
+ * sqrt(S|HH|^2 S|VV|^2), S over rows [max(0, j - nrange), min(n - 1, j + nrange))
+ * and columns [i - ntheta, i + ntheta) of the (n, ncols) images; a zero
+ * denominator gives NaN in both parts.  wrap != 0: the columns are periodic
+ * over ncols and chhvv is (n, ncols); wrap == 0: the images are already padded,
+ * chhvv is (n, ncols - 2 ntheta) and its column i is centred on input column
+ * i + ntheta.  Every window sum is made of additions only (no differences of
+ * running sums).  nrange >= 1, 1 <= ntheta, and ntheta <= ncols (wrap) or
+ * 2 ntheta < ncols (as given).
+ * impdar_qp_phase_gradient: (:199-216)  dphi_dz = (R dI - I dR) / (R^2 + I^2),
+ * R, I the parts of the (n, m) chhvv, dR, dI their numpy.gradient along the
+ * rows with impdar_kirchhoff's coefficients (grad_uniform, grad_h, ga, gb, gc);
+ * dphi_dz is (n, m) float64.  With b != NULL, R and I first go through
+ * impdar_filtfilt (b, a, zi of ncoef coefficients) along the rows: the
+ * reference's lowpass.
+ * The *_dev forms take device arrays (the tables stay host arrays), enqueue on
+ * the context's compute stream and return without waiting for it. */
+int impdar_qp_rotate(impdar_ctx *ctx, const double *shh, const double *shv, const double *svh, const double *svv, int n,
+                     const double *cos2, const double *sincos, const double *sin2, int n_thetas,
+                     double *HH, double *HV, double *VH, double *VV);
+int impdar_qp_rotate_dev(impdar_ctx *ctx, const double *d_shh, const double *d_shv, const double *d_svh,
+                         const double *d_svv, int n, const double *cos2, const double *sincos, const double *sin2,
+                         int n_thetas, double *d_HH, double *d_HV, double *d_VH, double *d_VV);
+int impdar_qp_coherence(impdar_ctx *ctx, const double *HH, const double *VV, int n, int ncols, int nrange, int ntheta,
+                        int wrap, double *chhvv);
+int impdar_qp_coherence_dev(impdar_ctx *ctx, const double *d_HH, const double *d_VV, int n, int ncols, int nrange,
+                            int ntheta, int wrap, double *d_chhvv);
+int impdar_qp_phase_gradient(impdar_ctx *ctx, const double *chhvv, int n, int m, int grad_uniform, double grad_h,
+                             const double *ga, const double *gb, const double *gc, const double *b, const double *a,
+                             int ncoef, const double *zi, double *dphi_dz);
+int impdar_qp_phase_gradient_dev(impdar_ctx *ctx, const double *d_chhvv, int n, int m, int grad_uniform, double grad_h,
+                                 const double *ga, const double *gb, const double *gc, const double *b, const double *a,
+                                 int ncoef, const double *zi, double *d_dphi_dz);
 
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
