@@ -9,7 +9,8 @@ filters (hbp, lp, hp; float64, as constant_space hands them on) at the same size
 (nmo, pretrigger crop, elev_correct), the gains (rangegain, agc), the trace-axis steps (reverse, hcrop, restack) and
 winavg_hfilt beside a device-to-device copy of equal bytes, and Stolt at the headline radargram's shape (4096 samples x 10000
 traces, no power of two: the library's own mixed-radix row transforms against rocFFT's plans, steady state and the first call
-of a fresh process),
+of a fresh process), and ApRES range conversion and stacking at an unattended deployment's size (40 bursts x 20 chirps x 40001
+samples, float64),
 each through the product path on one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
@@ -58,6 +59,64 @@ def stolt_first_call_child():
                       "finite": bool(np.isfinite(d.data).all())}))
 
 
+APRES = (40, 20, 40001, 2, 4000.)           # bnum, cnum, snum, pad factor, max_range of the "apres range" line
+APRES_HEADER = dict(bandwidth=2.e8, fc=3.e8, chirp_grad=2. * np.pi * 2.e8, ci=3.e8 / np.sqrt(3.18), lambdac=3.e8 / np.sqrt(3.18) / 3.e8)
+
+
+def apres_holder(bnum, cnum, snum, seed=5):
+    """Raw chirps of the "apres range" line: a DC offset, white noise and three tones with a random phase per chirp."""
+    from impdar_amd import apres as apm
+    rng = np.random.default_rng(seed)
+    dat = apm.Apres()
+    dat.bnum, dat.cnum, dat.snum = bnum, cnum, snum
+    t = np.arange(snum)
+    dat.data = 1.25 + 0.3 * rng.standard_normal((bnum, cnum, snum))
+    for f, a in ((0.013, 1.), (0.071, 0.5), (0.19, 0.2)):
+        dat.data += a * np.cos(2 * np.pi * f * t + rng.uniform(-np.pi, np.pi, (bnum, cnum, 1)))
+    for k, v in APRES_HEADER.items():
+        setattr(dat.header, k, v)
+    return dat
+
+
+def apres_first_call_child():
+    """`bench_paths.py --apres-first-call`: a fresh process -- import, context, the FIRST range conversion of the process on host
+    arrays (2 bursts of the line's shape: rocFFT builds its kernels for the row length at run time, whatever the batch), a second
+    for contrast.  One JSON line."""
+    from impdar_amd import _hip, apres as apm
+    bnum, cnum, snum, p, max_range = APRES
+    raw = apres_holder(2, cnum, snum).data
+    _hip.load()
+    _hip.context()
+    walls = []
+    for _ in range(2):
+        dat = apres_holder(2, cnum, snum)
+        dat.data = raw
+        t0 = time.perf_counter()
+        apm.apres_range(dat, p, max_range)
+        walls.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"first_call_ms": walls[0], "second_call_ms": walls[1], "chirps": 2 * cnum,
+                      "finite": bool(np.isfinite(dat.data.view(np.float64)).all())}))
+
+
+def apres_first_call():
+    """The first-call child of the "apres range" line against an empty rocFFT kernel database, then one against the database it left."""
+    import os
+    import subprocess
+    import tempfile
+    recs = []
+    with tempfile.TemporaryDirectory() as tmp:
+        env = dict(os.environ, HOME=tmp, XDG_CACHE_HOME=os.path.join(tmp, 'xdg'), ROCFFT_RTC_CACHE_PATH=os.path.join(tmp, 'rocfft_kernel_cache.db'))
+        for _ in range(2):
+            try:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), '--apres-first-call'], capture_output=True, text=True,
+                                   timeout=240, env=env)
+                line = [l for l in r.stdout.splitlines() if l.startswith('{"first_call_ms"')]
+                recs.append(json.loads(line[-1]) if line else {"error": (r.stderr or r.stdout)[-300:]})
+            except Exception as exc:
+                recs.append({"error": "%s: %s" % (type(exc).__name__, exc)})
+    return {"cold": recs[0], "warm_cache": recs[1]}
+
+
 def stolt_first_calls(children=3):
     """The first-call children of the "stolt 4096 x 10000" line, started before this process touches the GPU.  Per form
     (the default route: the own mixed-radix transforms; IMPDAR_STOLT_FFT=rocfft: the plans) one process against an empty rocFFT
@@ -91,6 +150,7 @@ def stolt_first_calls(children=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--stolt-first-call', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--apres-first-call', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--stolt', type=int, default=4096)
     ap.add_argument('--phsh', type=int, default=8192)
     ap.add_argument('--chain', type=str, default='4096x10000', help='snum x tnum of the band-pass / re-spacing lines')
@@ -100,7 +160,10 @@ def main():
     args = ap.parse_args()
     if args.stolt_first_call:
         return stolt_first_call_child()
+    if args.apres_first_call:
+        return apres_first_call_child()
     field_first = stolt_first_calls() if 'field' not in args.skip else None        # (children first: this process has not opened the GPU yet)
+    apres_first = apres_first_call() if 'apres' not in args.skip else None
     from impdar_amd import _hip, synth
     from impdar_amd.lib.RadarData import RadarData
     from impdar_amd.lib import migrationlib
@@ -791,6 +854,129 @@ def main():
                                                "once; the coherence's window sums (32 B per element written and re-read "
                                                "about 2 nrange / bk + bk times from cache) are not counted"}}), flush=True)
         free(d_vec + list(images) + [d_c])
+
+    if 'apres' not in args.skip:
+        # ApRES range conversion and stacking at an unattended deployment's size, resident: device time per call (host clock around
+        # a device synchronise, `reps` calls each: least, median, most), the conversion's three stages from the library's own
+        # events, bytes / time against HBM, a device copy of the same number of bytes timed the same way, the chain through host
+        # arrays, the first call of a fresh process, and the reference's per-chirp NumPy loop on one core
+        import ctypes
+        from impdar_amd import apres as apm
+        bnum, cnum, snum, p, max_range = APRES
+        rows, N = bnum * cnum, p * snum
+        ctx, lib = _hip.context(), _hip.load()
+        dat = apres_holder(bnum, cnum, snum)
+        t = apm.range_tables(dat, p, max_range)
+        raw = apm.raw_rows(dat)
+        n, nf, nh = t.n, t.nf, N // 2 + 1
+        d_raw = _hip.DeviceArray.from_host(ctx, raw)
+
+        def aspread(fn, reps=5):
+            fn()
+            ms = []
+            for _ in range(reps):
+                lib.impdar_ctx_sync(ctx)
+                t0 = time.perf_counter()
+                fn()
+                lib.impdar_ctx_sync(ctx)
+                ms.append((time.perf_counter() - t0) * 1e3)
+            ms.sort()
+            return {"min": ms[0], "median": ms[len(ms) // 2], "max": ms[-1]}
+
+        stages = []
+
+        def range_call():
+            out = apm.range_dev(d_raw, t)
+            lib.impdar_ctx_sync(ctx)
+            stages.append(apm.range_last_ms(ctx))
+            for d in out:
+                d.free()
+
+        range_ms = aspread(range_call)
+        st = np.array(stages[1:])
+        stage_ms = {k: {"min": float(st[:, i].min()), "median": float(np.median(st[:, i])), "max": float(st[:, i].max())}
+                    for i, k in enumerate(("prep", "transform", "post"))}
+        products = apm.range_dev(d_raw, t)
+
+        def stack_call():
+            d = apm.stack_dev(products[1], 1, rows)
+            lib.impdar_ctx_sync(ctx)
+            d.free()
+
+        stack_ms = aspread(stack_call)
+        for d in products:
+            d.free()
+        bytes_of = {"prep": rows * snum * 8 + rows * N * 8, "transform": rows * N * 8 + rows * nh * 16,
+                    "post": rows * nf * 16 + 2 * rows * n * 16 + rows * nf * 8, "stack": rows * n * 16 + n * 16}
+        range_bytes = bytes_of["prep"] + bytes_of["transform"] + bytes_of["post"]
+
+        def ap_copy(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+
+            def call():
+                b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+                lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8))
+                lib.impdar_ctx_sync(ctx)
+                b.free()
+            ms = aspread(call)
+            a.free()
+            return ms
+        copy_range, copy_stack = ap_copy(range_bytes), ap_copy(bytes_of["stack"])
+        d_raw.free()
+
+        def chain_call():
+            c = apres_holder(1, 1, 2)
+            c.bnum, c.cnum, c.snum, c.data = bnum, cnum, snum, dat.data
+            apm.chain(c, p, max_range)
+        t0 = time.perf_counter()
+        chain_call()
+        chain_first = (time.perf_counter() - t0) * 1e3
+        chain_ms = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            chain_call()
+            chain_ms.append((time.perf_counter() - t0) * 1e3)
+
+        cb = None
+        if not args.no_cpu:
+            sample = 20
+            t0 = time.perf_counter()
+            spec = np.zeros((sample, nf)).astype(np.cdouble)
+            cor = np.zeros((sample, nf)).astype(np.cdouble)
+            for ic in range(sample):                         # the reference's loop body, chirp by chirp
+                chirp = raw[ic].copy()
+                chirp = chirp - np.mean(chirp)
+                chirp *= t.win
+                f = (np.sqrt(2. * p) / len(chirp)) * np.fft.fft(chirp, N)
+                f /= np.sqrt(np.mean(t.win**2.))
+                spec[ic] = f[:nf]
+                cor[ic] = np.exp(-1j * t.phiref) * f[:nf]
+            el = time.perf_counter() - t0
+            cb = {"what": "the reference's per-chirp NumPy loop (de-mean, window, numpy.fft.fft of the padded chirp, scale, reference "
+                          "phasor) on one core", "sample": "%d of %d chirps, scaled" % (sample, rows), "ms": el * 1e3 * rows / sample}
+        hbm = lambda b, ms: b / ms / 1e6 / 8000.0                                   # noqa: E731
+        print(json.dumps({"path": "apres range %d x %d x %d float64, pad %d, %g m" % (bnum, cnum, snum, p, max_range),
+                          "config": "N %d, %d of %d bins kept, blackman, resident" % (N, n, nf),
+                          "device_ms": range_ms["median"], "device_ms_spread": range_ms, "stages_ms": stage_ms,
+                          "stack_ms": stack_ms, "algorithmic_bytes": range_bytes, "algorithmic_bytes_per_stage": bytes_of,
+                          "hbm_frac_per_stage": dict({k: hbm(bytes_of[k], stage_ms[k]["median"]) for k in stage_ms},
+                                                     stack=hbm(bytes_of["stack"], stack_ms["median"])),
+                          "copy_same_bytes_ms": {"range": copy_range, "stack": copy_stack},
+                          "time_over_copy": {"range": range_ms["median"] / copy_range["median"],
+                                             "stack": stack_ms["median"] / copy_stack["median"]},
+                          "chain_host_ms": {"first": chain_first, "later": chain_ms,
+                                            "moves": "%d MB up, %d MB down" % (raw.nbytes >> 20, (2 * rows * n * 16 + rows * nf * 8 + n * 16) >> 20)},
+                          "first_call": apres_first,
+                          "roofline": {"bound": "hbm", "achieved": range_bytes / range_ms["median"] / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                       "frac": hbm(range_bytes, range_ms["median"]),
+                                       "note": "time per call (host clock around a device synchronise), with the output allocations and "
+                                               "table upload; stages from events on the stream, summed over the chunks.  Bytes: prep reads "
+                                               "the chirps and writes the padded rows, the transform reads those and writes N / 2 + 1 bins "
+                                               "(its own passes over a row of this length are not counted), post reads nf bins and writes "
+                                               "spec, data (n bins) and Rfine (nf bins); stacking reads data once"},
+                          "cpu_baseline": cb}), flush=True)
 
 
 if __name__ == '__main__':

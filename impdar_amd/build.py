@@ -1,7 +1,7 @@
 """Build the HIP shared library in-tree (``impdar_amd/csrc/libimpdar_hip.so``).
 
 hipcc cross-compiles for gfx950 without a GPU present.  The library links
-rocFFT (Stolt / phase-shift transforms) and RCCL (multi-GPU all-gather).
+rocFFT (Stolt / phase-shift / ApRES range transforms) and RCCL (multi-GPU all-gather).
 """
 import os
 import subprocess
@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libimpdar_hip.so')
 SOURCES = ['api.hip', 'comm.hip', 'kirchhoff.hip', 'kirch_gen.hip', 'stolt.hip', 'phaseshift.hip', 'preproc.hip',
-           'hfilt.hip', 'denoise.hip', 'hpass.hip', 'vaxis.hip', 'gain.hip', 'taxis.hip', 'quadpol.hip']
+           'hfilt.hip', 'denoise.hip', 'hpass.hip', 'vaxis.hip', 'gain.hip', 'taxis.hip', 'quadpol.hip', 'apres.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off',
          '-fno-slp-vectorize', '-Wall', '-Wno-unused-function']
 

@@ -178,6 +178,7 @@ void impdar_vaxis_forget(impdar_ctx *ctx);         // vaxis.hip
 void impdar_gain_forget(impdar_ctx *ctx);          // gain.hip
 void impdar_taxis_forget(impdar_ctx *ctx);         // taxis.hip
 void impdar_quadpol_forget(impdar_ctx *ctx);       // quadpol.hip
+void impdar_apres_forget(impdar_ctx *ctx);         // apres.hip
 
 void impdar_kirch_trim();    // kirchhoff.hip
 void impdar_stolt_trim();    // stolt.hip
@@ -620,6 +621,7 @@ extern "C" void impdar_ctx_destroy(impdar_ctx *ctx)
     impdar_gain_forget(ctx);
     impdar_taxis_forget(ctx);
     impdar_quadpol_forget(ctx);
+    impdar_apres_forget(ctx);
     impdar_devcache_trim(ctx->device);
     pinned_adopt(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);

@@ -471,6 +471,49 @@ int impdar_qp_phase_gradient_dev(impdar_ctx *ctx, const double *d_chhvv, int n, 
                                  const double *ga, const double *gb, const double *gc, const double *b, const double *a,
                                  int ncoef, const double *zi, double *d_dphi_dz);
 
+/* ---- ApRES range conversion, stacking, phase difference (csrc/apres.hip) ----
+ * Everything float64 / complex128 (interleaved (re, im) doubles), row-major.
+ * impdar_apres_range: _ApresDataProcessing.py:84-113 for `rows` = bnum cnum
+ * chirps of `snum` real samples: de-mean, window, real transform of length
+ * N = p snum, nf = N / 2 (rounded down) bins of which the first n are kept:
+ *   spec[r, k] = X[r, k] scale_mul (1 / scale_div)                   k < n
+ *   data[r, k] = comp[k] spec[r, k]                                  k < n
+ *   Rfine[r, k] = atan2(im, re of data) / den[k]                     k < nf
+ * or, with first_order != 0, (lambdac atan2(im, re)) / den[k] (phase2range's
+ * first-order branch with den[k] = 4 pi; lambdac is not read otherwise).
+ * win: snum, comp: nf complex, den: nf host values.  spec, data: (rows, n);
+ * Rfine: (rows, nf).  n == 0 writes Rfine alone (spec and data may be null).
+ * The chirps are transformed `chunk` at a time, 0 for the library's choice
+ * (256 MiB of scratch); the results do not depend on it.
+ * snum < 2, p < 1, n > nf, a null table are IMPDAR_ERR_ARG before any device work.
+ * impdar_apres_range_last_ms: device time of the three stages of the last
+ * range conversion on this context, summed over its chunks (waits for it).
+ * impdar_apres_stack: (:191-222) out[g, j] = mean of rows g m ... g m + m - 1
+ * of the (rows, snum) array `data`, float64 or (is_complex != 0) complex128,
+ * g < groups, groups m <= rows: a sum in row order, then numpy.mean's last
+ * step (a division by m; for complex data a product with 1 / m).
+ * impdar_apres_phase_diff: _TimeDiffProcessing.py:75-91.  co[i] = S(s1 conj(s2))
+ * / sqrt(S|s1|^2 S|s2|^2), S over samples [i step, i step + 2 (win / 2)) of two
+ * complex128 vectors of `len` samples, i < ceil((len - 2 (win / 2)) / step)
+ * (none when that is not positive); a zero denominator gives NaN in both
+ * parts.  Sums are additions only.
+ * The *_dev forms take device arrays (the tables stay host arrays), enqueue on
+ * the context's compute stream and return without waiting for it. */
+int impdar_apres_range(impdar_ctx *ctx, const double *raw, int rows, int snum, int p, int n, const double *win,
+                       const double *comp, const double *den, double scale_mul, double scale_div, int first_order,
+                       double lambdac, int chunk, double *spec, double *data, double *rfine);
+int impdar_apres_range_dev(impdar_ctx *ctx, const double *d_raw, int rows, int snum, int p, int n, const double *win,
+                           const double *comp, const double *den, double scale_mul, double scale_div, int first_order,
+                           double lambdac, int chunk, double *d_spec, double *d_data, double *d_rfine);
+int impdar_apres_range_last_ms(impdar_ctx *ctx, float *prep_ms, float *fft_ms, float *post_ms);
+int impdar_apres_stack(impdar_ctx *ctx, const double *data, int is_complex, int rows, int snum, int groups, int m,
+                       double *out);
+int impdar_apres_stack_dev(impdar_ctx *ctx, const double *d_data, int is_complex, int rows, int snum, int groups, int m,
+                           double *d_out);
+int impdar_apres_phase_diff(impdar_ctx *ctx, const double *s1, const double *s2, int len, int win, int step, double *co);
+int impdar_apres_phase_diff_dev(impdar_ctx *ctx, const double *d_s1, const double *d_s2, int len, int win, int step,
+                                double *d_co);
+
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
 
