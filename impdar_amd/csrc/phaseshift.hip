@@ -1516,6 +1516,18 @@ static int ps_dispatch(const PsParams &P, hipStream_t st)
 #include "ps_series.h"      // a velocity that changes inside a piece: a few transforms with shared nodes + direct sums at the boundary
 #include "ps_runs.h"        // many runs of constant velocity: float32 MFMA, phases generated in the kernel
 
+// ---- the path runners: ps_runs_run, ps_nufft_run, ps_series_run, ps_mfma_run (and ps_smooth_run further down), one signature.
+// What a path plans on the host and every host-side reason to decline is ps_path_plan.h's (ps_series_plan.h for the series path);
+// a runner tests what depends on the device, allocates, uploads and launches.  *done = true: the frequency sums were produced
+// here; false with IMPDAR_OK: the call is not for this path, the next attempt of the route takes it.
+struct PsCall {
+    const double *kx, *vmig;    // the caller's host arrays: [tnum]; [snum] per-step velocities (vlen != 0)
+    int vlen;
+    bool tk_out;                // the sums go to a caller who asked for the rows TK themselves (a rank of a kx-sharded run): rows k and
+                                // tnum - k may not be written as their Hermitian combination and its conjugate
+    PsKnobs K;
+};
+
 // did a matrix-core path find more boundary frequencies than it lists on this (kx, runs) geometry before?  (ADVICE r4:
 // such inputs paid set-up + sums + a blocking read-back on EVERY call, discarded, before the vector kernels ran)
 static bool ps_known_overflow(const PsPlan &pl, const double *kx, int tnum, const std::vector<PsMfmaRun> &runs)
@@ -1532,93 +1544,101 @@ static void ps_note_overflow(PsPlan &pl, const double *kx, int tnum, const std::
     pl.ovf_runs = runs;
 }
 
-// ---- many-runs matrix-core path (ps_runs.h): stages, launch.  Same contract as ps_mfma_run.
-static int ps_runs_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &runs, const double *kx_host, const double *w_host,
-                       const double *thr, hipStream_t st, bool *done)
+// the whole wavenumber axis with kx[tnum - k] = -kx[k] (the Nyquist row of an even axis is its own partner): rows k and tnum - k
+// turn by the same angles and share a workgroup; a slab of a kx-sharded run has no mirror rows
+static bool ps_mirror_rows(const PsParams &P, const PsRoute &R) { return R.kx_antisym && P.k0 == 0 && P.nk == P.tnum && P.tnum >= 2; }
+
+// every buffer of a path at its size, or none of the path: not getting them is not an error, the other paths take the call
+static bool ps_ensure_all(std::initializer_list<std::pair<DevBuf *, size_t>> needs)
+{
+    for (const auto &n : needs)
+        if (n.first->ensure(n.second) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+    return true;
+}
+
+// rw = 1 / w by slot on the device (rw: the runner's staging, alive until its stream drain; pl.d_rw: ensured by the runner)
+static int ps_rw_upload(PsPlan &pl, const PsRoute &R, int nf, std::vector<double> &rw, hipStream_t st)
+{
+    rw.resize((size_t)nf);
+    for (int i = 0; i < nf; ++i) rw[i] = 1.0 / R.w[i];
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_rw.p, rw.data(), rw.size() * 8, hipMemcpyHostToDevice, st));
+    return IMPDAR_OK;
+}
+
+// MFMA instructions the kernel issued, counted by the kernel (the stream is drained)
+static int ps_mcount_read(PsPlan &pl)
+{
+    unsigned long long n = 0;
+    IMPDAR_HIP_CHECK(hipMemcpy(&n, pl.d_mcount.p, 8, hipMemcpyDeviceToHost));
+    pl.mfma_instructions = (double)n;
+    return IMPDAR_OK;
+}
+
+// Boundary frequencies: a path's kernel takes the frequencies on the evanescent boundary of some run out of its sums and lists the
+// first PM_EMAX per wavenumber; ps_edge_kernel walks the listed ones the reference's way.  The counter keeps counting: more
+// than PM_EMAX means contributions are missing from TK -- the result is discarded and another path produces it.
+// Before the path's kernel: room for the lists (*room false: none), E filled (ps_edge_kernel reads P and the lists only), counts cleared
+static int ps_edge_prepare(PsPlan &pl, const PsParams &P, bool clear, hipStream_t st, PsMfmaParams &E, bool *room)
+{
+    *room = ps_ensure_all({{&pl.d_edge, (size_t)P.tnum * (1 + PM_EMAX) * sizeof(int)}});
+    if (!*room) return IMPDAR_OK;
+    E.mfma_count = nullptr;
+    E.P = P;
+    E.nruns = 0;
+    E.pairs = 0;
+    E.edge_cnt = pl.d_edge.as<int>();
+    E.edge_list = E.edge_cnt + P.tnum;
+    if (clear) IMPDAR_HIP_CHECK(hipMemsetAsync(E.edge_cnt, 0, (size_t)P.tnum * sizeof(int), st));
+    return IMPDAR_OK;
+}
+// After it: ps_edge_kernel (walk; else the drain only), the stream drained (the runner's host tables must outlive their copies), the
+// counts of [k0, k0 + nk) read back.  *worst > PM_EMAX: lists overflowed, the geometry is remembered and not tried again
+template <typename T>
+static int ps_edge_finish(PsPlan &pl, const PsRoute &R, const PsCall &c, const PsMfmaParams &E, bool walk, const char *who, hipStream_t st, int *worst)
+{
+    const PsParams &P = E.P;
+    *worst = 0;
+    if (walk) hipLaunchKernelGGL(ps_edge_kernel_t<T>, dim3(P.nk), dim3(256), 0, st, E);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    if (who) impdar_trace("%s: buffers ready, tables copied, kernels enqueued", who);
+    IMPDAR_HIP_CHECK(hipStreamSynchronize(st));
+    if (who) impdar_trace("%s: stream drained", who);
+    if (!walk) return IMPDAR_OK;
+    std::vector<int> cnt((size_t)P.nk);
+    IMPDAR_HIP_CHECK(hipMemcpy(cnt.data(), E.edge_cnt + P.k0, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int n : cnt) *worst = std::max(*worst, n);
+    if (*worst > PM_EMAX) ps_note_overflow(pl, c.kx, P.tnum, R.runs);
+    return IMPDAR_OK;
+}
+
+// ---- many-runs matrix-core path (ps_runs.h): stages (pr_plan), launch
+static int ps_runs_run(PsPlan &pl, PsParams &P, const PsRoute &R, const PsCall &c, const PsAttempt &, hipStream_t st, bool *done, const char **kernel)
 {
     *done = false;
+    *kernel = "ps_runs_kernel";
     const int snum = P.snum, tnum = P.tnum;
-    if (P.nf % 32 != 0 || P.nf < 256 || snum < 64 || runs.empty()) return IMPDAR_OK;
-    for (int i = 0; i < snum; ++i)
-        if (!(thr[i] < 1e-10)) return IMPDAR_OK;           // the evanescence test must be the sign of coss off the boundary band
-    if (ps_known_overflow(pl, kx_host, tnum, runs)) return IMPDAR_OK;
-    // runs -> pieces: long (<= 512 steps, tiles of 8) and single steps
-    std::vector<PrRun> pr;
-    int nshort_total = 0, nblk_total = 0;
-    for (const PsMfmaRun &r : runs) {
-        if (r.len <= PR_SHORT_LEN) {
-            pr.push_back(PrRun{r.v, r.start, r.len, 1, 0});
-            nshort_total += r.len;
-            continue;
-        }
-        const int npiece = (r.len + PR_LONG_MAX - 1) / PR_LONG_MAX;
-        for (int i = 0, at = 0; i < npiece; ++i) {
-            // pieces of (nearly) equal length, whole tiles except the last
-            int len = ((r.len - at) / (npiece - i) + PR_TT - 1) / PR_TT * PR_TT;
-            len = std::min(len, r.len - at);
-            pr.push_back(PrRun{r.v, r.start + at, len, 0, 0});
-            nblk_total += ((len + PR_TT - 1) / PR_TT + PR_ROWS - 1) / PR_ROWS;
-            at += len;
-        }
-    }
-    // a record that is mostly single steps (a velocity that changes at nearly every step) is ps_smooth's
-    if (nshort_total > snum / 4 || nblk_total == 0) return IMPDAR_OK;
-    std::vector<PrStage> stages;
-    {
-        PrStage cur;
-        auto open = [&](int run0) {
-            cur = PrStage{};
-            cur.run0 = run0;
-            for (int i = 0; i < PR_LONGS; ++i) cur.long_run[i] = -1;
-        };
-        auto close = [&]() {
-            if (cur.nruns == 0) return;
-            // the single steps go to the wave with the fewest blocks
-            int best = 0;
-            for (int i = 1; i < PR_LONGS; ++i)
-                if (cur.long_nblk[i] < cur.long_nblk[best]) best = i;
-            cur.short_wave = best;
-            stages.push_back(cur);
-        };
-        open(0);
-        int nlong = 0;
-        for (int i = 0; i < (int)pr.size(); ++i) {
-            const bool is_long = pr[i].kind == 0;
-            // (single steps lead the long run that follows them: the set-up chains their states into its anchor -- a stage
-            // that has its four long runs is closed before the next group)
-            const bool fits = cur.nruns < PR_STAGE_RUNS && (is_long ? nlong < PR_LONGS : (nlong < PR_LONGS && cur.nshort + pr[i].len <= PR_SROWS));
-            if (!fits) {
-                close();
-                open(i);
-                nlong = 0;
-            }
-            if (is_long) {
-                pr[i].slot = nlong;
-                cur.long_run[nlong] = i;
-                cur.long_nblk[nlong] = ((pr[i].len + PR_TT - 1) / PR_TT + PR_ROWS - 1) / PR_ROWS;
-                ++nlong;
-            } else {
-                pr[i].slot = cur.nshort;
-                for (int s_ = 0; s_ < pr[i].len; ++s_) cur.short_tau[cur.nshort++] = pr[i].start + s_;
-            }
-            ++cur.nruns;
-        }
-        close();
-    }
+    if (!pr_gate((int)R.runs.size(), P.nf, snum) || !ps_thr_off_band(R.thr.data(), snum) || ps_known_overflow(pl, c.kx, tnum, R.runs)) return IMPDAR_OK;
+    PrPlan plan;
+    if (!pr_plan(plan, R.runs, P.nf, snum)) return IMPDAR_OK;
+    const std::vector<PrRun> &pr = plan.pr;
+    const std::vector<PrStage> &stages = plan.stages;
     impdar_trace("ps_runs: %zu pieces in %zu stages", pr.size(), stages.size());
-    const int nparts = (P.nf + PR_PART - 1) / PR_PART;
+    const int nparts = plan.nparts;
     const size_t part_bytes = nparts > 1 ? (size_t)nparts * P.nk * snum * sizeof(Cp<float>) : 0;
-    std::vector<double> rw((size_t)P.nf);
-    for (int i = 0; i < P.nf; ++i) rw[i] = 1.0 / w_host[i];
-    if (pl.d_pr_runs.ensure(pr.size() * sizeof(PrRun)) != hipSuccess || pl.d_pr_stages.ensure(stages.size() * sizeof(PrStage)) != hipSuccess ||
-        pl.d_rw.ensure(rw.size() * 8) != hipSuccess || pl.d_edge.ensure((size_t)tnum * (1 + PM_EMAX) * sizeof(int)) != hipSuccess ||
-        (part_bytes && pl.d_part.ensure(part_bytes) != hipSuccess) || pl.d_mcount.ensure(8) != hipSuccess) {
-        (void)hipGetLastError();
-        return IMPDAR_OK;                      // no room: the other paths take the call
-    }
+    PsMfmaParams E;
+    bool room;
+    int rc;
+    if (!ps_ensure_all({{&pl.d_pr_runs, pr.size() * sizeof(PrRun)}, {&pl.d_pr_stages, stages.size() * sizeof(PrStage)}, {&pl.d_rw, (size_t)P.nf * 8},
+                        {&pl.d_part, part_bytes}, {&pl.d_mcount, 8}}))
+        return IMPDAR_OK;
+    if ((rc = ps_edge_prepare(pl, P, true, st, E, &room)) || !room) return rc;
+    std::vector<double> rw;
     IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pr_runs.p, pr.data(), pr.size() * sizeof(PrRun), hipMemcpyHostToDevice, st));
     IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pr_stages.p, stages.data(), stages.size() * sizeof(PrStage), hipMemcpyHostToDevice, st));
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_rw.p, rw.data(), rw.size() * 8, hipMemcpyHostToDevice, st));
+    if ((rc = ps_rw_upload(pl, R, P.nf, rw, st))) return rc;
     PrParams Q;
     Q.P = P;
     Q.runs = pl.d_pr_runs.as<PrRun>();
@@ -1628,20 +1648,18 @@ static int ps_runs_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &run
     Q.nruns = (int)pr.size();
     Q.nparts = nparts;
     Q.part = pl.d_part.p;
-    Q.edge_cnt = pl.d_edge.as<int>();
-    Q.edge_list = Q.edge_cnt + tnum;
+    Q.edge_cnt = E.edge_cnt;
+    Q.edge_list = E.edge_list;
     Q.mfma_count = pl.d_mcount.as<unsigned long long>();
-    IMPDAR_HIP_CHECK(hipMemsetAsync(Q.edge_cnt, 0, (size_t)tnum * sizeof(int), st));
     IMPDAR_HIP_CHECK(hipMemsetAsync(Q.mfma_count, 0, 8, st));
-    // the whole wavenumber axis with kx[tnum - k] = -kx[k]: rows k and tnum - k in one workgroup (ps_runs.h); a slab of a
-    // kx-sharded run has no mirror rows
-    bool pairs = P.k0 == 0 && P.nk == tnum && tnum >= 2;
-    for (int k = 1; 2 * k < tnum && pairs; ++k) pairs = kx_host[k] == -kx_host[tnum - k];      // (the Nyquist row of an even axis is its own partner)
+    const bool pairs = ps_mirror_rows(P, R);     // rows k and tnum - k in one workgroup (ps_runs.h)
     const bool tr = impdar_trace_on();           // tracing: drain the stream between the launches, a line each
-    if (tr) {
+    auto drained = [&](const char *what) {
+        if (!tr) return;
         (void)hipStreamSynchronize(st);
-        impdar_trace("ps_runs: stream idle before the frequency sums");
-    }
+        impdar_trace("ps_runs: %s", what);
+    };
+    drained("stream idle before the frequency sums");
     if (pairs) {
         IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)ps_runs_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pr_lds_bytes(2)));
         hipLaunchKernelGGL(ps_runs_kernel<2>, dim3((unsigned)(tnum / 2 + 1) * nparts), dim3(256), pr_lds_bytes(2), st, Q);
@@ -1649,214 +1667,107 @@ static int ps_runs_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &run
         IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)ps_runs_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pr_lds_bytes(1)));
         hipLaunchKernelGGL(ps_runs_kernel<1>, dim3((unsigned)P.nk * nparts), dim3(256), pr_lds_bytes(1), st, Q);
     }
-    if (tr) {
-        (void)hipStreamSynchronize(st);
-        impdar_trace("ps_runs: ps_runs_kernel done");
-    }
+    drained("ps_runs_kernel done");
     if (nparts > 1) {
         const size_t n = (size_t)P.nk * snum;
         hipLaunchKernelGGL((ps_smooth_sum_kernel<float>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                            reinterpret_cast<const Cp<float> *>(pl.d_part.p), reinterpret_cast<Cp<float> *>(P.TK), nparts, n, snum);
     }
-    if (tr) {
-        (void)hipStreamSynchronize(st);
-        impdar_trace("ps_runs: partial images summed");
-    }
-    {
-        PsMfmaParams E;                        // (ps_edge_kernel reads P and the lists only)
-        E.mfma_count = nullptr;
-        E.P = P;
-        E.nruns = 0;
-        E.pairs = 0;
-        E.edge_cnt = Q.edge_cnt;
-        E.edge_list = Q.edge_list;
-        hipLaunchKernelGGL(ps_edge_kernel_t<float>, dim3(P.nk), dim3(256), 0, st, E);
-    }
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    impdar_trace("ps_runs: buffers ready, tables copied, kernels enqueued");
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(st));            // (the host tables must outlive their copies)
-    impdar_trace("ps_runs: stream drained");
-    std::vector<int> cnt((size_t)P.nk);
-    IMPDAR_HIP_CHECK(hipMemcpy(cnt.data(), Q.edge_cnt + P.k0, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-    int worst = 0;
-    for (int c : cnt) worst = std::max(worst, c);
+    drained("partial images summed");
     // every part of a wavenumber counts its own boundary frequencies into the same list: the first PM_EMAX are walked
-    if (worst > PM_EMAX) {
-        ps_note_overflow(pl, kx_host, tnum, runs);
-        return IMPDAR_OK;                      // contributions missing from TK: discarded, another path produces the result
-    }
-    {
-        unsigned long long n = 0;
-        IMPDAR_HIP_CHECK(hipMemcpy(&n, Q.mfma_count, 8, hipMemcpyDeviceToHost));
-        pl.mfma_instructions = (double)n;
-    }
+    int worst;
+    if ((rc = ps_edge_finish<float>(pl, R, c, E, true, "ps_runs", st, &worst)) || worst > PM_EMAX) return rc;
+    if ((rc = ps_mcount_read(pl))) return rc;
     impdar_trace("ps_runs: counters read back: %.0f MFMA instructions, worst edge count %d, %d parts, pairs %d", pl.mfma_instructions, worst, nparts, (int)pairs);
     *done = true;
     return IMPDAR_OK;
 }
 
-// 1 / psihat(n), n = 0 .. Lp/2, of every padded length in `need`: psihat(n) = int psi(x) cos(2 pi n x / G) dx over |x| < W/2
-// (Simpson, float64; the integrand ends at e^{-beta} = 1e-8 of its maximum).  Made once per length and plan; *grew: the device
-// copy is stale.  (Shared by the transform paths ps_nufft.h and ps_series.h: same window, same tables.)
+// 1 / psihat(n), n = 0 .. Lp/2, of every padded length in `need` (pn_corr_of_length, ps_path_plan.h).  Made once per length and
+// plan; *grew: the device copy is stale.  (Shared by the transform paths ps_nufft.h and ps_series.h: same window, same tables.)
 template <typename T>
 static std::vector<T> &pn_corr_tables(PsPlan &pl, const bool (&need)[13], int (&off_out)[13], bool *grew)
 {
-    constexpr int PN_W = PnCfg<T>::W;
     std::vector<T> &corr = sizeof(T) == 4 ? reinterpret_cast<std::vector<T> &>(pl.h_pn_corr) : reinterpret_cast<std::vector<T> &>(pl.h_pn_corr64);
     int *corr_off = pl.pn_corr_off[sizeof(T) == 8 ? 1 : 0];
     for (int l = 0; l < 13; ++l) {
         if (!need[l] || corr_off[l] >= 0) continue;
         corr_off[l] = (int)corr.size();
         *grew = true;
-        const int Lp = 1 << l, G = 2 * Lp, NS = 512;
-        const double beta = 2.30 * PN_W, h = (double)PN_W / NS;
-        std::vector<double> psi((size_t)NS + 1);
-        for (int q = 0; q <= NS; ++q) {
-            const double x = -0.5 * PN_W + q * h, z = 1.0 - (2.0 * x / PN_W) * (2.0 * x / PN_W);
-            psi[q] = std::exp(beta * (std::sqrt(z > 0.0 ? z : 0.0) - 1.0)) * ((q == 0 || q == NS) ? 1.0 : ((q & 1) ? 4.0 : 2.0));
-        }
-        // (sum_q psi_q cos(n theta_q), theta_q = 2 pi x_q / G, for all n at once: per node a rotation by theta_q from n to n + 1,
-        // re-seeded with the library's cos / sin every 64 -- a cos() per (n, q) was ~20 ms of a process's first call at 8192^2)
-        std::vector<double> acc((size_t)Lp / 2 + 1, 0.0);
-        for (int q = 0; q <= NS; ++q) {
-            const double th = 6.283185307179586 * (-0.5 * PN_W + q * h) / G, ct = std::cos(th), st_ = std::sin(th), pq = psi[q];
-            double c = 1.0, sn = 0.0;
-            for (int n = 0; n <= Lp / 2; ++n) {
-                if ((n & 63) == 0) {
-                    c = std::cos(th * n);
-                    sn = std::sin(th * n);
-                }
-                acc[(size_t)n] += pq * c;
-                const double c2 = c * ct - sn * st_;
-                sn = sn * ct + c * st_;
-                c = c2;
-            }
-        }
-        for (int n = 0; n <= Lp / 2; ++n) corr.push_back((T)(1.0 / (acc[(size_t)n] * h / 3.0)));
+        for (double x : pn_corr_of_length(PnCfg<T>::W, l)) corr.push_back((T)x);
     }
     for (int l = 0; l < 13; ++l) off_out[l] = corr_off[l] < 0 ? 0 : corr_off[l];
     return corr;
 }
 
-// ---- transform path (ps_nufft.h): pieces, correction tables, launch.  Same contract as ps_mfma_run.
-template <typename T>
-static int ps_nufft_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &runs, bool vz, const double *kx_host, const double *w_host,
-                        const double *thr, hipStream_t st, bool *done, bool kx_antisym, const double *vmig = nullptr, bool allow_pairs = false)
+// the grid tables of a transform path on the device and in its parameters Q: the twiddles of the grid lengths 2^(l + 1) in `need`,
+// the correction tables of the window.  *room false: no room for the tables
+template <typename T, typename Params>
+static int ps_grid_tables(PsPlan &pl, const bool (&need)[13], Params &Q, hipStream_t st, bool *room)
 {
-    // vmig (float64 data, v(z)): the per-step velocities -- the runs' rounding noise enters as a first-order term (ps_nufft.h)
-    // allow_pairs: the sums go on into the inverse transform (not to a caller who asked for the rows TK themselves): rows k and
-    // tnum - k may be written as their Hermitian combination and its conjugate (ps_nufft_kernel<float, true>)
-    const bool first_order = sizeof(T) == 8 && vz && vmig != nullptr;
-    *done = false;
-    const int snum = P.snum, tnum = P.tnum, nf = P.nf;
-    if (!P.herm || nf < 64 || nf > PN_NFMAX || snum < 64 || runs.empty()) return IMPDAR_OK;
-    if (vz && ps_known_overflow(pl, kx_host, tnum, runs)) return IMPDAR_OK;
-    if (vz)
-        for (int i = 0; i < snum; ++i)
-            if (!(thr[i] < 1e-10)) return IMPDAR_OK;       // the evanescence test must be the sign of coss off the boundary band
-    // the gather inverts the dispersion relation on a uniform frequency axis: slot i + 1 at (i + 1) dw, the Nyquist row (slot 0) at nf dw
-    const double dw = w_host[1];
-    if (!(dw > 0.0)) return IMPDAR_OK;
-    for (int i = 1; i < nf; ++i)
-        if (std::fabs(w_host[i] - (double)i * dw) > 1e-9 * (double)i * dw) return IMPDAR_OK;
-    if (std::fabs(std::fabs(w_host[0]) - (double)nf * dw) > 1e-9 * (double)nf * dw) return IMPDAR_OK;
-    // the whole wavenumber axis with kx[tnum - k] = -kx[k]: a pair of rows per workgroup, as ps_runs_kernel's
-    const bool pairs = allow_pairs && P.k0 == 0 && P.nk == tnum && tnum >= 2 && tnum % 2 == 0 && kx_antisym;     // (ps_route.h)
-    if (P.fhalf && !pairs) return IMPDAR_OK;           // (the half layout is read by the pairs only; ps_run repeats the transforms)
-    const int lmax_steps = pn_lmax<T>(pairs);
-    std::vector<PnPiece> pc;
-    int nshort_steps = 0;
-    bool need[13] = {};
-    for (const PsMfmaRun &r : runs) {
-        if (vz && r.len <= PN_SHORT) {
-            // consecutive short runs (the single steps of one smeared boundary) share a piece: one pass over the frequencies
-            nshort_steps += r.len;
-            if (!pc.empty() && pc.back().kind == 1 && pc.back().start + pc.back().len == r.start && pc.back().len + r.len <= PN_SHORT) {
-                for (int q = 0; q < r.len; ++q) pc.back().vs[pc.back().len + q] = r.v;
-                pc.back().len += r.len;
-            } else {
-                PnPiece p1{r.v, r.start, r.len, 1, 0, {}};
-                for (int q = 0; q < PN_SHORT; ++q) p1.vs[q] = r.v;
-                pc.push_back(p1);
-            }
-            continue;
-        }
-        const int npiece = (r.len + lmax_steps - 1) / lmax_steps;
-        for (int i = 0, at = 0; i < npiece; ++i) {
-            const int len = (r.len - at) / (npiece - i);
-            int l = 4;
-            while ((1 << l) < len) ++l;
-            PnPiece p0{r.v, r.start + at, len, 0, l, {}};
-            pc.push_back(p0);
-            need[l] = true;
-            at += len;
-        }
-    }
-    // a direct step costs as much as a tenth of a piece: tables of many layers stay with ps_runs_kernel
-    if (nshort_steps > 128 || pc.size() > 256) return IMPDAR_OK;
-    std::vector<double> e1;
-    if (first_order) {
-        // per piece: the reference velocity sqrt(mean v^2) and E(n) / cbar^2 = sum_{t <= n} (v_t^2 / mean - 1)
-        e1.assign((size_t)snum, 0.0);
-        for (PnPiece &p0 : pc) {
-            if (p0.kind != 0) continue;
-            long double acc = 0.0L;
-            for (int t = 0; t < p0.len; ++t) acc += (long double)vmig[p0.start + t] * vmig[p0.start + t];
-            const double vb2 = (double)(acc / p0.len);
-            p0.v = std::sqrt(vb2);
-            long double run = 0.0L;
-            for (int t = 0; t < p0.len; ++t) {
-                run += ((long double)vmig[p0.start + t] * vmig[p0.start + t] - (long double)vb2) / (long double)vb2;
-                e1[(size_t)p0.start + t] = (double)run;
-            }
-        }
-        if (pl.d_pn_e1.ensure(e1.size() * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            return IMPDAR_OK;
-        }
-    }
-    PnParams Q;
     bool grew = false;
     std::vector<T> &corr = pn_corr_tables<T>(pl, need, Q.corr_off, &grew);
-    std::vector<double> rw((size_t)nf);
-    for (int i = 0; i < nf; ++i) rw[i] = 1.0 / w_host[i];
-    if (pl.d_pn_pieces.ensure(pc.size() * sizeof(PnPiece)) != hipSuccess || pl.d_pn_corr.ensure(corr.size() * sizeof(T) + 16) != hipSuccess ||
-        pl.d_rw.ensure(rw.size() * 8) != hipSuccess || pl.d_edge.ensure((size_t)tnum * (1 + PM_EMAX) * sizeof(int)) != hipSuccess) {
-        (void)hipGetLastError();
-        return IMPDAR_OK;
-    }
+    *room = ps_ensure_all({{&pl.d_pn_corr, corr.size() * sizeof(T) + 16}});
+    if (!*room) return IMPDAR_OK;
     for (int l = 5; l <= 13; ++l)
         if (need[l - 1]) {
             int rc = pl.pn_tw[l].ensure<T>(1 << l, st);
             if (rc) return rc;
         }
     for (int l = 0; l < 14; ++l) Q.tw[l] = pl.pn_tw[l].buf.p;
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pn_pieces.p, pc.data(), pc.size() * sizeof(PnPiece), hipMemcpyHostToDevice, st));
     if (grew || pl.pn_corr_dev != (int)sizeof(T)) {
         IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pn_corr.p, corr.data(), corr.size() * sizeof(T), hipMemcpyHostToDevice, st));
         pl.pn_corr_dev = (int)sizeof(T);
     }
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_rw.p, rw.data(), rw.size() * 8, hipMemcpyHostToDevice, st));
+    Q.corr = pl.d_pn_corr.p;
+    return IMPDAR_OK;
+}
+
+// ---- transform path (ps_nufft.h): pieces (pn_plan), correction tables, launch
+template <typename T>
+static int ps_nufft_run(PsPlan &pl, PsParams &P, const PsRoute &R, const PsCall &c, const PsAttempt &, hipStream_t st, bool *done, const char **kernel)
+{
+    constexpr bool dbl = sizeof(T) == 8;
+    *done = false;
+    *kernel = "ps_nufft_kernel";
+    const bool vz = c.vlen != 0;
+    const int snum = P.snum, tnum = P.tnum, nf = P.nf;
+    double dw;
+    if (!pn_gate((int)R.runs.size(), nf, snum, P.herm != 0) || (vz && ps_known_overflow(pl, c.kx, tnum, R.runs)) ||
+        (vz && !ps_thr_off_band(R.thr.data(), snum)) || !ps_axis_uniform(R.w.data(), nf, 1e-9, &dw))
+        return IMPDAR_OK;
+    // a pair of rows per workgroup, as ps_runs_kernel's -- where the sums go on into the inverse transform: the rows are written as
+    // their Hermitian combination and its conjugate (ps_nufft_kernel<T, true>)
+    const bool pairs = !c.tk_out && tnum % 2 == 0 && ps_mirror_rows(P, R);
+    if (P.fhalf && !pairs) return IMPDAR_OK;           // (the half layout is read by the pairs only; ps_run repeats the transforms)
+    // float64 data, v(z): the per-step velocities too -- the runs' rounding noise enters as a first-order term (ps_nufft.h)
+    const bool first_order = dbl && vz;
+    PnPlan plan;
+    if (!pn_plan(plan, R.runs, vz, dbl, pairs, nf, snum, P.herm != 0, first_order ? c.vmig : nullptr)) return IMPDAR_OK;
+    const std::vector<PnPiece> &pc = plan.pieces;
+    PnParams Q;
+    PsMfmaParams E;
+    std::vector<double> rw;
+    bool room;
+    int rc;
+    if (!ps_ensure_all({{&pl.d_pn_e1, plan.e1.size() * 8}, {&pl.d_pn_pieces, pc.size() * sizeof(PnPiece)}, {&pl.d_rw, (size_t)nf * 8}})) return IMPDAR_OK;
+    if ((rc = ps_grid_tables<T>(pl, plan.need, Q, st, &room)) || !room) return rc;
+    if ((rc = ps_edge_prepare(pl, P, vz, st, E, &room)) || !room) return rc;
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pn_pieces.p, pc.data(), pc.size() * sizeof(PnPiece), hipMemcpyHostToDevice, st));
+    if ((rc = ps_rw_upload(pl, R, nf, rw, st))) return rc;
     Q.e1 = nullptr;
     if (first_order) {
-        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pn_e1.p, e1.data(), e1.size() * 8, hipMemcpyHostToDevice, st));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pn_e1.p, plan.e1.data(), plan.e1.size() * 8, hipMemcpyHostToDevice, st));
         Q.e1 = pl.d_pn_e1.as<double>();
     }
     Q.P = P;
     Q.pieces = pl.d_pn_pieces.as<PnPiece>();
     Q.npieces = (int)pc.size();
     Q.rw = pl.d_rw.as<double>();
-    Q.corr = pl.d_pn_corr.p;
-    Q.edge_cnt = pl.d_edge.as<int>();
-    Q.edge_list = Q.edge_cnt + tnum;
+    Q.edge_cnt = E.edge_cnt;
+    Q.edge_list = E.edge_list;
     Q.vz = vz ? 1 : 0;
-    if (vz) IMPDAR_HIP_CHECK(hipMemsetAsync(Q.edge_cnt, 0, (size_t)tnum * sizeof(int), st));
-    {
-        int lmax = 4;
-        for (int l = 0; l < 13; ++l)
-            if (need[l]) lmax = l;
-        Q.gmax = 2 << lmax;
-    }
+    Q.gmax = plan.gmax;
     if (pairs) {
         IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)ps_nufft_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)pn_lds_bytes<T>(2 * pn_lmax<T>(true), sizeof(T) == 8, true)));
@@ -1865,56 +1776,29 @@ static int ps_nufft_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &ru
         IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)ps_nufft_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pn_lds_bytes<T>(2 * PnCfg<T>::LMAX, sizeof(T) == 8)));
         hipLaunchKernelGGL(ps_nufft_kernel<T>, dim3((unsigned)P.nk), dim3(PnCfg<T>::NTH), pn_lds_bytes<T>(Q.gmax, first_order), st, Q);
     }
-    if (vz) {
-        PsMfmaParams E;                        // (ps_edge_kernel reads P and the lists only)
-        E.mfma_count = nullptr;
-        E.P = P;
-        E.nruns = 0;
-        E.pairs = 0;
-        E.edge_cnt = Q.edge_cnt;
-        E.edge_list = Q.edge_list;
-        hipLaunchKernelGGL(ps_edge_kernel_t<T>, dim3(P.nk), dim3(256), 0, st, E);
-    }
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(st));            // (the host tables must outlive their copies)
-    if (vz) {
-        std::vector<int> cnt((size_t)P.nk);
-        IMPDAR_HIP_CHECK(hipMemcpy(cnt.data(), Q.edge_cnt + P.k0, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int worst = 0;
-        for (int c : cnt) worst = std::max(worst, c);
-        if (worst > PM_EMAX) {
-            ps_note_overflow(pl, kx_host, tnum, runs);
-            return IMPDAR_OK;                  // contributions missing from TK: discarded, another path produces the result
-        }
-    }
+    int worst;
+    if ((rc = ps_edge_finish<T>(pl, R, c, E, vz, nullptr, st, &worst)) || worst > PM_EMAX) return rc;
     *done = true;
     return IMPDAR_OK;
 }
 
-// ---- series path (ps_series.h): any v(z) profile -- pieces from the planner (ps_series_plan.h, cached per profile), tables, launch.
-// Same contract as ps_mfma_run: *done = false and IMPDAR_OK when the call is not for this path.
+// ---- series path (ps_series.h): any v(z) profile -- pieces from the planner (ps_series_plan.h, cached per profile), tables, launch
 template <typename T>
-static int ps_series_run(PsPlan &pl, PsParams P, const double *vmig, const double *kx_host, const double *w_host, const double *thr,
-                         hipStream_t st, bool *done, double alt_ms_8192 = 0.0, bool allow_pairs = false)
+static int ps_series_run(PsPlan &pl, PsParams &P, const PsRoute &R, const PsCall &c, const PsAttempt &a, hipStream_t st, bool *done, const char **kernel)
 {
-    // allow_pairs: as ps_nufft_run's -- the sums go on into the inverse transform: rows k and tnum - k as their Hermitian combination
-    // alt_ms_8192 > 0: what the kernel that would take the call otherwise is expected to need (per 8192 wavenumbers); the call is
+    // a.alt > 0: what the kernel that would take the call otherwise is expected to need (per 8192 wavenumbers); the call is
     // taken only where the estimate from the planner.s model is SR_MARGIN (0.9) of that or less.  0: taken regardless (IMPDAR_PS_MFMA=7)
     *done = false;
+    *kernel = "ps_series_kernel";
+    const double *vmig = c.vmig, alt_ms_8192 = a.alt;
     const int snum = P.snum, tnum = P.tnum, nf = P.nf;
     constexpr bool dbl = sizeof(T) == 8;
-    if (!P.herm || nf < 64 || nf > SR_NFMAX || snum < 32) return IMPDAR_OK;
-    for (int i = 0; i < snum; ++i)
-        if (!(thr[i] < 1e-10) || !std::isfinite(vmig[i]) || vmig[i] == 0.0) return IMPDAR_OK;   // the evanescence test must be the sign of coss off the boundary band
-    // the gather inverts the dispersion relation on a uniform frequency axis: slot i + 1 at (i + 1) dw, the Nyquist row (slot 0) at nf dw
+    if (!P.herm || nf < 64 || nf > SR_NFMAX || snum < 32 || !R.vfinite || !ps_thr_off_band(R.thr.data(), snum)) return IMPDAR_OK;
     // (the kernel's coefficients take w = (i + 1) dw: the axis must be that to rounding -- 2 pi fftfreq is)
-    const double dw = w_host[1];
-    if (!(dw > 0.0)) return IMPDAR_OK;
-    for (int i = 1; i < nf; ++i)
-        if (std::fabs(w_host[i] - (double)i * dw) > 2e-15 * (double)i * dw) return IMPDAR_OK;
-    if (std::fabs(std::fabs(w_host[0]) - (double)nf * dw) > 2e-15 * (double)nf * dw) return IMPDAR_OK;
+    double dw;
+    if (!ps_axis_uniform(R.w.data(), nf, 2e-15, &dw)) return IMPDAR_OK;
     double kxh_max = 0.0;
-    for (int k = 0; k < tnum; ++k) kxh_max = std::max(kxh_max, 0.5 * std::fabs(kx_host[k]));
+    for (int k = 0; k < tnum; ++k) kxh_max = std::max(kxh_max, 0.5 * std::fabs(c.kx[k]));
     if (!(kxh_max > 0.0) || !std::isfinite(kxh_max)) return IMPDAR_OK;
     SrHostPlan &hp = pl.sr_plan;
     const bool same = hp.v.size() == (size_t)snum && memcmp(hp.v.data(), vmig, (size_t)snum * 8) == 0 && hp.dt == P.dt && hp.dw == dw &&
@@ -1929,12 +1813,11 @@ static int ps_series_run(PsPlan &pl, PsParams P, const double *vmig, const doubl
         impdar_trace("ps_series: %zu pieces", hp.pieces.size());
     }
     if (hp.pieces.empty() || hp.pieces.size() > 4096) return IMPDAR_OK;
-    // the whole wavenumber axis with kx[tnum - k] = -kx[k]: a pair of rows per workgroup (ps_series_kernel<T, true>)
+    // a pair of rows per workgroup (ps_series_kernel<T, true>), as ps_nufft_run's.
     // float32 only: on float64 data the pair's records take the frequencies through LDS in four rounds of two gather passes each and the
     // kernel spills twice as much -- 8192^2: rising gradient 368 -> 365 ms, falling 274 -> 312, firn column 66 -> 72 (float32: 110 -> 77.5,
     // 52 -> 41, 14.7 -> 11.5; profiles/r06_series.txt section 7)
-    bool pairs = !dbl && allow_pairs && P.k0 == 0 && P.nk == tnum && tnum >= 2 && tnum % 2 == 0 && !P.fhalf;
-    for (int k = 1; 2 * k < tnum && pairs; ++k) pairs = kx_host[k] == -kx_host[tnum - k];
+    const bool pairs = !dbl && !c.tk_out && tnum % 2 == 0 && !P.fhalf && ps_mirror_rows(P, R);
     if (alt_ms_8192 != 0.0) {
         // (alt < 0: per alive pair -- the per-step kernels)
         const double alt = alt_ms_8192 > 0.0 ? alt_ms_8192 : -alt_ms_8192 * hp.alive_pairs;
@@ -1947,41 +1830,24 @@ static int ps_series_run(PsPlan &pl, PsParams P, const double *vmig, const doubl
     bool need[13] = {};
     for (const SrPiece &pc : hp.pieces) need[pc.loglp] = true;
     SrParams Q;
-    bool grew = false;
-    std::vector<T> &corr = pn_corr_tables<T>(pl, need, Q.corr_off, &grew);
-    std::vector<double> rw((size_t)nf);
-    for (int i = 0; i < nf; ++i) rw[i] = 1.0 / w_host[i];
+    std::vector<double> rw;
     std::vector<T> ev(hp.ev.begin(), hp.ev.end());
-    if (pl.d_sr_pieces.ensure(hp.pieces.size() * sizeof(SrPiece)) != hipSuccess || pl.d_sr_ev.ensure(ev.size() * sizeof(T) + 16) != hipSuccess ||
-        pl.d_pn_corr.ensure(corr.size() * sizeof(T) + 16) != hipSuccess || pl.d_rw.ensure(rw.size() * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return IMPDAR_OK;
-    }
-    for (int l = 5; l <= 13; ++l)
-        if (need[l - 1]) {
-            int rc = pl.pn_tw[l].ensure<T>(1 << l, st);
-            if (rc) return rc;
-        }
-    {
-        int rc = pl.pn_tw[9].ensure<T>(SR_TWLDS, st);       // (the kernel keeps this one in LDS)
-        if (rc) return rc;
-    }
-    for (int l = 0; l < 14; ++l) Q.tw[l] = pl.pn_tw[l].buf.p;
+    bool room;
+    int rc;
+    if (!ps_ensure_all({{&pl.d_sr_pieces, hp.pieces.size() * sizeof(SrPiece)}, {&pl.d_sr_ev, ev.size() * sizeof(T) + 16}, {&pl.d_rw, (size_t)nf * 8}})) return IMPDAR_OK;
+    if ((rc = ps_grid_tables<T>(pl, need, Q, st, &room)) || !room) return rc;
+    if ((rc = pl.pn_tw[9].ensure<T>(SR_TWLDS, st))) return rc;       // (the kernel keeps this one in LDS)
+    Q.tw[9] = pl.pn_tw[9].buf.p;
     if (!pl.sr_dev) {
         IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sr_pieces.p, hp.pieces.data(), hp.pieces.size() * sizeof(SrPiece), hipMemcpyHostToDevice, st));
         if (!ev.empty()) IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_sr_ev.p, ev.data(), ev.size() * sizeof(T), hipMemcpyHostToDevice, st));
     }
-    if (grew || pl.pn_corr_dev != (int)sizeof(T)) {
-        IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_pn_corr.p, corr.data(), corr.size() * sizeof(T), hipMemcpyHostToDevice, st));
-        pl.pn_corr_dev = (int)sizeof(T);
-    }
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_rw.p, rw.data(), rw.size() * 8, hipMemcpyHostToDevice, st));
+    if ((rc = ps_rw_upload(pl, R, nf, rw, st))) return rc;
     Q.P = P;
     Q.pieces = pl.d_sr_pieces.as<SrPiece>();
     Q.npieces = (int)hp.pieces.size();
     Q.ev = pl.d_sr_ev.p;
     Q.rw = pl.d_rw.as<double>();
-    Q.corr = pl.d_pn_corr.p;
     Q.kxh_max = kxh_max;
     {
         // the grids' LDS doubles as the scratch of the direct sums: the chunk sums of every wave and lane + one group's [L] partial sums
@@ -2008,88 +1874,49 @@ static int ps_series_run(PsPlan &pl, PsParams P, const double *vmig, const doubl
     return IMPDAR_OK;
 }
 
-// ---- matrix-core path (ps_mfma.h): eligibility, row-block table, launch ---------------------------------------
-// runs: (velocity, first step, length) of every constant-velocity run (one run for a constant velocity).  Returns
-// IMPDAR_OK with *done = true when the frequency sums were produced here; *done = false: not eligible, the vector
-// kernels take the call.
-static int ps_mfma_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &runs, bool vz, const double *kx_host, const double *thr,
-                       bool force_overflow, hipStream_t st, bool *done, const char **kernel_name)
+// ---- matrix-core path (ps_mfma.h): row-block table (pm_plan), launch
+static int ps_mfma_run(PsPlan &pl, PsParams &P, const PsRoute &R, const PsCall &c, const PsAttempt &, hipStream_t st, bool *done, const char **kernel)
 {
     *done = false;
-    *kernel_name = "ps_mfma_kernel";
+    *kernel = "ps_mfma_kernel";
+    const bool vz = c.vlen != 0;
     const int snum = P.snum, tnum = P.tnum;
-    if (vz && ps_known_overflow(pl, kx_host, tnum, runs)) return IMPDAR_OK;
-    if (P.nf % (PM_CH * PM_NQ) != 0 || P.nf < 256 || P.nf > 4096 + 2048 || snum < 256 || runs.empty() || (int)runs.size() > PM_MAX_RUNS) return IMPDAR_OK;
-    if (vz)
-        for (int i = 0; i < snum; ++i)
-            if (!(thr[i] < 1e-10)) return IMPDAR_OK;       // the evanescence test must be the sign of coss off the boundary band
-    // row blocks: 32 tiles of 64 steps of one run; runs of a few steps (a layer boundary smeared over 3-4 steps by
-    // 2 * gradient(z(t))) get none: ps_trans_kernel sums their steps directly
-    std::vector<int2> blocks;
-    int nshort_steps = 0;
-    for (size_t r = 0; r < runs.size(); ++r) {
-        if (vz && runs[r].len <= PM_SHORT) {
-            nshort_steps += runs[r].len;
-            continue;
-        }
-        const int ntile = (runs[r].len + PM_TT - 1) / PM_TT;
-        for (int a0 = 0; a0 < ntile; a0 += 32) blocks.push_back(make_int2((int)r, a0));
-    }
-    const int nb = (int)blocks.size();
-    // limits of the matrix-core path: long runs, row padding (blocks x 2048 steps against the record), steps in short
-    // runs.  A row block costs ~2.4 ms at 8192^2 and the vector runs kernels ~40-50 ms for the whole record: 16 runs /
-    // 3 x padding is where the two meet (a 21-row table of equal layers: 44.5 -> 38.1 ms; profiles/r03_ps_layers.txt)
-    constexpr int max_long = 16, max_short = 200;
-    constexpr double max_pad = 3.0;
-    if (nb == 0 || nshort_steps > max_short || (int)runs.size() - (vz ? (int)std::count_if(runs.begin(), runs.end(), [](const PsMfmaRun &r) { return r.len <= PM_SHORT; }) : 0) > max_long) return IMPDAR_OK;
-    if ((double)nb * 32 * PM_TT > (double)snum * max_pad + 32 * PM_TT) return IMPDAR_OK;      // many medium runs: rows mostly padding
-    // groups of up to PM_NRB row blocks (the state tiles a workgroup keeps in LDS), consecutive blocks together
-    int ngroups = (nb + PM_NRB - 1) / PM_NRB;
-    const int per_group = (nb + ngroups - 1) / ngroups;
-    std::vector<int2> table((size_t)ngroups * PM_NRB, make_int2(-1, 0));
-    for (int g = 0, at = 0; g < ngroups; ++g) {
-        const int n = std::min(per_group, nb - at);
-        for (int i = 0; i < n; ++i, ++at) table[(size_t)g * PM_NRB + i] = blocks[at];
-    }
+    const std::vector<PsMfmaRun> &runs = R.runs;
+    if ((vz && ps_known_overflow(pl, c.kx, tnum, runs)) || !pm_gate((int)runs.size(), P.nf, snum) || (vz && !ps_thr_off_band(R.thr.data(), snum))) return IMPDAR_OK;
+    PmPlan plan;
+    if (!pm_plan(plan, runs, vz, P.nf, snum)) return IMPDAR_OK;
     PsMfmaParams Q;
-    Q.P = P;
     Q.nruns = (int)runs.size();
     for (int r = 0; r < Q.nruns; ++r) Q.runs[r] = runs[r];
     for (int r = Q.nruns; r < PM_MAX_RUNS; ++r) Q.runs[r] = PsMfmaRun{0.0, 0, 0};
-    Q.ngroups = ngroups;
+    Q.ngroups = plan.ngroups;
+    Q.nlong = plan.nlong;
+    std::copy(plan.long_of, plan.long_of + PM_MAX_RUNS, Q.long_of);
     // The path's own buffers (runtab: 16 bytes per wavenumber, frequency and long run -- 8.6 GB for 16 runs at
     // 8192 x 4096).  Not getting them is not an error: the vector kernels need none of it and take the call.
-    Q.nlong = 0;
-    for (int r = 0; r < PM_MAX_RUNS; ++r) Q.long_of[r] = -1;
-    for (int r = 0; r < Q.nruns; ++r)
-        if (!(vz && runs[r].len <= PM_SHORT)) Q.long_of[r] = Q.nlong++;
-    {
-        const size_t rt_bytes = (size_t)P.nk * P.nf * Q.nlong * sizeof(double2);
-        size_t free_b = 0, total_b = 0;
-        if (rt_bytes > pl.d_runtab.bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && rt_bytes > free_b / 2) {
-            (void)hipGetLastError();
-            return IMPDAR_OK;                  // would take more than half of what is free: leave it to the vector kernels
-        }
-        if (pl.d_blocks.ensure(table.size() * sizeof(int2)) != hipSuccess ||
-            pl.d_edge.ensure((size_t)tnum * (1 + PM_EMAX) * sizeof(int)) != hipSuccess || pl.d_runtab.ensure(rt_bytes) != hipSuccess ||
-            pl.d_mcount.ensure(8) != hipSuccess) {
-            (void)hipGetLastError();
-            return IMPDAR_OK;
-        }
+    const size_t rt_bytes = (size_t)P.nk * P.nf * Q.nlong * sizeof(double2);
+    size_t free_b = 0, total_b = 0;
+    if (rt_bytes > pl.d_runtab.bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && rt_bytes > free_b / 2) {
+        (void)hipGetLastError();
+        return IMPDAR_OK;                  // would take more than half of what is free: leave it to the vector kernels
     }
-    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_blocks.p, table.data(), table.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+    PsMfmaParams E;
+    bool room;
+    int rc;
+    static_assert(sizeof(PmBlock) == sizeof(int2), "the row-block table is the kernel's int2 array");
+    if (!ps_ensure_all({{&pl.d_blocks, plan.table.size() * sizeof(PmBlock)}, {&pl.d_runtab, rt_bytes}, {&pl.d_mcount, 8}})) return IMPDAR_OK;
+    if ((rc = ps_edge_prepare(pl, P, vz, st, E, &room)) || !room) return rc;
+    IMPDAR_HIP_CHECK(hipMemcpyAsync(pl.d_blocks.p, plan.table.data(), plan.table.size() * sizeof(PmBlock), hipMemcpyHostToDevice, st));
+    Q.P = P;
     Q.blocks = pl.d_blocks.as<int2>();
-    Q.edge_cnt = pl.d_edge.as<int>();
-    Q.edge_list = Q.edge_cnt + tnum;
-    if (vz) IMPDAR_HIP_CHECK(hipMemsetAsync(Q.edge_cnt, 0, (size_t)tnum * sizeof(int), st));
+    Q.edge_cnt = E.edge_cnt;
+    Q.edge_list = E.edge_list;
     Q.mfma_count = pl.d_mcount.as<unsigned long long>();
     IMPDAR_HIP_CHECK(hipMemsetAsync(Q.mfma_count, 0, 8, st));
     Q.vz = vz ? 1 : 0;
     Q.runtab = pl.d_runtab.as<double2>();
-    // the whole wavenumber axis with kx[tnum - k] = -kx[k]: rows k and tnum - k turn by the same angles -- one set-up walk and
-    // one table row for both; a slab of a kx-sharded run has no mirror rows
-    bool sym = P.k0 == 0 && P.nk == tnum && tnum >= 2;
-    for (int k = 1; 2 * k < tnum && sym; ++k) sym = kx_host[k] == -kx_host[tnum - k];      // (the Nyquist row of an even axis is its own partner)
+    // rows k and tnum - k turn by the same angles -- one set-up walk and one table row for both
+    const bool sym = ps_mirror_rows(P, R);
     Q.pairs = sym ? 1 : 0;
     {
         // set-up pass: per-run phases of every (wavenumber, frequency), boundary frequencies, the steps of the short runs
@@ -2101,27 +1928,11 @@ static int ps_mfma_run(PsPlan &pl, PsParams P, const std::vector<PsMfmaRun> &run
     }
     IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)ps_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PM_LDS_BYTES));
     hipLaunchKernelGGL(ps_mfma_kernel, dim3((unsigned)P.nk * Q.ngroups), dim3(PM_WAVES * 64), PM_LDS_BYTES, st, Q);
-    if (vz) hipLaunchKernelGGL(ps_edge_kernel_t<float>, dim3(P.nk), dim3(256), 0, st, Q);
-    IMPDAR_HIP_CHECK(hipGetLastError());
-    // the host table must outlive its async copy
-    IMPDAR_HIP_CHECK(hipStreamSynchronize(st));
-    if (vz) {
-        // ps_setup_kernel takes every boundary frequency out of the matrix-core sums but lists only the first PM_EMAX per
-        // wavenumber for ps_edge_kernel (more needs a table of many runs on a rational grid).  The counter keeps
-        // counting: an overflow means contributions are missing from TK -- the result is discarded and the vector
-        // kernels, which walk every boundary frequency themselves, produce it.
-        std::vector<int> cnt((size_t)P.nk);
-        IMPDAR_HIP_CHECK(hipMemcpy(cnt.data(), Q.edge_cnt + P.k0, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int worst = 0;
-        for (int c : cnt) worst = std::max(worst, c);
-        if (worst > PM_EMAX) ps_note_overflow(pl, kx_host, tnum, runs);    // (remembered: not tried again on this geometry)
-        if (worst > PM_EMAX || force_overflow) return IMPDAR_OK;           // *done stays false
-    }
-    {
-        unsigned long long n = 0;
-        IMPDAR_HIP_CHECK(hipMemcpy(&n, Q.mfma_count, 8, hipMemcpyDeviceToHost));
-        pl.mfma_instructions = (double)n;
-    }
+    // (an overflow, or IMPDAR_PS_TEST_EDGE_OVERFLOW behaving as one: *done stays false, the vector kernels, which walk every
+    // boundary frequency themselves, produce the result)
+    int worst;
+    if ((rc = ps_edge_finish<float>(pl, R, c, E, vz, nullptr, st, &worst)) || worst > PM_EMAX || (vz && c.K.edge_overflow)) return rc;
+    if ((rc = ps_mcount_read(pl))) return rc;
     *done = true;
     return IMPDAR_OK;
 }
@@ -2333,14 +2144,14 @@ static int ps_order_rows(PsPlan &pl, PsParams &P, const PsRoute &R, std::vector<
 // no runs of constant velocity to live on (the velocity changes in most 16-step tiles): ps_smooth_kernel.  Declines (*done
 // false) on a profile that is not finite, a vertical taper inside the record, or no room for the partial images.
 template <typename T>
-static int ps_smooth_run(PsPlan &pl, PsParams &P, const PsRoute &R, const double *vmig, hipStream_t st, bool *done)
+static int ps_smooth_run(PsPlan &pl, PsParams &P, const PsRoute &R, const PsCall &c, const PsAttempt &, hipStream_t st, bool *done, const char **kernel)
 {
-    const int snum = P.snum, tnum = P.tnum;
+    const int snum = P.snum;
+    const double *vmig = c.vmig;
     *done = false;
-    for (int i = 0; i < snum; ++i)
-        if (!(std::isfinite(vmig[i]) && vmig[i] != 0.0 && R.thr[i] < 1e-10)) return IMPDAR_OK;
+    if (!R.vfinite || !ps_thr_off_band(R.thr.data(), snum)) return IMPDAR_OK;
     // float32, the whole wavenumber axis with kx[tnum - k] = -kx[k]: rows k and tnum - k in one wave (ps_smooth.h)
-    const bool sm_pairs = P.k0 == 0 && P.nk == tnum && tnum >= 2 && R.kx_antisym;
+    const bool sm_pairs = ps_mirror_rows(P, R);
     P.sm_m = ps_smooth_m(sizeof(T) == 8, sm_pairs);
     P.sm_nchunks = ps_smooth_chunks(R.nf, P.sm_m);
     const size_t part_bytes = P.sm_nchunks > 1 ? (size_t)P.sm_nchunks * P.nk * snum * sizeof(Cp<T>) : 0;
@@ -2360,7 +2171,7 @@ static int ps_smooth_run(PsPlan &pl, PsParams &P, const PsRoute &R, const double
     P.sm_part = pl.d_part.p;
     ps_smooth_launch<T>(P, st, sm_pairs);
     IMPDAR_HIP_CHECK(hipGetLastError());
-    t_ps_kernel = sizeof(T) == 4 ? "ps_smooth32_kernel" : "ps_smooth_kernel";
+    *kernel = sizeof(T) == 4 ? "ps_smooth32_kernel" : "ps_smooth_kernel";
     *done = true;
     return IMPDAR_OK;
 }
@@ -2483,6 +2294,10 @@ static int ps_run(impdar_ctx *ctx, PsPlan &pl, const void *d_data, int snum, int
     bool done = false;
     const char *kernel = "";
     pl.mfma_instructions = -1.0;
+    using PsRunner = int (*)(PsPlan &, PsParams &, const PsRoute &, const PsCall &, const PsAttempt &, hipStream_t, bool *, const char **);
+    static const PsRunner runners[] = {ps_series_run<T>, ps_nufft_run<T>, ps_runs_run, ps_mfma_run, ps_smooth_run<T>};      // by PsAttemptKind
+    static_assert(PS_SERIES == 0 && PS_NUFFT == 1 && PS_RUNS == 2 && PS_MFMA == 3 && PS_SMOOTH == 4, "the runners in the order of their kinds");
+    const PsCall call{kx, vmig, vlen, tk_out != nullptr, K};
     for (const PsAttempt &a : R.attempts) {
         // Only ps_nufft_kernel reads the half layout: a call it handed on gets the other one (SERIES never meets fhalf: its conditions exclude half_front's)
         if (P.fhalf && a.kind != PS_NUFFT) {
@@ -2491,32 +2306,13 @@ static int ps_run(impdar_ctx *ctx, PsPlan &pl, const void *d_data, int snum, int
             P.fstride = R.fstride;
             if ((rc = ps_front_full<T>(pl, P, R, d_data, htaper, vtaper, st))) return rc;
         }
-        switch (a.kind) {
-        case PS_SERIES:
-            rc = ps_series_run<T>(pl, P, vmig, kx, R.w.data(), R.thr.data(), st, &done, a.alt, tk_out == nullptr);
-            kernel = "ps_series_kernel";
-            break;
-        case PS_NUFFT:      // (float64 v(z): the per-step velocities too -- the runs' rounding noise as a first-order term)
-            rc = ps_nufft_run<T>(pl, P, R.runs, vlen != 0, kx, R.w.data(), R.thr.data(), st, &done, R.kx_antisym, dbl && vlen ? vmig : nullptr,
-                                 tk_out == nullptr);
-            kernel = "ps_nufft_kernel";
-            break;
-        case PS_RUNS:
-            rc = ps_runs_run(pl, P, R.runs, kx, R.w.data(), R.thr.data(), st, &done);
-            kernel = "ps_runs_kernel";
-            break;
-        case PS_MFMA:
-            rc = ps_mfma_run(pl, P, R.runs, vlen != 0, kx, R.thr.data(), K.edge_overflow, st, &done, &kernel);
-            break;
-        case PS_SMOOTH:
-            if ((rc = ps_smooth_run<T>(pl, P, R, vmig, st, &done))) return rc;
-            if (done) kernel = t_ps_kernel;
-            break;
-        default:            // PS_VECTOR; with a schedule, the launch order of its runs kernels is made now
+        if (a.kind == PS_VECTOR) {      // with a schedule, the launch order of its runs kernels is made now
             if (R.use_sched && (rc = ps_order_rows(pl, P, R, rowmap, kx, ws, vmig, dbl, st))) return rc;
             if ((rc = ps_dispatch<T>(P, st))) return rc;
             kernel = t_ps_kernel;
             done = true;
+        } else {
+            rc = runners[a.kind](pl, P, R, call, a, st, &done, &kernel);
         }
         if (rc) return rc;
         if (done) {

@@ -48,13 +48,13 @@
 // Frequencies on the evanescent boundary of some run (|coss| < 1e-8: kept or dropped by the reference at every
 // step's own velocity, mig_python.py:456-485) take no part: they are listed per wavenumber and ps_edge_kernel walks
 // them over the whole depth axis in float64 afterwards, the way the reference does.
+// PsMfmaRun, PM_SHORT, PM_TT, PM_NRB, PM_EMAX, PM_MAX_RUNS, with the host-side plan of the row blocks and groups (pm_plan): ps_path_plan.h.
 #pragma once
-#include "ps_route.h"        // PsMfmaRun, PM_SHORT
+#include "ps_route.h"        // (includes ps_path_plan.h)
 
 typedef _Float16 pm_half8 __attribute__((ext_vector_type(8)));
 typedef float pm_float16 __attribute__((ext_vector_type(16)));
 
-constexpr int PM_TT = 64;                   // depth steps per tile
 #ifndef PM_CHUNK
 #define PM_CHUNK 32      // 16 (three waves per SIMD, 168 VGPRs) measured 12.1 / 20.2 ms at config 5 against 11.3 / 19.1 ms for 32 (two waves): the per-frequency sincos work doubles
 #endif
@@ -64,18 +64,16 @@ constexpr int PM_ROW = PM_CH;               // dwords per tile row (one complex 
 constexpr int PM_NSLOT = PM_ROW / 4;        // 16-byte slots per row
 constexpr int PM_TILE = 32 * PM_ROW;        // dwords per tile (hi or lo halves of 32 rows): 2 or 4 KB
 constexpr int PM_NQ = 1, PM_NP = 4;         // waves of a workgroup: (one frequency part) x step blocks of 16
-constexpr int PM_NRB = 5;                   // row blocks per group (state tiles per frequency half, accumulators per wave)
 constexpr int PM_WAVES = PM_NQ * PM_NP;
+static_assert(PM_SLOTS == PM_CH * PM_NQ, "the frequency slots the host plans by (ps_path_plan.h)");
 constexpr int PM_RED_LD = 20;               // dwords per lane in the final reduction image (16 + 4: conflict-free b128)
-constexpr int PM_EMAX = 16;                 // boundary frequencies listed per wavenumber
-constexpr int PM_MAX_RUNS = 96;
 constexpr size_t PM_LDS_BYTES = ((size_t)PM_NQ * PM_NRB * 2 + (size_t)PM_WAVES * 2) * PM_TILE * 4 + 64;
 
 struct PsMfmaParams {
     PsParams P;
     PsMfmaRun runs[PM_MAX_RUNS];
     int nruns;
-    const int2 *blocks;     // [ngroups][PM_NRB]: (run, first tile inside the run) of every row block; run = -1: none
+    const int2 *blocks;     // [ngroups][PM_NRB]: (run, first tile inside the run) of every row block; run = -1: none (the host's PmBlock)
     int ngroups;
     int *edge_cnt;          // [tnum] boundary frequencies found for the wavenumber (v(z))
     int *edge_list;         // [tnum][PM_EMAX] their slots

@@ -32,8 +32,9 @@
 // velocity the reference's own test decides them (:411-412).
 // Measured at 8192^2: round 5 (profiles/r05_ps_nufft.txt) config 5 3.7 ms (ps_mfma_kernel 9.1), constant velocity 1.6 ms (5.3);
 // round 6 with pairs (profiles/r06_transforms.txt) 1.64 and 0.90 ms; float64 data 6.7 and 4.0 ms.
+// PnPiece, PN_NFMAX, PN_SHORT and the piece lengths, with the host-side plan of the pieces (pn_plan, pn_corr_of_length): ps_path_plan.h.
 #pragma once
-#include "ps_route.h"        // PN_NFMAX, PN_SHORT
+#include "ps_route.h"        // (includes ps_path_plan.h)
 
 // float32 data: a window of 8 grid points (3.5e-7 of the result in float32 arithmetic), 1024 threads;
 // float64 data: 14 points (5e-13 in float64 arithmetic; the stated bar against the reference is 1e-10), 512 threads.
@@ -46,17 +47,9 @@
 // one more accumulation per window value and 17 KB of LDS instead of a second float64 grid.
 template <typename T> struct PnCfg;
 // LMAX: steps per piece at most (G = 2 LMAX grid points): spreading and coefficients cost per PIECE -- as long as LDS allows
-template <> struct PnCfg<float> { static constexpr int W = 8, NTH = 1024, OCC = 1, LMAX = 4096; };
-template <> struct PnCfg<double> { static constexpr int W = 14, NTH = 512, OCC = 1, LMAX = 1024; };       // (1024 threads at 128 registers: 54 spilled, 9.34 -> 9.82 ms at 8192^2)
+template <> struct PnCfg<float> { static constexpr int W = 8, NTH = 1024, OCC = 1, LMAX = PN_LMAX_F32; };
+template <> struct PnCfg<double> { static constexpr int W = 14, NTH = 512, OCC = 1, LMAX = PN_LMAX_F64; };       // (1024 threads at 128 registers: 54 spilled, 9.34 -> 9.82 ms at 8192^2)
 
-struct PnPiece {
-    double v;               // velocity (kind 0)
-    int start, len;         // first depth step, steps
-    int kind;               // 0: transform, 1: direct sums (len <= PN_SHORT steps, each at its own velocity: the single steps of a
-                            // smeared layer boundary, and short runs, taken in ONE pass over the frequencies)
-    int loglp;              // kind 0: log2 of the padded length Lp >= len (G = 2 Lp)
-    double vs[PN_SHORT];    // kind 1: the steps' velocities
-};
 struct PnParams {
     PsParams P;
     const PnPiece *pieces;
@@ -76,7 +69,7 @@ struct PnParams {
 // with a quarter's arrays LDS has room for pieces of 2048 steps: half as many pieces, and a piece's cost -- coefficients, window
 // values -- does not depend on its length
 template <typename T> __host__ __device__ constexpr int pn_halves(bool pair) { return pair && sizeof(T) == 8 ? 4 : 1; }
-template <typename T> __host__ __device__ constexpr int pn_lmax(bool pair) { return pair && sizeof(T) == 8 ? 2 * PnCfg<T>::LMAX : PnCfg<T>::LMAX; }
+template <typename T> __host__ __device__ constexpr int pn_lmax(bool pair) { return pn_lmax_steps(sizeof(T) == 8, pair); }
 template <typename T> __host__ __device__ constexpr size_t pn_lds_bytes(int gmax, bool first_order = false, bool pair = false)
 {
     // (coefficient, fraction and floor of the grid place: three arrays -- one 16-byte record per frequency and a ds_read_b128 per

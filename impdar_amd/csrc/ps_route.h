@@ -5,6 +5,7 @@
 // frequency axis, lists that overflow, no memory) and hand the call to the next attempt of the list.
 #pragma once
 #include "own_fft_len.h"
+#include "ps_path_plan.h"      // PsMfmaRun, PM_SHORT, PN_SHORT, PN_NFMAX; the planners of the paths under the attempts
 #include "ps_series_plan.h"
 #include <algorithm>
 #include <cmath>
@@ -12,15 +13,6 @@
 #include <cstring>
 #include <utility>
 #include <vector>
-
-constexpr int PM_SHORT = 8;                 // runs of up to this many steps (the few steps a layer boundary is smeared over) get no row blocks: ps_trans_kernel
-constexpr int PN_NFMAX = 4096;              // frequencies per wavenumber ps_nufft_kernel takes (one workgroup holds them all)
-constexpr int PN_SHORT = 8;                 // runs of up to this many steps are summed directly by ps_nufft_kernel
-
-struct PsMfmaRun {
-    double v;               // velocity of the run (v(z)); unused for constant velocity
-    int start, len;         // first depth step, number of steps
-};
 
 // The knobs of a call.  Read per call, not cached: the tests flip them inside one process.
 struct PsKnobs {

@@ -36,20 +36,12 @@
 // blocks x 2 + 1 per wave.  Frequencies on the evanescent boundary of some run take no part and are listed for
 // ps_edge_kernel, as in ps_mfma.h; a frequency that has turned evanescent is out for good (NaN phase), chunks of 32 dead
 // frequencies are skipped.
+// PrRun, PrStage and the PR_* constants of the tiling, with the host-side plan of the runs and stages (pr_plan): ps_path_plan.h.
 #pragma once
+#include "ps_route.h"        // (includes ps_path_plan.h)
 
 typedef float pr_float4 __attribute__((ext_vector_type(4)));
 
-constexpr int PR_TT = 8;            // depth steps per tile
-constexpr int PR_ROWS = 16;         // tiles per block
-constexpr int PR_NM = 4;            // frequencies per thread (super-chunks of 256 slots per part)
-constexpr int PR_PART = PR_NM * 256;
-constexpr int PR_LONGS = 4;         // long runs per stage = waves
-constexpr int PR_NBLK = 4;          // blocks per long run: up to 512 steps
-constexpr int PR_LONG_MAX = PR_NBLK * PR_ROWS * PR_TT;
-constexpr int PR_SHORT_LEN = 2;     // runs of up to this many steps: every step a row of its own
-constexpr int PR_SROWS = 12;        // single-step rows per stage
-constexpr int PR_STAGE_RUNS = 16;   // runs per stage
 constexpr int PR_LD = 32;            // dwords per tile row: 32 frequencies, one float16 pair each; the eight 16-byte slots of row r sit at slot ^ (r & 7):
                                      // both the generating ds_write_b32 and the operands' ds_read_b128 touch every bank once (a padded row of 36
                                      // dwords: SQ_LDS_BANK_CONFLICT 23 % of the LDS cycles, profiles/r05_ps_runs.txt)
@@ -60,20 +52,6 @@ constexpr size_t pr_lds_bytes(int nmem)      // see the kernel's layout
 }
 static_assert(pr_lds_bytes(2) <= 80 * 1024, "two workgroups per CU");
 
-struct PrRun {
-    double v;               // velocity
-    int start, len;         // first depth step, steps
-    int kind;               // 0: long (tiles of 8 steps), 1: single steps
-    int slot;               // long: the wave that multiplies it; short: its first row among the stage's single-step rows
-};
-static_assert(sizeof(PrRun) == 24, "the kernel copies a stage's runs to LDS as 6 words each");
-struct PrStage {
-    int run0, nruns;        // the stage's runs, in depth order
-    int nshort, short_wave; // single-step rows and the wave that multiplies them
-    int long_run[PR_LONGS]; // run of wave p (-1: none)
-    int long_nblk[PR_LONGS];
-    int short_tau[PR_SROWS];
-};
 struct PrParams {
     PsParams P;
     const PrRun *runs;
