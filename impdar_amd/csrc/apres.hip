@@ -16,7 +16,9 @@
 //                          reference crops Rfine on its first axis, not along range).
 //   * stacking: ap_stack_kernel, the mean over `m` consecutive rows of a (rows, snum) float64 or complex128 array: per
 //       output sample a sum in row order, then NumPy's own last step -- a division by m for real data, a product
-//       with 1 / m for complex data (its complex division by (m + 0j)).  Bit for bit numpy.mean(x, axis=1).
+//       with 1 / m for complex data (its complex division by (m + 0j)).  Bit for bit numpy.mean(x, axis=1) of the
+//       (groups, m, snum) view for snum >= 2; at snum = 1 the m-axis is contiguous, NumPy sums it pairwise and differs
+//       from the row-order sum from m = 8 on.
 //   * phase difference: window i covers samples [i step, i step + 2 (win / 2)) of two complex128 vectors;
 //       co[i] = S(s1 conj(s2)) / sqrt(S|s1|^2 S|s2|^2), every S a plain sum in sample order of the lanes' parts (no
 //       running differences); 0 / 0 is NaN in both parts.  ap_phase_diff_thread_kernel gives a window to a thread
