@@ -853,6 +853,49 @@ def main():
                                                "synchronise and free.  Bytes: every input read once, every product written "
                                                "once; the coherence's window sums (32 B per element written and re-read "
                                                "about 2 nrange / bk + bk times from cache) are not counted"}}), flush=True)
+        # the reference's full flow -- rotation, cpe axis, coherence, the coherence along the axis -- timed the same way;
+        # find_cpe's three stages from the library's own events
+        spec = qpm.lowpass_spec(0.1 * 0.5 / 1.0e-8, 1. / 1.0e-8)
+        i0, i1 = int(np.argmin(abs(thetas - np.pi / 4.))), int(np.argmin(abs(thetas - 3. * np.pi / 4.)))
+        cpe_stages = []
+
+        def cpe_call():
+            d = qpm.find_cpe_dev(images[1], spec, i0, i1)
+            lib.impdar_ctx_sync(ctx)
+            cpe_stages.append(qpm.find_cpe_last_ms(ctx))
+            d.free()
+
+        def qp_flow():
+            im = qpm.rotate_dev(d_vec, *factors)
+            idx = qpm.find_cpe_dev(im[1], spec, i0, i1)
+            c = qpm.coherence_dev(im[0], im[3], nrange, ntheta)
+            cc = qpm.cpe_gather_dev(c, idx)
+            lib.impdar_ctx_sync(ctx)
+            free(list(im) + [idx, c, cc])
+        cpe_ms = spread(cpe_call)
+        st = np.array(cpe_stages[1:])
+        cpe_stage_ms = {k: {"min": float(st[:, i].min()), "median": float(np.median(st[:, i])), "max": float(st[:, i].max())}
+                        for i, k in enumerate(("anomaly", "filter", "argmin"))}
+        # anomaly: HV read, both planes written; filter: the planes read and written; argmin: the window read, an int32 written
+        cpe_bytes = {"anomaly": 2 * el * 16, "filter": 2 * el * 16, "argmin": n * (i1 - i0) * 16 + n * 4}
+        flow_bytes = {"rotation": bytes_of["rotation"], "find_cpe": sum(cpe_bytes.values()), "coherence": bytes_of["coherence"],
+                      "gather": n * (16 + 4 + 16)}
+        falgo = sum(flow_bytes.values())
+        flow = spread(qp_flow)
+        fcms = qp_copy(falgo)
+        print(json.dumps({"path": "quadpol flow %d x %d complex128" % (n, n_thetas),
+                          "config": "nrange %d, ntheta %d, Wn 0.1 of Nyquist, window [%d, %d), resident" % (nrange, ntheta, i0, i1),
+                          "device_ms": flow["median"], "device_ms_spread": flow,
+                          "find_cpe_ms": cpe_ms, "find_cpe_stages_ms": cpe_stage_ms, "find_cpe_bytes_per_stage": cpe_bytes,
+                          "hbm_frac_per_stage": {k: cpe_bytes[k] / cpe_stage_ms[k]["median"] / 1e6 / 8000.0 for k in cpe_bytes},
+                          "algorithmic_bytes": falgo, "algorithmic_bytes_per_step": flow_bytes,
+                          "copy_same_bytes_ms": fcms, "time_over_copy": flow["median"] / fcms["median"],
+                          "roofline": {"bound": "hbm", "achieved": falgo / flow["median"] / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                       "frac": falgo / flow["median"] / 1e6 / 8000.0,
+                                       "note": "time per call (host clock around a device synchronise), with the output "
+                                               "allocations and table uploads; the stages of find_cpe are device time between "
+                                               "the library's events.  The filter is a serial fp64 recurrence along range over "
+                                               "2 n_thetas columns: bound by step latency, not HBM"}}), flush=True)
         free(d_vec + list(images) + [d_c])
 
     if 'apres' not in args.skip:

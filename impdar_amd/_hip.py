@@ -115,6 +115,13 @@ SIGNATURES = {
     'impdar_qp_coherence_dev': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_qp_phase_gradient': (_i, [_p, _dp, _i, _i, _i, _d, _dp, _dp, _dp, _dp, _dp, _i, _dp, _dp]),
     'impdar_qp_phase_gradient_dev': (_i, [_p, _p, _i, _i, _i, _d, _dp, _dp, _dp, _dp, _dp, _i, _dp, _p]),
+    'impdar_qp_power_anomaly': (_i, [_p, _dp, _i, _i, _dp]),
+    'impdar_qp_power_anomaly_dev': (_i, [_p, _p, _i, _i, _p]),
+    'impdar_qp_find_cpe': (_i, [_p, _dp, _i, _i, _dp, _dp, _i, _dp, _i, _i, _ip, _dp]),
+    'impdar_qp_find_cpe_dev': (_i, [_p, _p, _i, _i, _dp, _dp, _i, _dp, _i, _i, _p, _p]),
+    'impdar_qp_find_cpe_last_ms': (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    'impdar_qp_cpe_gather': (_i, [_p, _dp, _i, _i, _i, _ip, _dp]),
+    'impdar_qp_cpe_gather_dev': (_i, [_p, _p, _i, _i, _i, _p, _p]),
     'impdar_apres_range': (_i, [_p, _dp, _i, _i, _i, _i, _dp, _dp, _dp, _d, _d, _i, _d, _i, _dp, _dp, _dp]),
     'impdar_apres_range_dev': (_i, [_p, _p, _i, _i, _i, _i, _dp, _dp, _dp, _d, _d, _i, _d, _i, _p, _p, _p]),
     'impdar_apres_range_last_ms': (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

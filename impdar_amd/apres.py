@@ -1,17 +1,21 @@
-"""ApRES range conversion, stacking and phase difference: from raw FMCW voltages to the complex range profile that
-``quadpol.py`` consumes, and to the coherence between two acquisitions.  The functions take any object with the
+"""ApRES range conversion, stacking, phase uncertainty and the time-difference flow: from raw FMCW voltages to the
+complex range profile that ``quadpol.py`` consumes, and from two such profiles to the vertical velocity, the strain
+rate and the bed.  The functions take any object with the
 attributes of the reference's ``ApresData`` / ``ApresTimeDiff`` -- those objects themselves, or the :class:`Apres` and
 :class:`TimeDiff` holders below -- and leave the same attributes and flags behind as NumPy arrays.  The O(n) tables
 (window, ``tau``, ``Rcoarse``, ``phiref``, the reference phasor, the fine-range denominator, the crop) are NumPy
 here, by the reference's own expressions in its order; everything that touches a (chirps, samples) array runs in
 ``csrc/apres.hip`` through the C ABI, on host buffers or, in :func:`chain`, resident in HBM from the raw chirps to
-the stacked profile.
+the stacked profile.  What follows the phase difference -- :func:`phase_unwrap`, :func:`range_diff`,
+:func:`strain_rate`, :func:`bed_pick` -- and :func:`phase_uncertainty` work on vectors of a few hundred to a few
+thousand elements: they are NumPy / SciPy on the host, the reference's expressions in its order, with its messages,
+exception types and quirks.  :func:`single_processing` and :func:`time_diff_processing` are the reference's two
+full flows.
 
-All data is float64 / complex128, as in the reference.  ``phase_uncertainty``, ``phase_unwrap``, ``range_diff``,
-``strain_rate``, ``bed_pick``, loaders and savers are not here.
+All data is float64 / complex128, as in the reference.  Loaders and savers are not here.
 
-Reference: ``src/impdar/lib/ApresData/_ApresDataProcessing.py:24-123`` and ``:156-222``,
-``src/impdar/lib/ApresData/_TimeDiffProcessing.py:57-93``.
+Reference: ``src/impdar/lib/ApresData/_ApresDataProcessing.py:24-222``,
+``src/impdar/lib/ApresData/_TimeDiffProcessing.py:57-247``, ``src/impdar/bin/apdar.py:337-354``.
 """
 import ctypes as C
 import operator
@@ -23,6 +27,13 @@ from . import _hip
 _MSG_RANGE_DONE = 'The range filter has already been done on these data.'
 _MSG_WINDOW = 'Window must be in: blackman, bartlett, hamming, hanning, kaiser'
 _WINDOWS = ['blackman', 'bartlett', 'hamming', 'hanning', 'kaiser']
+_MSG_RANGE_FIRST = ('The range filter has not been executed on this data class, do that before the uncertainty '
+                    'calculation.')
+_MSG_DIFF_FIRST = 'Need to do the phase difference calculation first.'
+_MSG_UNWRAP_FIRST = 'Should unwrap the phase profile before converting to range'
+_MSG_RANGE_DIFF_FIRST = "Get the vertical velocity profile first with 'range_diff()'."
+_MSG_BED_APART = 'Bed pick from first and second acquisitions are too far apart.'
+_MSG_BED_COHERENCE = 'Bed pick has too low coherence.'
 
 
 class ApresFlags(object):
@@ -80,6 +91,7 @@ class Apres(object):
         self.Rcoarse = None
         self.Rfine = None
         self.phiref = None
+        self.uncertainty = None
         self.flags = ApresFlags()
         self.header = ApresHeader()
 
@@ -97,6 +109,13 @@ class TimeDiff(object):
         self.co = None
         self.w = None
         self.data_dtype = None
+        self.unc1 = None
+        self.unc2 = None
+        self.phi = None
+        self.w_err = None
+        self.eps_zz = None
+        self.w0 = None
+        self.bed = None
         self.flags = TimeDiffFlags()
         self.header = ApresHeader()
 
@@ -361,6 +380,98 @@ def phase_diff(diff, win, step, range_ext=None):
     diff.flags.phase_diff = np.array([win, step])
 
 
+def phase_uncertainty(dat, bed_range, noise_phase=None):
+    """Phase uncertainty from a noise phasor of random phase and the median magnitude below the bed (reference
+    :126-153, Kingslake et al. 2014): leaves ``uncertainty`` and ``flags.uncertainty``.  The phase is drawn from
+    NumPy's global generator by the reference's own call unless ``noise_phase`` (an array of the data's squeezed
+    shape) is given."""
+    if dat.flags.range == 0:
+        raise TypeError(_MSG_RANGE_FIRST)
+    meas = np.squeeze(dat.data)
+    # (the first axis of the squeezed data, whatever it is: a per-burst stack is NumPy's IndexError, as in the reference)
+    below = np.argwhere(dat.Rcoarse > bed_range)
+    median_mag = np.nanmedian(abs(meas[below]))
+    if noise_phase is None:
+        noise_phase = np.random.uniform(-np.pi, np.pi, np.shape(meas))
+    noise = median_mag * (np.cos(noise_phase) + 1j * np.sin(noise_phase))
+    noise_orth = median_mag * np.sin(np.angle(meas) - np.angle(noise))
+    dat.uncertainty = np.abs(np.arcsin(noise_orth / np.abs(meas)))
+    dat.flags.uncertainty = True
+
+
+def phase_unwrap(diff, win=10, thresh=0.9):
+    """Unwrap the phase of ``co`` wherever the coherence around a sample is not all below ``thresh`` (reference
+    :96-123): leaves ``phi``.  For ``idx < win`` the slice starts at a negative index and is empty, so nothing is
+    unwrapped there -- the reference's behaviour."""
+    if diff.flags.phase_diff is None:
+        raise ValueError(_MSG_DIFF_FIRST)
+    diff.phi = np.angle(diff.co).astype(float)
+    for idx in range(1, len(diff.co)):
+        if np.all(abs(diff.co[idx - win:idx + win]) < thresh):
+            continue
+        if diff.phi[idx] - diff.phi[idx - 1] > np.pi:
+            diff.phi[idx:] -= 2. * np.pi
+        elif diff.phi[idx] - diff.phi[idx - 1] < -np.pi:
+            diff.phi[idx:] += 2. * np.pi
+
+
+def range_diff(diff, uncertainty='noise_phasor'):
+    """Phase profile to range offset (reference :126-170): leaves ``w`` and, when ``unc1`` is there, ``w_err`` by the
+    Cramer-Rao bound ('CR') or the noise phasor."""
+    if not hasattr(diff, 'phi'):
+        raise ValueError(_MSG_UNWRAP_FIRST)
+    win, step = diff.flags.phase_diff
+    h = diff.header
+    diff.w = phase2range(diff, diff.phi, h.lambdac, diff.ds, h.chirp_grad, h.ci)
+    if diff.unc1 is not None:
+        if uncertainty == 'CR':
+            sigma = (1. / abs(diff.co)) * np.sqrt((1. - abs(diff.co)**2.) / (2. * win))
+            diff.w_err = phase2range(diff, sigma, h.lambdac, diff.ds, h.chirp_grad, h.ci)
+        elif uncertainty == 'noise_phasor':
+            r_unc = phase2range(diff, diff.unc1, h.lambdac) + phase2range(diff, diff.unc2, h.lambdac)
+            idxs = np.arange(win // 2, len(diff.data) - win // 2, step)
+            diff.w_err = np.array([np.nanmean(r_unc[i - win // 2:i + win // 2]) for i in idxs])
+
+
+def strain_rate(diff, strain_window=(200, 1200), w_surf=0.):
+    """Mean vertical strain rate over ``strain_window`` by linear regression of ``w`` on ``ds`` (reference :173-200):
+    leaves ``eps_zz``, ``w0`` and shifts ``w`` by ``w_surf - w0``."""
+    from scipy.stats import linregress
+    if not hasattr(diff, 'w'):
+        raise ValueError(_MSG_RANGE_DIFF_FIRST)
+    print('Calculating vertical strain rate over range from %s to %s meters.' % strain_window)
+    idx = np.logical_and(diff.ds > strain_window[0], diff.ds < strain_window[1])
+    slope, intercept, r_value, p_value, std_err = linregress(diff.ds[idx], diff.w[idx])
+    diff.eps_zz = slope
+    diff.w0 = intercept
+    print('Vertical strain rate (yr-1):', diff.eps_zz)
+    print('r_squared:', r_value**2.)
+    diff.w += w_surf - diff.w0
+
+
+def bed_pick(diff, sample_threshold=50, coherence_threshold=0.9, filt_kernel=201, prominence=10, peak_width=300):
+    """The ice-bed interface as the deepest wide, prominent peak of the median-filtered power of both acquisitions
+    (reference :203-247): leaves ``bed = [sample, range, coherence, power]``."""
+    from scipy.signal import find_peaks, medfilt
+    picks, power = [], []
+    for acq in (diff.data, diff.data2):
+        P = 10. * np.log10(acq**2.)
+        mfilt = medfilt(P.real, filt_kernel)
+        peaks = find_peaks(mfilt, prominence=prominence, width=peak_width)[0]
+        picks.append(max(peaks))
+        power.append(mfilt[picks[-1]])
+    if not abs(picks[0] - picks[1]) < sample_threshold:
+        raise ValueError(_MSG_BED_APART)
+    bed_samp = (picks[0] + picks[1]) // 2
+    bed_power = (power[0] + power[1]) / 2.
+    bed_range = diff.range[bed_samp]
+    diff_idx = np.argmin(abs(diff.ds - bed_range))
+    bed_coherence = np.median(abs(diff.co[diff_idx - 10:diff_idx + 10]))
+    if not bed_coherence > coherence_threshold:
+        raise ValueError(_MSG_BED_COHERENCE)
+    diff.bed = np.array([bed_samp, bed_range, bed_coherence, bed_power])
+
+
 def chain(dat, p, max_range=4000, winfun='blackman', num_chirps=None):
     """Range conversion then stacking with the converted data resident in HBM in between: the raw chirps go up once.
     Leaves what the two calls leave, bit for bit."""
@@ -380,3 +491,23 @@ def chain(dat, p, max_range=4000, winfun='blackman', num_chirps=None):
     finally:
         for d in held:
             d.free()
+
+
+def single_processing(dat, p=2, max_range=4000., num_chirps=0., noise_bed_range=3000.):
+    """The reference's full flow for one acquisition (``apdar.py:337-345``): :func:`chain`, then
+    :func:`phase_uncertainty`.  ``num_chirps = 0`` stacks everything."""
+    if num_chirps == 0.:
+        chain(dat, p, max_range)
+    else:
+        chain(dat, p, max_range, num_chirps=num_chirps)
+    phase_uncertainty(dat, noise_bed_range)
+
+
+def time_diff_processing(diff, win=20, step=20, thresh=0.95, strain_window=(200, 1000), w_surf=-0.15):
+    """The reference's full flow for a pair of acquisitions (``apdar.py:348-354``): the phase difference on the GPU,
+    then unwrapping, range difference, strain rate and bed pick on the host."""
+    phase_diff(diff, win, step)
+    phase_unwrap(diff, win, thresh)
+    range_diff(diff)
+    strain_rate(diff, strain_window=strain_window, w_surf=w_surf)
+    bed_pick(diff)

@@ -20,6 +20,22 @@
 //   * phase gradient (:199-216): dphi/dz = (R dI/dz - I dR/dz) / (R^2 + I^2) with numpy.gradient's edge-order-1
 //       differences along range (the rule of impdar_kirchhoff's coefficients); R, I optionally through the
 //       library's own filtfilt first (the reference's lowpass).                       (qp_split_kernel, qp_grad_kernel)
+//   * cross-polarised extinction axis (:225-272, power_anomaly :303-319, lowpass :323-355): per row of HV the azimuth
+//       inside a window of columns at which the low-passed power anomaly is least.
+//         qp_anomaly_kernel  P = 10 log10(HV^2), complex as NumPy forms it (the square, clog, the two products with
+//                            log10(e), the complex product with 10 + 0j), minus the row's nanmean; one wavefront per
+//                            row.  The mean skips every element with a NaN in either part, as numpy.nanmean does, and
+//                            its sum has one order whatever the grid or the entry point: lane l adds columns l, l + 64,
+//                            l + 128 ... in that order, then the 64 lane sums meet in a butterfly over lane distances
+//                            32, 16, 8, 4, 2, 1.  The quotient is NumPy's complex / (count + 0j).  Output: ONE (n, 2 m)
+//                            float64 array, row j = the m real parts then the m imaginary parts, so that a single
+//                            impdar_filtfilt_dev call over 2 m columns filters both (no qp_split_kernel pass).
+//         impdar_filtfilt_dev  the library's own filtfilt along range, bit for bit SciPy's;
+//         qp_argmin_kernel   numpy.argmin of complex values over columns [c0, c1): the first element with a NaN in
+//                            either part, else the least (real, imag) in lexicographic order, ties to the lowest
+//                            column; one wavefront per row, int32 out (the column itself, c0 included).
+//   * gather (:174, :220, :266-270): out[j] = image[j, idx[j]] of a complex128 or float64 (n, m) image.
+//                                                                                          (qp_gather_kernel)
 //
 // All data is complex128 as interleaved (re, im) doubles, row-major.  Compiled with -ffp-contract=off.
 #include <cmath>
@@ -160,12 +176,131 @@ __global__ __launch_bounds__(QP_BLOCK) void qp_grad_kernel(const double *__restr
     out[idx] = (rv * di - iv * dr) / (rv * rv + iv * iv);
 }
 
+
+// ---- cross-polarised extinction axis ---------------------------------------------------------------------------
+
+#define QP_WAVE 64
+#define QP_ROWS_PER_BLOCK (QP_BLOCK / QP_WAVE)
+
+// 10. * numpy.log10(z ** 2.) of one complex128 element, operation by operation
+__device__ __forceinline__ double2 qp_power(const double2 z)
+{
+    const double log10e = 0.434294481903251827651;
+    const double sr = z.x * z.x - z.y * z.y, si = z.x * z.y + z.y * z.x;
+    const double lr = log(hypot(sr, si)) * log10e, li = atan2(si, sr) * log10e;
+    // (10 + 0j) * (lr + li j): a zero element (lr = -inf) leaves NaN in the imaginary part
+    return make_double2(10.0 * lr - 0.0 * li, 10.0 * li + 0.0 * lr);
+}
+
+// one wavefront per row; pa is (n, 2 m): m real parts, then m imaginary parts
+__global__ __launch_bounds__(QP_BLOCK) void qp_anomaly_kernel(const double2 *__restrict__ HV, double *__restrict__ pa, int n, int m)
+{
+    const int lane = threadIdx.x & (QP_WAVE - 1);
+    const size_t row = (size_t)blockIdx.x * QP_ROWS_PER_BLOCK + (threadIdx.x / QP_WAVE);
+    if (row >= (size_t)n) return;   // (a whole wavefront at a time)
+    const double2 *src = HV + row * m;
+    double *re = pa + row * 2 * m, *im = re + m;
+    double sr = 0.0, si = 0.0;
+    int cnt = 0;
+    for (int c = lane; c < m; c += QP_WAVE) {
+        const double2 p = qp_power(src[c]);
+        re[c] = p.x;
+        im[c] = p.y;
+        const bool skip = isnan(p.x) || isnan(p.y);   // numpy.nanmean: the element becomes 0 and is not counted
+        sr += skip ? 0.0 : p.x;
+        si += skip ? 0.0 : p.y;
+        cnt += skip ? 0 : 1;
+    }
+#pragma unroll
+    for (int d = QP_WAVE / 2; d >= 1; d >>= 1) {
+        sr += __shfl_xor(sr, d, QP_WAVE);
+        si += __shfl_xor(si, d, QP_WAVE);
+        cnt += __shfl_xor(cnt, d, QP_WAVE);
+    }
+    // NumPy's complex quotient by (cnt + 0j): ratio 0 / cnt = 0, scale 1 / cnt; 0 / 0 is NaN in both parts
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double mr = nan, mi = nan;
+    if (cnt > 0) {
+        const double scl = 1.0 / (double)cnt;
+        mr = (sr + si * 0.0) * scl;
+        mi = (si - sr * 0.0) * scl;
+    }
+    for (int c = lane; c < m; c += QP_WAVE) {   // (every lane reads back what it wrote itself)
+        re[c] -= mr;
+        im[c] -= mi;
+    }
+}
+
+struct QpPick {
+    double re, im;
+    int idx, nan;   // idx < 0: nothing yet
+};
+
+// numpy.argmin's order on complex values: a NaN before everything, then (real, imag), then the lower column
+__device__ __forceinline__ bool qp_before(const QpPick &a, const QpPick &b)
+{
+    if (a.idx < 0) return false;
+    if (b.idx < 0) return true;
+    if (a.nan != b.nan) return a.nan != 0;
+    if (!a.nan) {
+        if (a.re != b.re) return a.re < b.re;
+        if (a.im != b.im) return a.im < b.im;
+    }
+    return a.idx < b.idx;
+}
+
+// one wavefront per row of the (n, 2 m) filtered anomaly; columns [c0, c1), 0 <= c0 < c1 <= m
+__global__ __launch_bounds__(QP_BLOCK) void qp_argmin_kernel(const double *__restrict__ pa, int *__restrict__ out, int n, int m,
+                                                             int c0, int c1)
+{
+    const int lane = threadIdx.x & (QP_WAVE - 1);
+    const size_t row = (size_t)blockIdx.x * QP_ROWS_PER_BLOCK + (threadIdx.x / QP_WAVE);
+    if (row >= (size_t)n) return;
+    const double *re = pa + row * 2 * m, *im = re + m;
+    QpPick best = {0.0, 0.0, -1, 0};
+    for (int c = c0 + lane; c < c1; c += QP_WAVE) {
+        QpPick p = {re[c], im[c], c, 0};
+        p.nan = (isnan(p.re) || isnan(p.im)) ? 1 : 0;
+        if (qp_before(p, best)) best = p;
+    }
+#pragma unroll
+    for (int d = QP_WAVE / 2; d >= 1; d >>= 1) {
+        QpPick o;
+        o.re = __shfl_xor(best.re, d, QP_WAVE);
+        o.im = __shfl_xor(best.im, d, QP_WAVE);
+        o.idx = __shfl_xor(best.idx, d, QP_WAVE);
+        o.nan = __shfl_xor(best.nan, d, QP_WAVE);
+        if (qp_before(o, best)) best = o;
+    }
+    if (lane == 0) out[row] = best.idx;
+}
+
+// out[j] = image[j, idx[j]]; `step` doubles per element (2: complex128).  An index outside [0, m) gives NaN.
+__global__ __launch_bounds__(QP_BLOCK) void qp_gather_kernel(const double *__restrict__ image, const int *__restrict__ idx,
+                                                             double *__restrict__ out, int n, int m, int step)
+{
+    const size_t j = (size_t)blockIdx.x * QP_BLOCK + threadIdx.x;
+    if (j >= (size_t)n) return;
+    const int i = idx[j];
+    const bool ok = i >= 0 && i < m;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int k = 0; k < step; ++k) out[j * step + k] = ok ? image[(j * m + i) * step + k] : nan;
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 struct QpBufs {
-    DevBuf in[4], out[4], tab, box, blk, re, im;   // staging of the host-buffer forms, host tables, window sums, R and I
+    DevBuf in[4], out[4], tab, box, blk, re, im, idx;   // staging of the host-buffer forms, host tables, window sums, R and I, indices
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // stage boundaries of the last find_cpe (impdar_qp_find_cpe_last_ms)
+    bool ev_set = false;
     void release()
     {
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        ev_set = false;
+        idx.release();
         for (DevBuf &b : in) b.release();
         for (DevBuf &b : out) b.release();
         tab.release();
@@ -308,6 +443,116 @@ extern "C" int impdar_qp_phase_gradient_dev(impdar_ctx *ctx, const double *d_chh
     return impdar_ctx_mark_produced(ctx);
 }
 
+
+// ---- cross-polarised extinction axis ---------------------------------------------------------------------------
+
+static inline dim3 qp_row_grid(int n) { return dim3((unsigned)(((size_t)n + QP_ROWS_PER_BLOCK - 1) / QP_ROWS_PER_BLOCK)); }
+
+static int anomaly_check(const char *who, impdar_ctx *ctx, const void *HV, int n, int m, const void *pa)
+{
+    IMPDAR_ARG_CHECK(ctx && HV && pa, "%s: null argument", who);
+    IMPDAR_ARG_CHECK(HV != pa, "%s: the anomaly cannot be written over the image", who);
+    IMPDAR_ARG_CHECK(n >= 1 && m >= 1, "%s: %d range bins and %d azimuths", who, n, m);
+    IMPDAR_ARG_CHECK((size_t)n * m <= (size_t)1 << 34, "%s: %d x %d is too large", who, n, m);
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_qp_power_anomaly_dev(impdar_ctx *ctx, const double *d_HV, int n, int m, double *d_pa)
+{
+    const auto lock = g_qp.lock();
+    const int rc = anomaly_check("impdar_qp_power_anomaly", ctx, d_HV, n, m, d_pa);
+    if (rc) return rc;
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_qp.bind(ctx);
+    hipLaunchKernelGGL(qp_anomaly_kernel, qp_row_grid(n), dim3(QP_BLOCK), 0, ctx->stream, (const double2 *)d_HV, d_pa, n, m);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return impdar_ctx_mark_produced(ctx);
+}
+
+static int find_cpe_check(impdar_ctx *ctx, const void *HV, int n, int m, const double *b, const double *a, int ncoef,
+                          const double *zi, int idx_start, int idx_stop, const void *cpe_idxs, const void *pa)
+{
+    IMPDAR_ARG_CHECK(cpe_idxs, "impdar_qp_find_cpe: null argument");
+    const int rc = anomaly_check("impdar_qp_find_cpe", ctx, HV, n, m, cpe_idxs);
+    if (rc) return rc;
+    IMPDAR_ARG_CHECK(pa != HV, "impdar_qp_find_cpe: the anomaly cannot be written over the image");
+    IMPDAR_ARG_CHECK(b && a && zi && ncoef >= 2, "impdar_qp_find_cpe: the filter needs b, a and zi");
+    IMPDAR_ARG_CHECK(0 <= idx_start && idx_start < idx_stop && idx_stop <= m,
+                     "impdar_qp_find_cpe: columns [%d, %d) are no window of %d azimuths", idx_start, idx_stop, m);
+    return IMPDAR_OK;
+}
+
+static int qp_mark(impdar_ctx *ctx, int k)
+{
+    if (!g_qp.ev[k]) IMPDAR_HIP_CHECK(hipEventCreate(&g_qp.ev[k]));
+    IMPDAR_HIP_CHECK(hipEventRecord(g_qp.ev[k], ctx->stream));
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_qp_find_cpe_dev(impdar_ctx *ctx, const double *d_HV, int n, int m, const double *b, const double *a,
+                                      int ncoef, const double *zi, int idx_start, int idx_stop, int *d_cpe_idxs, double *d_pa)
+{
+    const auto lock = g_qp.lock();
+    int rc = find_cpe_check(ctx, d_HV, n, m, b, a, ncoef, zi, idx_start, idx_stop, d_cpe_idxs, d_pa);
+    if (rc) return rc;
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_qp.bind(ctx);
+    if (!d_pa) {
+        IMPDAR_HIP_CHECK(g_qp.re.ensure((size_t)n * m * 2 * sizeof(double)));
+        d_pa = g_qp.re.as<double>();
+    }
+    g_qp.ev_set = false;
+    if ((rc = qp_mark(ctx, 0))) return rc;
+    hipLaunchKernelGGL(qp_anomaly_kernel, qp_row_grid(n), dim3(QP_BLOCK), 0, ctx->stream, (const double2 *)d_HV, d_pa, n, m);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    if ((rc = qp_mark(ctx, 1))) return rc;
+    // real and imaginary parts side by side: one filtfilt along range over 2 m columns, bit for bit SciPy's
+    rc = impdar_filtfilt_dev(ctx, d_pa, IMPDAR_F64, n, 2 * m, b, a, ncoef, zi);
+    if (rc) return rc;
+    if ((rc = qp_mark(ctx, 2))) return rc;
+    hipLaunchKernelGGL(qp_argmin_kernel, qp_row_grid(n), dim3(QP_BLOCK), 0, ctx->stream, (const double *)d_pa, d_cpe_idxs, n, m,
+                       idx_start, idx_stop);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    if ((rc = qp_mark(ctx, 3))) return rc;
+    g_qp.ev_set = true;
+    return impdar_ctx_mark_produced(ctx);
+}
+
+extern "C" int impdar_qp_find_cpe_last_ms(impdar_ctx *ctx, float *anomaly_ms, float *filter_ms, float *argmin_ms)
+{
+    const auto lock = g_qp.lock();
+    IMPDAR_ARG_CHECK(ctx && anomaly_ms && filter_ms && argmin_ms, "impdar_qp_find_cpe_last_ms: null argument");
+    IMPDAR_ARG_CHECK(g_qp.owner == ctx && g_qp.ev_set, "no find_cpe has run on this context");
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    IMPDAR_HIP_CHECK(hipEventSynchronize(g_qp.ev[3]));
+    float *out[3] = {anomaly_ms, filter_ms, argmin_ms};
+    for (int k = 0; k < 3; ++k) IMPDAR_HIP_CHECK(hipEventElapsedTime(out[k], g_qp.ev[k], g_qp.ev[k + 1]));
+    return IMPDAR_OK;
+}
+
+static int gather_check(impdar_ctx *ctx, const void *image, int n, int m, const void *idx, const void *out)
+{
+    IMPDAR_ARG_CHECK(ctx && image && idx && out, "impdar_qp_cpe_gather: null argument");
+    IMPDAR_ARG_CHECK(image != out, "impdar_qp_cpe_gather: the result cannot be written over the image");
+    IMPDAR_ARG_CHECK(n >= 1 && m >= 1, "impdar_qp_cpe_gather: %d range bins and %d azimuths", n, m);
+    IMPDAR_ARG_CHECK((size_t)n * m <= (size_t)1 << 34, "impdar_qp_cpe_gather: %d x %d is too large", n, m);
+    return IMPDAR_OK;
+}
+
+extern "C" int impdar_qp_cpe_gather_dev(impdar_ctx *ctx, const double *d_image, int is_complex, int n, int m, const int *d_idx,
+                                        double *d_out)
+{
+    const auto lock = g_qp.lock();
+    const int rc = gather_check(ctx, d_image, n, m, d_idx, d_out);
+    if (rc) return rc;
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_qp.bind(ctx);
+    hipLaunchKernelGGL(qp_gather_kernel, qp_grid((size_t)n), dim3(QP_BLOCK), 0, ctx->stream, d_image, d_idx, d_out, n, m,
+                       is_complex ? 2 : 1);
+    IMPDAR_HIP_CHECK(hipGetLastError());
+    return impdar_ctx_mark_produced(ctx);
+}
+
 // ---- host-buffer forms ---------------------------------------------------------------------------------------
 
 extern "C" int impdar_qp_rotate(impdar_ctx *ctx, const double *shh, const double *shv, const double *svh, const double *svv, int n,
@@ -361,6 +606,49 @@ extern "C" int impdar_qp_phase_gradient(impdar_ctx *ctx, const double *chhvv, in
                               return impdar_qp_phase_gradient_dev(ctx, (const double *)d_in, n, m, grad_uniform, grad_h, ga, gb, gc,
                                                                   b, a, ncoef, zi, (double *)d_out);
                           });
+}
+
+
+extern "C" int impdar_qp_power_anomaly(impdar_ctx *ctx, const double *HV, int n, int m, double *pa)
+{
+    const int rc = anomaly_check("impdar_qp_power_anomaly", ctx, HV, n, m, pa);
+    if (rc) return rc;
+    return g_qp.host_form(ctx, g_qp.in[0], HV, (size_t)n * m * 16, &g_qp.out[0], pa, (size_t)n * m * 16,
+                          [&](void *d_in, void *d_out) { return impdar_qp_power_anomaly_dev(ctx, (const double *)d_in, n, m, (double *)d_out); });
+}
+
+extern "C" int impdar_qp_find_cpe(impdar_ctx *ctx, const double *HV, int n, int m, const double *b, const double *a, int ncoef,
+                                  const double *zi, int idx_start, int idx_stop, int *cpe_idxs, double *pa)
+{
+    int rc = find_cpe_check(ctx, HV, n, m, b, a, ncoef, zi, idx_start, idx_stop, cpe_idxs, pa);
+    if (rc) return rc;
+    const auto held = g_qp.lock();
+    const size_t bytes = (size_t)n * m * 16;
+    rc = g_qp.stage_in(ctx, g_qp.in[0], HV, bytes);
+    if (rc) return rc;
+    IMPDAR_HIP_CHECK(g_qp.out[0].ensure(bytes));
+    IMPDAR_HIP_CHECK(g_qp.idx.ensure((size_t)n * sizeof(int)));
+    rc = impdar_qp_find_cpe_dev(ctx, g_qp.in[0].as<double>(), n, m, b, a, ncoef, zi, idx_start, idx_stop, g_qp.idx.as<int>(),
+                                g_qp.out[0].as<double>());
+    if (rc) return rc;
+    rc = impdar_download(ctx, cpe_idxs, g_qp.idx.p, (size_t)n * sizeof(int), ctx->stream);
+    if (rc || !pa) return rc;
+    return impdar_download(ctx, pa, g_qp.out[0].p, bytes, ctx->stream);
+}
+
+extern "C" int impdar_qp_cpe_gather(impdar_ctx *ctx, const double *image, int is_complex, int n, int m, const int *idx, double *out)
+{
+    int rc = gather_check(ctx, image, n, m, idx, out);
+    if (rc) return rc;
+    const auto held = g_qp.lock();
+    const size_t es = is_complex ? 16 : 8;
+    rc = g_qp.stage_in(ctx, g_qp.in[0], image, (size_t)n * m * es);
+    if (!rc) rc = g_qp.stage_in(ctx, g_qp.idx, idx, (size_t)n * sizeof(int));
+    if (rc) return rc;
+    IMPDAR_HIP_CHECK(g_qp.out[0].ensure((size_t)n * es));
+    rc = impdar_qp_cpe_gather_dev(ctx, g_qp.in[0].as<double>(), is_complex, n, m, g_qp.idx.as<int>(), g_qp.out[0].as<double>());
+    if (rc) return rc;
+    return impdar_download(ctx, out, g_qp.out[0].p, (size_t)n * es, ctx->stream);
 }
 
 // ---- the reference's native hook (src/impdar/lib/ApresData/coherence.h:13) -----------------------------------

@@ -1,15 +1,18 @@
 """Quad-polarised ApRES processing: the rotation of the scattering matrix through a set of azimuths, the hhvv
-coherence image and its phase gradient along range.  The functions take any object with the attributes of the
+coherence image, its phase gradient along range, the cross-polarised extinction (cpe) axis and the fabric strength
+along it.  The functions take any object with the attributes of the
 reference's ``ApresQuadPol`` -- that object itself, or the :class:`QuadPol` holder below -- and leave the same
 attributes and flags behind as NumPy arrays.  The O(n) and O(n_thetas) tables (azimuths and their cos^2, sin cos,
 sin^2, window sizes, gradient coefficients, filter design) are NumPy / SciPy here; everything that touches an
-(n, n_thetas) image runs in ``csrc/quadpol.hip`` through the C ABI, on host buffers or, in :func:`chain`, resident
-in HBM from the four measured vectors to the phase gradient.
+(n, n_thetas) image runs in ``csrc/quadpol.hip`` through the C ABI, on host buffers or, in :func:`chain` and
+:func:`quadpol_processing`, resident in HBM from the four measured vectors to the last product.  What is left on
+the host is O(n): ``cpe = thetas[cpe_idxs]``, the product of :func:`phase_gradient_to_fabric`, and the column roll of
+:func:`azimuthal_rotation`.
 
-All data is complex128, as in the reference.  ``find_cpe``, ``phase_gradient_to_fabric``, loaders and containers
-are not here.
+All data is complex128, as in the reference.  Loaders and containers are not here.
 
-Reference: ``src/impdar/lib/ApresData/_QuadPolProcessing.py:37-222``; the native hook is
+Reference: ``src/impdar/lib/ApresData/_QuadPolProcessing.py:37-389`` and the ``quadpol_processing`` flow of
+``src/impdar/bin/apdar.py:357-363``; the native hook is
 ``src/impdar/lib/ApresData/coherence.h:13`` with its wrapper ``_coherence.pyx``.
 """
 import ctypes as C
@@ -27,6 +30,8 @@ _MSG_COHERENCE_FIRST = 'Calculate coherence before calling this function.'
 _MSG_CROSS_POL = 'Cross-polarized terms are of the opposite sign, check and update.'
 _MSG_FILTER = 'Filter: %s has \
                             not been implemented yet.'
+_MSG_FABRIC = "Get the phase gradient along CPE axis \
+                             before calling this function."
 
 
 class QuadPolFlags(object):
@@ -151,6 +156,54 @@ def refuse_nan_subset(chhvv):
                                       'edges is not supported by the MI355X engine' % nan_idx)
 
 
+def cpe_tables(qp, Wn, rad_start, rad_end):
+    """``(spec, idx_start, idx_stop)`` of the reference's ``find_cpe`` (:243-254): its error before a rotation, the
+    low-pass design (SciPy's own errors for a bad ``Wn``), the window of columns nearest the two azimuths.  An empty
+    window is the ``ValueError`` that ``np.argmin`` raises on an empty sequence."""
+    if qp.flags.rotation[0] != 1:
+        raise ImpdarError(_MSG_ROTATE_FIRST)
+    spec = lowpass_spec(Wn, 1. / qp.dt)
+    idx_start = int(np.argmin(abs(qp.thetas - rad_start)))
+    idx_stop = int(np.argmin(abs(qp.thetas - rad_end)))
+    if idx_stop <= idx_start:
+        np.argmin(np.empty((0,)))
+    return spec, idx_start, idx_stop
+
+
+def refuse_nan_anomaly(anomaly_of_rows, n):
+    """:func:`refuse_nan_subset` on the power anomaly, of which only the leading rows are formed: a row of the anomaly
+    depends on that row of the image alone.  ``anomaly_of_rows(k)`` gives the first ``k`` rows as complex128."""
+    k = 1
+    while True:
+        try:
+            return refuse_nan_subset(anomaly_of_rows(k))
+        except StopIteration:                                # every row so far starts with NaN: look further down
+            if k >= n:
+                raise
+            k = min(n, 8 * k)
+
+
+def _planes_to_complex(pa):
+    """complex128 (n, m) of the kernels' (n, 2 m) layout: m real parts, then m imaginary parts per row."""
+    m = pa.shape[1] // 2
+    out = np.empty((pa.shape[0], m), dtype=np.complex128)
+    out.real = pa[:, :m]
+    out.imag = pa[:, m:]
+    return out
+
+
+def _check_idx(idx, n, m):
+    idx = np.asarray(idx)
+    if idx.shape != (n,):
+        raise IndexError('shape mismatch: %d rows and indices of shape %s' % (n, idx.shape))
+    if not np.issubdtype(idx.dtype, np.integer):
+        raise IndexError('arrays used as indices must be of integer (or boolean) type')
+    if n and (idx.min() < -m or idx.max() >= m):
+        bad = idx[(idx < -m) | (idx >= m)][0]
+        raise IndexError('index %d is out of bounds for axis 1 with size %d' % (bad, m))
+    return np.ascontiguousarray(np.where(idx < 0, idx + m, idx), dtype=np.int32)
+
+
 def _grad_args(grad):
     uniform, h, ga, gb, gc = grad
     return (1 if uniform else 0, float(h), _hip.as_dp(ga), _hip.as_dp(gb), _hip.as_dp(gc))
@@ -203,6 +256,47 @@ def phase_gradient_host(chhvv, grad, spec=None):
     return out
 
 
+def anomaly_host(HV):
+    """Power anomaly of an (n, m) complex128 image in the kernels' (n, 2 m) float64 layout."""
+    HV = _c128(HV)
+    if HV.ndim != 2:
+        raise ValueError('the image must be a (range_bins, azimuth_bins) array')
+    n, m = HV.shape
+    pa = np.empty((n, 2 * m), dtype=np.float64)
+    rc = _hip.load().impdar_qp_power_anomaly(_hip.context(), _cdp(HV), n, m, _hip.as_dp(pa)[1])
+    _hip.check(rc, 'impdar_qp_power_anomaly')
+    return pa
+
+
+def find_cpe_host(HV, spec, idx_start, idx_stop, filtered=False):
+    """int32 column of the least low-passed power anomaly in ``[idx_start, idx_stop)`` per row of an (n, m)
+    complex128 image; with ``filtered`` also that anomaly, (n, 2 m) float64."""
+    HV = _c128(HV)
+    n, m = HV.shape
+    idxs = np.empty((n,), dtype=np.int32)
+    pa = np.empty((n, 2 * m), dtype=np.float64) if filtered else None
+    filt, keep = _spec_args(spec)
+    rc = _hip.load().impdar_qp_find_cpe(_hip.context(), _cdp(HV), n, m, *filt, int(idx_start), int(idx_stop),
+                                       idxs.ctypes.data_as(C.POINTER(C.c_int)), _hip.as_dp(pa)[1])
+    _hip.check(rc, 'impdar_qp_find_cpe')
+    return (idxs, pa) if filtered else idxs
+
+
+def cpe_gather_host(image, idx):
+    """``image[np.arange(n), idx]`` of an (n, m) complex128 or float64 image."""
+    image = np.asarray(image)
+    is_complex = np.iscomplexobj(image)
+    image = np.ascontiguousarray(image, dtype=np.complex128 if is_complex else np.float64)
+    n, m = image.shape
+    idx = _check_idx(idx, n, m)
+    out = np.empty((n,), dtype=image.dtype)
+    ptr = _cdp if is_complex else (lambda a: _hip.as_dp(a)[1])
+    rc = _hip.load().impdar_qp_cpe_gather(_hip.context(), ptr(image), 1 if is_complex else 0, n, m,
+                                         idx.ctypes.data_as(C.POINTER(C.c_int)), ptr(out))
+    _hip.check(rc, 'impdar_qp_cpe_gather')
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ resident
 def rotate_dev(d_vectors, cos2, sincos, sin2):
     """Four new resident (n, n_thetas) complex128 arrays from four resident complex128 vectors."""
@@ -243,6 +337,55 @@ def phase_gradient_dev(d_chhvv, grad, spec=None):
     return d_out
 
 
+def anomaly_dev(d_HV, rows=None):
+    """New resident (rows, 2 m) float64 power anomaly of the first ``rows`` rows (all of them by default) of a
+    resident (n, m) complex128 image."""
+    n, m = d_HV.shape
+    rows = n if rows is None else int(rows)
+    with _hip.new_device_array(d_HV.ctx, (rows, 2 * m), np.float64) as d_pa:
+        rc = _hip.load().impdar_qp_power_anomaly_dev(d_HV.ctx, d_HV.ptr, rows, m, d_pa.ptr)
+        _hip.check(rc, 'impdar_qp_power_anomaly')
+    return d_pa
+
+
+def find_cpe_dev(d_HV, spec, idx_start, idx_stop, filtered=False):
+    """New resident int32 indices of a resident (n, m) complex128 image; with ``filtered`` also the resident
+    (n, 2 m) float64 low-passed anomaly."""
+    n, m = d_HV.shape
+    filt, keep = _spec_args(spec)
+    out = []
+    try:
+        out.append(_hip.DeviceArray(d_HV.ctx, (n,), np.int32))
+        if filtered:
+            out.append(_hip.DeviceArray(d_HV.ctx, (n, 2 * m), np.float64))
+        rc = _hip.load().impdar_qp_find_cpe_dev(d_HV.ctx, d_HV.ptr, n, m, *filt, int(idx_start), int(idx_stop), out[0].ptr,
+                                               out[1].ptr if filtered else None)
+        _hip.check(rc, 'impdar_qp_find_cpe')
+    except Exception:
+        for d in out:
+            d.free()
+        raise
+    return tuple(out) if filtered else out[0]
+
+
+def find_cpe_last_ms(ctx=None):
+    """Device milliseconds ``(anomaly, filter, argmin)`` of the last ``find_cpe``."""
+    ms = [C.c_float(), C.c_float(), C.c_float()]
+    rc = _hip.load().impdar_qp_find_cpe_last_ms(ctx or _hip.context(), *[C.byref(m) for m in ms])
+    _hip.check(rc, 'impdar_qp_find_cpe_last_ms')
+    return tuple(m.value for m in ms)
+
+
+def cpe_gather_dev(d_image, d_idx):
+    """New resident ``image[np.arange(n), idx]`` of a resident (n, m) image and resident int32 indices."""
+    n, m = d_image.shape
+    with _hip.new_device_array(d_image.ctx, (n,), d_image.dtype) as d_out:
+        rc = _hip.load().impdar_qp_cpe_gather_dev(d_image.ctx, d_image.ptr, 1 if d_image.dtype == np.complex128 else 0, n, m,
+                                                 d_idx.ptr, d_out.ptr)
+        _hip.check(rc, 'impdar_qp_cpe_gather')
+    return d_out
+
+
 # ------------------------------------------------------------------------------------------------ bookkeeping
 def _set_rotation(qp, thetas, images, n_thetas):
     qp.thetas = thetas
@@ -263,6 +406,18 @@ def _set_gradient(qp, dphi_dz):
     if qp.flags.cpe is True:
         qp.dphi_dz_cpe = qp.dphi_dz[np.arange(qp.snum), qp.cpe_idxs]
     qp.flags.phasegradient = True
+
+
+def _set_cpe(qp, idxs, chhvv_cpe=None, dphi_dz_cpe=None):
+    """What ``find_cpe`` leaves (:260-272).  The two gathers are taken from the host images unless the caller has
+    made them already from resident ones."""
+    qp.cpe_idxs = np.asarray(idxs).astype(int)
+    qp.cpe = np.array([qp.thetas[i] for i in qp.cpe_idxs]).astype(float)
+    if qp.flags.coherence[0] == 1.:
+        qp.chhvv_cpe = qp.chhvv[np.arange(qp.snum), qp.cpe_idxs] if chhvv_cpe is None else chhvv_cpe
+    if qp.flags.phasegradient:
+        qp.dphi_dz_cpe = qp.dphi_dz[np.arange(qp.snum), qp.cpe_idxs] if dphi_dz_cpe is None else dphi_dz_cpe
+    qp.flags.cpe = True
 
 
 # ------------------------------------------------------------------------------------------------ the steps
@@ -291,6 +446,41 @@ def phase_gradient2d(qp, filt=None, Wn=0):
     _set_gradient(qp, phase_gradient_host(qp.chhvv, grad, spec))
 
 
+def power_anomaly(data):
+    """Power anomaly from the row mean of an (n, m) image (reference :303-319): complex128, computed on the GPU."""
+    return _planes_to_complex(anomaly_host(data))
+
+
+def find_cpe(qp, Wn=50, rad_start=np.pi / 4., rad_end=3. * np.pi / 4.):
+    """The cross-polarised extinction axis (reference :225-272): leaves ``cpe_idxs``, ``cpe``, ``flags.cpe`` and,
+    where the coherence or the phase gradient is there already, ``chhvv_cpe`` / ``dphi_dz_cpe``."""
+    spec, idx_start, idx_stop = cpe_tables(qp, Wn, rad_start, rad_end)
+    HV = _c128(qp.HV)
+    refuse_nan_anomaly(lambda k: _planes_to_complex(anomaly_host(HV[:k])), HV.shape[0])
+    _set_cpe(qp, find_cpe_host(HV, spec, idx_start, idx_stop))
+
+
+def phase_gradient_to_fabric(qp, c=300e6, fc=300e6, delta_eps=0.035, eps=3.12):
+    """Fabric strength from the phase gradient along the cpe axis (reference :276-299): leaves ``e2e1``."""
+    if not hasattr(qp, 'dphi_dz_cpe'):
+        raise AttributeError(_MSG_FABRIC)
+    qp.e2e1 = (c / (4. * np.pi * fc)) * (2. * np.sqrt(eps) / delta_eps) * qp.dphi_dz_cpe
+
+
+def azimuthal_rotation(data, thetas, azi):
+    """Roll the columns of an image to a known antenna orientation (reference :359-389); ``thetas`` is shifted and
+    shifted back in place, as there."""
+    thetas += azi
+    if azi < 0:
+        clip = np.argwhere(thetas > 0)[0][0]
+        data = np.append(data[:, clip:], data[:, :clip], axis=1)
+    elif azi > 0:
+        clip = np.argwhere(thetas > np.pi)[0][0]
+        data = np.append(data[:, clip:], data[:, :clip], axis=1)
+    thetas -= azi
+    return data
+
+
 def chain(qp, theta_start=0, theta_end=np.pi, n_thetas=100, cross_pol_exception=False, cross_pol_flip=False,
           flip_force=False, delta_theta=20.0 * np.pi / 180., delta_range=100., filt=None, Wn=0):
     """The three steps with the images resident in HBM in between: the four vectors go up once, every product comes
@@ -315,6 +505,58 @@ def chain(qp, theta_start=0, theta_end=np.pi, n_thetas=100, cross_pol_exception=
         d_dphi = phase_gradient_dev(d_chhvv, grad, spec)
         held.append(d_dphi)
         _set_gradient(qp, d_dphi.to_host())
+    finally:
+        for d in held:
+            d.free()
+
+
+def quadpol_processing(qp, nthetas=100, dtheta=20.0 * np.pi / 180., drange=100., Wn=50, cross_pol_flip=False,
+                       gradient=False, filt=None, Wn_gradient=0):
+    """The reference's full flow (``apdar.py:357-363``) -- rotation, cpe axis, coherence -- and with ``gradient`` the
+    phase gradient, its values along the cpe axis and the fabric strength, with every image resident in HBM in
+    between: the four vectors go up once, every product comes down once.  Leaves what the separate calls leave, bit
+    for bit."""
+    vectors, thetas, cos2, sincos, sin2 = rotation_tables(qp, 0, np.pi, nthetas, False, cross_pol_flip, False)
+    ctx = _hip.context()
+    held = []
+    try:
+        for v in vectors:
+            held.append(_hip.DeviceArray.from_host(ctx, v))
+        images = rotate_dev(held[:4], cos2, sincos, sin2)
+        held.extend(images)
+        _set_rotation(qp, thetas, tuple(d.to_host() for d in images), nthetas)
+        # the cpe axis of the resident HV
+        spec, idx_start, idx_stop = cpe_tables(qp, Wn, np.pi / 4., 3. * np.pi / 4.)
+
+        def lead(k):
+            d_pa = anomaly_dev(images[1], k)
+            try:
+                return _planes_to_complex(d_pa.to_host())
+            finally:
+                d_pa.free()
+        refuse_nan_anomaly(lead, images[1].shape[0])
+        d_idx = find_cpe_dev(images[1], spec, idx_start, idx_stop)
+        held.append(d_idx)
+        # (a coherence or a gradient left by an earlier call is gathered from its host image, as find_cpe does)
+        _set_cpe(qp, d_idx.to_host())
+        nrange, ntheta = coherence_windows(qp, dtheta, drange)
+        d_chhvv = coherence_dev(images[0], images[3], nrange, ntheta, wrap=True)
+        held.append(d_chhvv)
+        held.append(cpe_gather_dev(d_chhvv, d_idx))
+        qp.chhvv = d_chhvv.to_host()
+        qp.chhvv_cpe = held[-1].to_host()
+        qp.flags.coherence = np.array([1, dtheta, drange])
+        if gradient:
+            grad, gspec = gradient_tables(qp, filt, Wn_gradient)
+            if gspec is not None:
+                refuse_nan_subset(qp.chhvv)
+            d_dphi = phase_gradient_dev(d_chhvv, grad, gspec)
+            held.append(d_dphi)
+            held.append(cpe_gather_dev(d_dphi, d_idx))
+            qp.dphi_dz = d_dphi.to_host()
+            qp.dphi_dz_cpe = held[-1].to_host()
+            qp.flags.phasegradient = True
+            phase_gradient_to_fabric(qp)
     finally:
         for d in held:
             d.free()

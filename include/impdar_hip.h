@@ -452,6 +452,26 @@ void coherence2d(double *chhvv, double *HH, double *VV, int nrange, int ntheta,
  * dphi_dz is (n, m) float64.  With b != NULL, R and I first go through
  * impdar_filtfilt (b, a, zi of ncoef coefficients) along the rows: the
  * reference's lowpass.
+ * impdar_qp_power_anomaly: (:303-319)  pa = 10 log10(HV^2) - nanmean over each
+ * row, complex arithmetic as NumPy does it (a zero element gives -inf + NaN j
+ * and, like every element with a NaN in either part, is left out of the mean).
+ * HV: (n, m) complex128.  pa: ONE (n, 2 m) float64 array, row j holding the m
+ * real parts and then the m imaginary parts, the layout impdar_filtfilt_dev
+ * filters in a single call.  The row sum has one order whatever the entry
+ * point: lane l of a 64-lane wavefront adds columns l, l + 64, ... in turn, the
+ * lane sums meet in a butterfly over distances 32, 16, 8, 4, 2, 1.
+ * impdar_qp_find_cpe: (:225-272)  that anomaly, impdar_filtfilt (b, a, zi of
+ * ncoef coefficients) along the rows, then per row numpy.argmin of the complex
+ * values in columns [idx_start, idx_stop): the first element with a NaN in
+ * either part, else the least in (real, imag) order, ties to the lowest
+ * column.  cpe_idxs: n int32 column numbers (idx_start is included).  pa, when
+ * not NULL, receives the filtered anomaly in the (n, 2 m) layout.
+ * 0 <= idx_start < idx_stop <= m; n <= 3 ncoef fails with scipy's message.
+ * impdar_qp_find_cpe_last_ms: device time of the three stages of the last
+ * find_cpe on this context (waits for it).
+ * impdar_qp_cpe_gather: out[j] = image[j, idx[j]] of an (n, m) float64 or
+ * (is_complex != 0) complex128 image; idx: n int32.  An index outside [0, m)
+ * gives NaN.
  * The *_dev forms take device arrays (the tables stay host arrays), enqueue on
  * the context's compute stream and return without waiting for it. */
 int impdar_qp_rotate(impdar_ctx *ctx, const double *shh, const double *shv, const double *svh, const double *svv, int n,
@@ -470,6 +490,16 @@ int impdar_qp_phase_gradient(impdar_ctx *ctx, const double *chhvv, int n, int m,
 int impdar_qp_phase_gradient_dev(impdar_ctx *ctx, const double *d_chhvv, int n, int m, int grad_uniform, double grad_h,
                                  const double *ga, const double *gb, const double *gc, const double *b, const double *a,
                                  int ncoef, const double *zi, double *d_dphi_dz);
+int impdar_qp_power_anomaly(impdar_ctx *ctx, const double *HV, int n, int m, double *pa);
+int impdar_qp_power_anomaly_dev(impdar_ctx *ctx, const double *d_HV, int n, int m, double *d_pa);
+int impdar_qp_find_cpe(impdar_ctx *ctx, const double *HV, int n, int m, const double *b, const double *a, int ncoef,
+                       const double *zi, int idx_start, int idx_stop, int *cpe_idxs, double *pa);
+int impdar_qp_find_cpe_dev(impdar_ctx *ctx, const double *d_HV, int n, int m, const double *b, const double *a, int ncoef,
+                           const double *zi, int idx_start, int idx_stop, int *d_cpe_idxs, double *d_pa);
+int impdar_qp_find_cpe_last_ms(impdar_ctx *ctx, float *anomaly_ms, float *filter_ms, float *argmin_ms);
+int impdar_qp_cpe_gather(impdar_ctx *ctx, const double *image, int is_complex, int n, int m, const int *idx, double *out);
+int impdar_qp_cpe_gather_dev(impdar_ctx *ctx, const double *d_image, int is_complex, int n, int m, const int *d_idx,
+                             double *d_out);
 
 /* ---- ApRES range conversion, stacking, phase difference (csrc/apres.hip) ----
  * Everything float64 / complex128 (interleaved (re, im) doubles), row-major.
