@@ -50,6 +50,16 @@ struct impdar_ctx {
     char m_extra[320] = "";
 };
 
+// "this entry point ran this kernel, nothing was timed, no further metrics"
+static inline void impdar_ctx_note(impdar_ctx *ctx, const char *entry, const char *kernel)
+{
+    ctx->m_entry = entry;
+    ctx->m_kernel = kernel;
+    ctx->m_kernel_ms = -1.f;
+    ctx->timed = ctx->ktimed = false;
+    ctx->m_extra[0] = 0;
+}
+
 // the staging ring of impdar_download_blocks_f64
 constexpr size_t IMPDAR_STAGE_RING_BYTES = (size_t)64 << 20;
 // start allocating a pinned staging buffer of `bytes` unless the context has one (impdar_ctx_pinned adopts it)

@@ -1,4 +1,4 @@
-// Small RAII wrapper over rocFFT plans (used by stolt.hip and phaseshift.hip).
+// Small RAII wrapper over rocFFT plans (used by stolt.hip, phaseshift.hip and ffd.hip).
 #pragma once
 #include <functional>
 #include <string>

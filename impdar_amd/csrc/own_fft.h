@@ -22,6 +22,7 @@
 #pragma once
 #include "common.h"
 #include "own_fft_len.h"
+#include "own_fft_mixed_plan.h"      // own_fft_mixed_len_ok
 #include <cmath>
 #include <vector>
 
@@ -212,7 +213,7 @@ __global__ __launch_bounds__(1024) void own_fft_rows(const void *__restrict__ in
     }
 }
 
-// complex (rows x cols) -> (cols x rows) through an LDS tile (phaseshift.hip's ps_transpose_c, shared with stolt.hip)
+// complex (rows x cols) -> (cols x rows) through an LDS tile (ps_layout.h's ps_transpose_c, shared with stolt.hip)
 template <typename T, int TS>
 __global__ __launch_bounds__(256) void own_transpose_c(const OCp<T> *__restrict__ in, OCp<T> *__restrict__ out, int rows, int cols)
 {
@@ -255,7 +256,10 @@ struct OwnTwiddles {
     }
 };
 
-#include "own_fft_mixed.h"
+// the lengths that are no power of two (own_fft_mixed.h, included at the end: it builds on everything above)
+template <typename T>
+static int own_fft_mixed_launch(int mode, int n, size_t batch, const void *in, void *out, size_t in_dist, size_t out_dist, double scale,
+                                const OwnTwiddles &tw, hipStream_t st, const double *wcol, const double *wrow, int wfirst);
 
 // mode: OWN_*; n = the transform length (complex length for C2C, real length for R2C / C2R); dists in elements of the
 // respective side (complex for complex rows, real for real rows)
@@ -299,3 +303,5 @@ static int own_fft_launch(int mode, int n, size_t batch, const void *in, void *o
     IMPDAR_HIP_CHECK(hipGetLastError());
     return IMPDAR_OK;
 }
+
+#include "own_fft_mixed.h"

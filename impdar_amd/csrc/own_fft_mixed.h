@@ -1,12 +1,13 @@
 // Batched row transforms of any length M = 2^a 3^b 5^c 7^d, 16 <= M <= 8192, in LDS: own_fft.h's contract (the five modes, one
 // workgroup per row, the OwnTwiddles table, taper weights on the R2C load, the caller's scale) at the lengths field records
-// have -- 10000 traces are R2C / C2R rows of 5000 complex numbers.  Included by own_fft.h, whose own_fft_launch sends the
-// lengths that are no power of two here; the power-of-two kernel is untouched.
+// have -- 10000 traces are R2C / C2R rows of 5000 complex numbers.  own_fft.h includes this file at its end; its own_fft_launch
+// sends the lengths that are no power of two here; the power-of-two kernel is untouched.
 //
 // The passes, their order and every index are own_fft_mixed_plan.h's (host-only, tested by itself); this file adds the
 // butterflies.  Radix 4 is own_fft.h's butterfly (W^2j, W^3j by multiplication); radix 3, 5 and 7 pair point k with point
 // r - k (sums take the cosines, differences the sines) and read each output's twiddle from the table.
 #pragma once
+#include "own_fft.h"            // OCp, own_pad, the radix-4 butterfly, OwnTwiddles
 #include "own_fft_mixed_plan.h"
 
 // cos and sin of 2 pi k / R for the odd radices, k = 1 .. (R - 1) / 2

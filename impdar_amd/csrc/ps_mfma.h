@@ -1,4 +1,4 @@
-// Phase-shift frequency sum on the matrix cores (float32 data; included by phaseshift.hip).
+// Phase-shift frequency sum on the matrix cores (float32 data; run by ps_mfma_run, phaseshift.hip).
 //
 // Inside a run of constant velocity every frequency turns by a fixed angle per depth step, so with the steps of the
 // run cut into tiles of 64 (step = start + 64 a + b) the sum the reference accumulates (mig_python.py:418-420, :464, :487)
@@ -7,7 +7,7 @@
 // a complex matrix product (tiles x frequencies) . (frequencies x 64 steps) per wavenumber: 1/64 of the rotations
 // remain vector work for the states S_w(a) (a recurrence over a from an anchor that carries the phase in float64)
 // plus 64 step factors per (frequency, run); the contraction over the frequencies -- all of the rotate-accumulate
-// work of ps_kernel / ps_vz32_kernel -- goes to v_mfma_f32_32x32x16_f16.
+// work of ps_kernel / ps_vz32_kernel (ps_direct.h) -- goes to v_mfma_f32_32x32x16_f16.
 // Real form: [C_re C_im] = [S_re S_im] . [[B_re B_im] [-B_im B_re]].
 //
 // float32 accuracy from float16 operands: every operand is split into two halves (x = hi + lo, 11 + 11 bits) and
@@ -50,6 +50,7 @@
 // them over the whole depth axis in float64 afterwards, the way the reference does.
 // PsMfmaRun, PM_SHORT, PM_TT, PM_NRB, PM_EMAX, PM_MAX_RUNS, with the host-side plan of the row blocks and groups (pm_plan): ps_path_plan.h.
 #pragma once
+#include "ps_common.h"
 #include "ps_route.h"        // (includes ps_path_plan.h)
 
 typedef _Float16 pm_half8 __attribute__((ext_vector_type(8)));

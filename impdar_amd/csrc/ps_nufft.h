@@ -1,11 +1,11 @@
 // Phase-shift frequency sum as a NON-UNIFORM FAST FOURIER TRANSFORM (float32 and float64 data, a few long runs of constant velocity;
-// included by phaseshift.hip after own_fft.h and ps_mfma.h).
+// run by ps_nufft_run, phaseshift.hip).
 //
 // Inside a run of constant velocity every frequency turns by a fixed angle phi_w per depth step, so what the reference
 // accumulates step by step (mig_python.py:418-420, :464, :487) is a sum of exponentials sampled on the integers,
 //     TK[tau0 + n] = sum_w  C_w e^{i phi_w (n + 1)},     C_w = FK_w e^{i Phi_w(tau0)},   n = 0 .. L - 1,
 // a type-1 non-uniform discrete Fourier transform ("non-uniform frequencies phi_w in (0, 2 pi) -> uniform samples n").  The
-// kernels of ps.hip / ps_mfma.h / ps_runs.h evaluate it directly, O(frequencies x steps) rotations per wavenumber -- on the
+// kernels of ps_direct.h / ps_mfma.h / ps_runs.h evaluate it directly, O(frequencies x steps) rotations per wavenumber -- on the
 // vector units, or as a matrix product on the matrix cores.  Here it costs O(frequencies x W + G log G):
 //   1. the coefficient of every frequency, turned to the middle of the piece (the transform's band is centred),
 //      D_w = C_w e^{i phi_w (1 + Lp/2)}, and its place on a fine grid of G = 2 Lp points, u_w = phi_w G / 2 pi;
@@ -34,6 +34,10 @@
 // round 6 with pairs (profiles/r06_transforms.txt) 1.64 and 0.90 ms; float64 data 6.7 and 4.0 ms.
 // PnPiece, PN_NFMAX, PN_SHORT and the piece lengths, with the host-side plan of the pieces (pn_plan, pn_corr_of_length): ps_path_plan.h.
 #pragma once
+#include "own_fft.h"
+#include "ps_common.h"
+#include "ps_mfma.h"         // pm_coss, pm_sqrt01, pm_sincos, pm_wrap
+#include "ps_smooth.h"       // pss_sincos_small
 #include "ps_route.h"        // (includes ps_path_plan.h)
 
 // float32 data: a window of 8 grid points (3.5e-7 of the result in float32 arithmetic), 1024 threads;

@@ -41,7 +41,7 @@ struct PsAttempt {
 };
 
 struct PsRoute {
-    bool herm = false;                      // Hermitian walk (see ps_load_slot): nf frequency slots per wavenumber, rows of fstride
+    bool herm = false;                      // Hermitian walk (see ps_load_slot, ps_common.h): nf frequency slots per wavenumber, rows of fstride
     int nf = 0, fstride = 0;
     std::vector<int> k_zero;                // ... the wavenumbers with kx = 0 (the zero-frequency row propagates there)
     double w0 = 0.0;                        // what stands for the zero frequency (:400-402)
@@ -182,7 +182,7 @@ static inline void ps_route_estimate(PsRoute &R, bool dbl, int snum)
 //   MFMA / RUNS (float32): up to 3 long runs ps_mfma_kernel first (64-step tiles, phases from a table), more ps_runs_kernel (8-step
 //           tiles, phases generated in the kernel); whichever declines hands over to the other
 //   SMOOTH  no runs of constant velocity to live on (the velocity changes in most 16-step tiles): ps_smooth_kernel
-//   VECTOR  ps_dispatch: the runs kernels of the vector path with a schedule, else the per-step kernel.  Always last, never declines.
+//   VECTOR  ps_dispatch (ps_direct.h): the runs kernels of the vector path with a schedule, else the per-step kernel.  Always last, never declines.
 static inline void ps_route_attempts(PsRoute &R, bool dbl, int snum, double vconst, int vlen, const PsKnobs &K)
 {
     const int pref = K.mfma;

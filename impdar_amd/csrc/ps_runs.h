@@ -1,4 +1,4 @@
-// Phase-shift frequency sum for MANY runs of constant velocity (float32 data; included by phaseshift.hip).
+// Phase-shift frequency sum for MANY runs of constant velocity (float32 data; run by ps_runs_run, phaseshift.hip).
 //
 // Reference: mig_python.py:438-487 with the vmig that getVelocityProfile (:582-604) makes of an N-row (v, z) table: N - 1
 // layers of constant velocity, each boundary smeared over three or four single steps by 2 * gradient(z(t)).  ps_mfma.h
@@ -38,6 +38,8 @@
 // frequencies are skipped.
 // PrRun, PrStage and the PR_* constants of the tiling, with the host-side plan of the runs and stages (pr_plan): ps_path_plan.h.
 #pragma once
+#include "ps_common.h"
+#include "ps_mfma.h"         // pm_coss, pm_split, pm_pack, pm_conj, pm_swap, pm_wrap
 #include "ps_route.h"        // (includes ps_path_plan.h)
 
 typedef float pr_float4 __attribute__((ext_vector_type(4)));

@@ -1,5 +1,5 @@
 // Phase-shift frequency sum for a velocity that CHANGES inside a piece of the depth axis, as a few non-uniform FFTs that share
-// their nodes (float32 and float64 data; included by phaseshift.hip after ps_nufft.h).
+// their nodes (float32 and float64 data; run by ps_series_run, phaseshift.hip).
 //
 // Reference (mig_python.py:438-487): per depth step tau and frequency w of wavenumber kx
 //     coss = 1 - (0.5 v_tau kx / w)^2;  FK[w] *= exp(i w dt sqrt(coss));  FK[w] = 0 for good once coss <= thr_tau;  TK[tau] += FK[w]
@@ -34,7 +34,7 @@
 // chunk's phase sum, then the phases, a sincos per (frequency, step) and a wave sum per step) -> coefficients / grid places of
 // the regular frequencies -> gather -> J FFTs -> output.  Every sum has a fixed order: results are reproducible bit for bit.
 #pragma once
-
+#include "ps_nufft.h"        // PnWinF and its window; with it own_fft.h, ps_common.h, ps_mfma.h
 #include "ps_series_plan.h"
 
 template <typename T> struct SrCfg;

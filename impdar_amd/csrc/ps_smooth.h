@@ -1,11 +1,11 @@
 // Phase shift (Gazdag) for velocity profiles that change at (nearly) EVERY depth step -- a firn profile, a linear
 // gradient: what getVelocityProfile's 2 * gradient(z(t)) gives for anything but a few thick layers.
-// (included by phaseshift.hip)
+// (run by ps_smooth_run, phaseshift.hip)
 //
 // Reference: mig_python.py:438-487.  Per depth step tau and frequency w (wavenumber kx):
 //     coss = 1 - (0.5 v_tau kx / w)^2;   FK[w] *= exp(i w dt sqrt(coss));   FK[w] = 0 for good once coss <= thr_tau;
 //     TK[tau] += FK[w]
-// The runs kernels (ps_vz32_kernel / ps_vz64_kernel, ps_mfma.h) live on runs of constant velocity, where the rotation
+// The runs kernels (ps_vz32_kernel / ps_vz64_kernel in ps_direct.h, ps_mfma.h) live on runs of constant velocity, where the rotation
 // per step is fixed.  Without runs the per-step kernel paid a float64 divide, square root and a sincos per
 // (tau, w): 917 ms (float32) / 834 ms (float64) at 8192^2 against 15 / 60 ms for a four-layer table.
 //
@@ -31,6 +31,7 @@
 // root + Newton and the series of sine and cosine (the phase is small where coss is).
 // float32 data (ps_smooth32_kernel): see there.
 #pragma once
+#include "ps_common.h"
 
 #define PSS_BAND 60.0
 #define PSS_NARROW 0.01     // bands up to this take the short way through the exact branch

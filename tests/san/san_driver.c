@@ -80,9 +80,23 @@ int main(void)
     EXPECT(impdar_stolt(NULL, tt, IMPDAR_F64, SNUM, TNUM, dist, tt, 1.68e8, 10, 10, out) == IMPDAR_ERR_ARG, "stolt(NULL)");
     EXPECT(impdar_stolt_dev(fctx, tt, 9, SNUM, TNUM, dist, tt, 1.68e8, 10, 10, out) == IMPDAR_ERR_ARG, "stolt bad dtype");
     EXPECT(impdar_stolt_dev(fctx, tt, IMPDAR_F32, 1, TNUM, dist, tt, 1.68e8, 10, 10, out) == IMPDAR_ERR_ARG, "stolt snum 1");
-    EXPECT(impdar_phaseshift_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 32, dist, tt, 1e-8, tt, 1.69e8, NULL, 0, 10, 10, out) == IMPDAR_ERR_ARG, "phase shift nt < snum");
+    EXPECT(impdar_phaseshift_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 32, dist, tt, 1e-8, tt, 1.69e8, NULL, 0, 10, 10, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "bad sizes snum 64 tnum 40 nt 32"), "phase shift nt < snum");
     EXPECT(impdar_phaseshift_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 64, dist, tt, 1e-8, tt, 1.69e8, tt, 5, 10, 10, out) == IMPDAR_ERR_ARG
-           && strstr(impdar_last_error(), "velocity profile"), "phase shift velocity profile of the wrong length");
+           && strstr(impdar_last_error(), "velocity profile is not the length"), "phase shift velocity profile of the wrong length");
+    /* the same two checks at the other entry points of ps_run, and the slab of the sharded one (before the empty slab's early return) */
+    EXPECT(impdar_phaseshift(fctx, tt, IMPDAR_F32, SNUM, TNUM, 32, dist, tt, 1e-8, tt, 1.69e8, NULL, 0, 10, 10, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "bad sizes snum 64 tnum 40 nt 32"), "phase shift (host arrays) nt < snum");
+    EXPECT(impdar_phaseshift(fctx, tt, IMPDAR_F32, SNUM, TNUM, 64, dist, tt, 1e-8, tt, 1.69e8, tt, 5, 10, 10, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "velocity profile is not the length"), "phase shift (host arrays) velocity profile of the wrong length");
+    EXPECT(impdar_phaseshift_tk_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 32, dist, tt, 1e-8, tt, 1.69e8, NULL, 0, 10, 10, 0, TNUM, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "bad sizes snum 64 tnum 40 nt 32"), "phase shift (wavenumber slab) nt < snum");
+    EXPECT(impdar_phaseshift_tk_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 64, dist, tt, 1e-8, tt, 1.69e8, tt, 5, 10, 10, 0, TNUM, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "velocity profile is not the length"), "phase shift (wavenumber slab) velocity profile of the wrong length");
+    EXPECT(impdar_phaseshift_tk_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 64, dist, tt, 1e-8, tt, 1.69e8, NULL, 0, 10, 10, TNUM - 3, 4, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "wavenumber slab [37, 41) outside [0, 40)"), "phase shift wavenumber slab outside the axis");
+    EXPECT(impdar_phaseshift_tk_dev(fctx, tt, IMPDAR_F32, SNUM, TNUM, 64, dist, tt, 1e-8, tt, 1.69e8, tt, 5, 10, 10, 7, 0, out) == IMPDAR_ERR_ARG
+           && strstr(impdar_last_error(), "velocity profile is not the length"), "phase shift: an empty slab is still checked");
     EXPECT(impdar_filtfilt_dev(fctx, out, IMPDAR_F64, 10, 4, tt, tt + 1, 5, tt) == IMPDAR_ERR_ARG && strstr(impdar_last_error(), "padlen"),
            "filtfilt on a trace shorter than the padding");
     EXPECT(impdar_filtfilt_dev(fctx, out, IMPDAR_F64, 100, 4, tt, tt, 5, tt) == IMPDAR_ERR_ARG, "filtfilt a[0] == 0");
