@@ -10,8 +10,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libimpdar_hip.so')
-SOURCES = ['api.hip', 'comm.hip', 'kirchhoff.hip', 'kirch_gen.hip', 'stolt.hip', 'phaseshift.hip', 'ffd.hip', 'preproc.hip',
-           'hfilt.hip', 'denoise.hip', 'hpass.hip', 'vaxis.hip', 'gain.hip', 'taxis.hip', 'quadpol.hip', 'apres.hip']
+SOURCES = ['api.hip', 'comm.hip', 'kirchhoff.hip', 'kirch_ring32.hip', 'kirch_ring64.hip', 'kirch_oneshot.hip', 'kirch_gen.hip',
+           'stolt.hip', 'phaseshift.hip', 'ffd.hip', 'preproc.hip', 'hfilt.hip', 'denoise.hip', 'hpass.hip', 'vaxis.hip', 'gain.hip',
+           'taxis.hip', 'quadpol.hip', 'apres.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off',
          '-fno-slp-vectorize', '-Wall', '-Wno-unused-function']
 
@@ -47,7 +48,7 @@ def build(force=False, verbose=True):
             cmd = [hipcc] + FLAGS + ['-c', s, '-o', o]
             if verbose:
                 print(' '.join(cmd), flush=True)
-            jobs.append((cmd, subprocess.Popen(cmd)))      # the sources compile side by side (kirchhoff.hip is minutes)
+            jobs.append((cmd, subprocess.Popen(cmd)))      # the sources compile side by side (the ring units are minutes)
     failed = [cmd for cmd, proc in jobs if proc.wait() != 0]
     if failed:
         raise subprocess.CalledProcessError(1, failed[0])

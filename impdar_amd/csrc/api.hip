@@ -169,7 +169,7 @@ void impdar_comm_destroy(impdar_ctx *ctx);   // comm.hip
 
 void impdar_stolt_forget(const impdar_ctx *ctx);   // stolt.hip
 void impdar_ps_forget(const impdar_ctx *ctx);      // phaseshift.hip
-void impdar_kirch_forget(const impdar_ctx *ctx);   // kirchhoff.hip
+void impdar_kirch_forget(const impdar_ctx *ctx);   // kirch_oneshot.hip
 void impdar_preproc_forget(impdar_ctx *ctx);       // preproc.hip
 void impdar_hfilt_forget(impdar_ctx *ctx);         // hfilt.hip
 void impdar_denoise_forget(impdar_ctx *ctx);       // denoise.hip
@@ -180,7 +180,7 @@ void impdar_taxis_forget(impdar_ctx *ctx);         // taxis.hip
 void impdar_quadpol_forget(impdar_ctx *ctx);       // quadpol.hip
 void impdar_apres_forget(impdar_ctx *ctx);         // apres.hip
 
-void impdar_kirch_trim();    // kirchhoff.hip
+void impdar_kirch_trim();    // kirch_oneshot.hip
 void impdar_stolt_trim();    // stolt.hip
 void impdar_ps_trim();       // phaseshift.hip
 

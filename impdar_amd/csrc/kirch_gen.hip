@@ -1,7 +1,7 @@
 // Kirchhoff diffraction sum on a NON-UNIFORM trace spacing: float32 data, uniform travel_time, sorted dist[].
 //
 // Reference: src/impdar/lib/migrationlib/mig_python.py:35-60 sums over ANY dist[] (:44 takes dist[j] - dist[xi]).
-// The ring kernels of kirchhoff.hip tabulate a pair's pick per (sample, trace OFFSET), which only exists on a
+// The ring kernels (kirch_ring32.hip, kirch_ring64.hip) tabulate a pair's pick per (sample, trace OFFSET), which only exists on a
 // uniform profile; everything else fell to the per-pair float64 kernel (0.77 s at 10000 x 4096).  This kernel keeps
 // what makes the ring kernels fast -- input traces staged once per workgroup in LDS, many outputs per lane -- and
 // computes the pick of every pair from the positions:

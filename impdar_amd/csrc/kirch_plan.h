@@ -1,5 +1,6 @@
-// The Kirchhoff plan object shared by kirchhoff.hip (plan creation, prep, the ring kernels and their launches)
-// and kirch_gen.hip (the non-uniform-spacing kernel).
+// The Kirchhoff plan object and the functions by which the Kirchhoff units reach each other: kirchhoff.hip (plan creation,
+// prep, migrate dispatch, exchange), kirch_ring32.hip / kirch_ring64.hip (the LDS-ring kernels and their launches),
+// kirch_gen.hip (the non-uniform-spacing kernel) and kirch_oneshot.hip (the cached one-shot entry and the reference hook).
 #pragma once
 #include "common.h"
 #include "kirch_route.h"
@@ -86,5 +87,44 @@ static int upload(DevBuf &b, const void *src, size_t bytes)
     return IMPDAR_OK;
 }
 
+// the axes every table / per-pair parameter struct carries
+template <typename P>
+static void kirch_fill_axes(P &T, const impdar_kirch_plan *p)
+{
+    T.zs = p->d_zs.as<double>();
+    T.zs2 = p->d_zs2.as<double>();
+    T.tt = p->d_tt.as<double>();
+    T.vel = p->vel;
+    T.tmax = p->tmax;
+    T.inv_dt = 1.0 / p->dt;
+    T.tt0 = p->tt0;
+    T.snum = p->snum;
+}
+
+// ---- what the units call of each other ----
+// (what this split made a cross-unit call stays out of the library's dynamic symbol table)
+#define KIRCH_LOCAL __attribute__((visibility("hidden")))
 // kirch_gen.hip: kirch_gen_kernel + kirch_gen_shell_kernel on output traces [xlo, xhi) of the prepared image
 int kirch_launch_gen(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st);
+// kirch_ring32.hip (kirch_quad_kernel, kirch_tab_kernel) and kirch_ring64.hip (kirch_dquad_kernel): the diffraction sum of the
+// plan's ring kernel on output traces [xlo, xhi), and the pick / weight table of buffer set b on the producer stream
+KIRCH_LOCAL int kirch_launch_ring32(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st);
+KIRCH_LOCAL int kirch_table_ring32(impdar_kirch_plan *p, int b, hipStream_t st);
+KIRCH_LOCAL int kirch_launch_ring64(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st);
+KIRCH_LOCAL int kirch_table_ring64(impdar_kirch_plan *p, int b, hipStream_t st);
+
+// kirchhoff.hip, for the cached entry points of kirch_oneshot.hip.
+// What mig_kirch_loop hands over with its call: the time limit t > t_max drops a pair at (mig_python.py:52) is the caller's
+// argument there, not max(tt); `standard`: the depth tables are what the plan computes itself, bit for bit.
+struct KirchCallerTables {
+    double tmax;
+    const double *zs, *zs2;
+    bool standard;
+};
+KIRCH_LOCAL int kirch_plan_create_impl(impdar_ctx *ctx, int dtype, int snum, int tnum, const double *dist_m, const double *tt_sec,
+                                       double vel, int nearfield, int grad_uniform, double grad_h, const double *ga, const double *gb,
+                                       const double *gc, int mode, int nranks, const KirchKnobs &knobs, const KirchCallerTables *caller,
+                                       impdar_kirch_plan **out);
+// (`more`: further input traces of a radargram whose first traces an earlier prep took; see the definition)
+KIRCH_LOCAL int kirch_prep_impl(impdar_kirch_plan *p, const void *d_data, int ld, int jlo, int nloc, int precomputed, bool more = false);
+int impdar_kirch_prep_precomputed(impdar_kirch_plan *p, const void *d_grad, int ld, int jlo, int nloc);

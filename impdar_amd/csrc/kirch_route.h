@@ -1,7 +1,8 @@
 // What the Kirchhoff plan (impdar_kirch_plan_create, kirchhoff.hip) decides on the host: the analysis of the two axes, the
 // choice between the six kernels with their tile widths, ring sizes and table shifts, and the host tables the stages of the
-// plan upload.  Plain C++, no device code -- compiled into the library by kirchhoff.hip and, by itself with g++, into the CPU
-// suite's checker (tests/test_kirch_route.py).  The IMPDAR_KIRCH_* plan knobs are read once, by KirchKnobs::from_env() when
+// plan upload; and where the one-shot entry point (kirch_oneshot.hip) cuts a large radargram.  Plain C++, no device code --
+// compiled into the library through kirch_plan.h by every Kirchhoff unit and, by itself with g++, into the CPU suite's
+// checker (tests/test_kirch_route.py).  The IMPDAR_KIRCH_* plan knobs are read once, by KirchKnobs::from_env() when
 // a plan is created; the plan keeps them with its route, and prep / migrate go by what is stored.
 #pragma once
 #include "../../include/impdar_hip.h"
@@ -547,6 +548,37 @@ static inline std::vector<short> kirch_tilemap(const std::vector<int> &h_hmax, i
     return map;
 }
 
+// How the one-shot entry point (impdar_kirchhoff, kirch_oneshot.hip) takes a large radargram through in pieces.  OUTPUT
+// traces in blocks [cut[i], cut[i + 1]), one launch each; block i reads the input traces up to its right edge + the
+// aperture half width `halo` only, so its launch starts when input traces [0, need[i]) are on the device and the rest of
+// the upload runs under it.  Four blocks [0, .10, .40, .70, 1] tnum when the aperture leaves something to overlap (the
+// second block's need stays below 9/10 of the input; sweeps of the cuts: profiles/r03_oneshot_pipeline.txt,
+// r05_oneshot_cuts.txt), else -- or with `two`, the round-3 first form kept for A/B -- two (5/8 + 3/8, download overlap
+// only; with `two` every block waits for the whole input).  Interior cuts and needs are multiples of 8 (whole image groups).
+#ifndef KOS_PCT
+#define KOS_PCT {10, 40, 70}
+#endif
+struct __attribute__((visibility("hidden"))) KirchOneShotCuts {      // (hidden: no weak symbol of it in the library's dynamic table)
+    std::vector<int> cut;       // nblk + 1 output cuts, 0 .. tnum
+    std::vector<int> need;      // per block: input traces [0, need) its launch reads
+};
+static inline KirchOneShotCuts kirch_oneshot_cuts(int tnum, int halo, bool two)
+{
+    auto r8 = [](long long x) { return (int)(x / 8 * 8); };
+    KirchOneShotCuts C;
+    const std::vector<int> pct = KOS_PCT;              // interior cuts in percent of tnum
+    if (!two && (long long)tnum * pct[pct.size() > 1 ? 1 : 0] / 100 + halo < (long long)tnum * 9 / 10) {
+        C.cut = {0};
+        for (int q : pct) C.cut.push_back(r8((long long)tnum * q / 100));
+        C.cut.push_back(tnum);
+    } else {
+        C.cut = {0, r8((long long)tnum * 5 / 8), tnum};
+    }
+    for (size_t i = 0; i + 1 < C.cut.size(); ++i)
+        C.need.push_back(two ? tnum : (int)std::min<long long>(tnum, ((long long)C.cut[i + 1] + halo + 7) / 8 * 8));
+    return C;
+}
+
 #ifdef KIRCH_ROUTE_PROBE
 // The route and the tables as flat arrays (tests/test_kirch_route.py compiles this header by itself).
 // knobs[15]: xb_set, xb, nh_set, nh, lk_set, lk, parts_set, parts, nhd_set, nhd, xbd_set, xbd, impl, exact_impl, tiefix_off.
@@ -637,5 +669,14 @@ extern "C" int impdar_kirch_tilemap_probe(const int *h_hmax, int nchunks, int tn
                                                step_block, G, tiles_per_xcd, nchunks);
     std::copy(m.begin(), m.end(), map);
     return (int)m.size();
+}
+
+// returns the number of blocks; cut[blocks + 1], need[blocks] (at most 8 blocks)
+extern "C" int impdar_kirch_oneshot_cuts_probe(int tnum, int halo, int two, int *cut, int *need)
+{
+    const KirchOneShotCuts C = kirch_oneshot_cuts(tnum, halo, two != 0);
+    std::copy(C.cut.begin(), C.cut.end(), cut);
+    std::copy(C.need.begin(), C.need.end(), need);
+    return (int)C.need.size();
 }
 #endif

@@ -1,5 +1,5 @@
 """ms per step of the float64 Kirchhoff ring kernel (kirch_dquad_kernel) at config 3 (10000 x 4096, resident), from bench.py's own
-timed loop.   usage: dquad_time.py   (IMPDAR_HIP_LIB picks the build: profiles/tools/variant.sh kirchhoff.hip ...)"""
+timed loop.   usage: dquad_time.py   (IMPDAR_HIP_LIB picks the build: profiles/tools/variant.sh kirch_ring64.hip ...)"""
 import subprocess, sys, json, os
 out = subprocess.run([sys.executable, 'bench.py', '--dtype', 'f64', '--mode', 'exact', '--steps', '8', '--warmup', '2', '--no-cpu', '--no-pmc',
                       '--no-paths', '--no-e2e'], capture_output=True, text=True, env=dict(os.environ)).stdout

@@ -7,7 +7,7 @@ ROWS=${1:-41}
 shift
 VARS=${@:-FULL PR_ABL_NOSETUP PR_ABL_NOITEMS PR_ABL_NOMFMA}
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-slp-vectorize -Wno-unused-function"
-OBJS="api.o comm.o kirchhoff.o kirch_gen.o stolt.o preproc.o"
+OBJS=$(ls *.o | grep -v "^phaseshift.o$")      # every other unit from the regular build
 for v in $VARS; do
   D=$(echo $v | sed 's/+/ -D/g')
   /opt/rocm/bin/hipcc $FLAGS -D$D -c phaseshift.hip -o /tmp/ps_$v.o || exit 1

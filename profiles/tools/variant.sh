@@ -8,7 +8,7 @@ CMD=$2
 shift 2
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-slp-vectorize -Wno-unused-function"
 OBJS=""
-for o in api comm kirchhoff kirch_gen stolt phaseshift preproc; do [ "$o.hip" != "$SRC" ] && OBJS="$OBJS $o.o"; done
+for o in *.o; do [ "${o%.o}.hip" != "$SRC" ] && OBJS="$OBJS $o"; done      # every other unit from the regular build
 for v in "$@"; do
   D=$(echo $v | sed 's/+/ -D/g')
   /opt/rocm/bin/hipcc $FLAGS -D$D -c $SRC -o /tmp/v_$v.o || exit 1

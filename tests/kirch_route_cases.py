@@ -197,6 +197,13 @@ def tilemap(lib, hmax, tnum, xlo, xhi, tile_w, align_mask, ring_blocks, step_blo
     return m[:n].reshape(len(hm), tiles_per_xcd, 8) if n else None
 
 
+def oneshot_cuts(lib, tnum, halo, two=False):
+    """kirch_oneshot_cuts: (output cuts, input traces each block needs) of the one-shot entry point's pipeline."""
+    cut, need = np.full(16, -1, dtype=np.int32), np.full(16, -1, dtype=np.int32)
+    n = lib.impdar_kirch_oneshot_cuts_probe(tnum, halo, int(two), cut.ctypes.data_as(_ip), need.ctypes.data_as(_ip))
+    return cut[:n + 1].tolist(), need[:n].tolist()
+
+
 # ---- one plan through the C ABI under a case's knobs (GPU)
 def run(hip, c, monkeypatch=None):
     """Create the plan of case c, one prep and one migrate of a noise radargram: (what the plan reports, the image)."""

@@ -296,6 +296,35 @@ def test_tilemap(lib):
     assert KC.tilemap(lib, [10], 40000 * 24, 0, 40000 * 24, 24, 7, 5, 8, 4, 40000 // 8) is None
 
 
+@pytest.mark.parametrize('tnum,halo,two,cut,need', [
+    (4100, 2000, False, [0, 408, 1640, 2864, 4100], [2408, 3640, 4100, 4100]),
+    (4100, 2050, False, [0, 2560, 4100], None),          # 1640 + 2050 is not below 3690: the two-block form
+    (4100, 2000, True, [0, 2560, 4100], [4100, 4100]),
+    (10000, 500, False, [0, 1000, 4000, 7000, 10000], None),
+])
+def test_oneshot_cuts_where_the_rule_turns(lib, tnum, halo, two, cut, need):
+    """The cut planner of the one-shot entry point (default KOS_PCT) at the values where it changes form."""
+    got_cut, got_need = KC.oneshot_cuts(lib, tnum, halo, two)
+    assert got_cut == cut
+    assert len(got_need) == len(cut) - 1
+    if need is not None:
+        assert got_need == need
+
+
+def test_oneshot_cuts_properties(lib):
+    """Over a sweep of (tnum, halo): cuts strictly increase from 0 to tnum, interior cuts are multiples of 8, and what a block
+    needs on the device never shrinks, covers the block's right edge and stays inside the radargram."""
+    for tnum in (4096, 4097, 4100, 4103, 5000, 8191, 10000, 12345, 65536, 100001):
+        for halo in (16, 17, 100, tnum // 10, tnum // 4, tnum // 2 - 1, tnum // 2, tnum // 2 + 1, tnum, 3 * tnum):
+            for two in (False, True):
+                cut, need = KC.oneshot_cuts(lib, tnum, halo, two)
+                assert len(cut) in (3, 5) and len(need) == len(cut) - 1, (tnum, halo, two)
+                assert cut[0] == 0 and cut[-1] == tnum and all(a < b for a, b in zip(cut, cut[1:])), (tnum, halo, two, cut)
+                assert all(c % 8 == 0 for c in cut[1:-1]), (tnum, halo, two, cut)
+                assert all(a <= b for a, b in zip(need, need[1:])), (tnum, halo, two, need)
+                assert all(cut[i + 1] <= need[i] <= tnum for i in range(len(need))), (tnum, halo, two, cut, need)
+
+
 def test_route_agrees_with_what_the_library_reported(lib):
     """tests/kirch_route_recorded.json: impdar_kirch_plan_kernel / _mode / _tnum_pad / _xnoise of the gpu cases from a GPU run of
     the commit before kirch_route.h."""
