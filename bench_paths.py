@@ -1021,6 +1021,98 @@ def main():
                                                "spec, data (n bins) and Rfine (nf bins); stacking reads data once"},
                           "cpu_baseline": cb}), flush=True)
 
+    if 'autopick' not in args.skip:
+        # layer picking on the resident radargram: 16 seeds walked over every trace (a chain of dependent steps per
+        # seed and direction), then the two trace-parallel readers, the guided pick and the continuity index
+        import ctypes
+        from impdar_amd import picking
+        snum, tnum = (int(v) for v in args.chain.split('x'))
+        ctx, lib = _hip.context(), _hip.load()
+        nseeds, dt = 16, 1.0e-8
+        plength, FWW, scst, pol = 49, 17, 16, 1                        # PickParameters.freq_update(4) at this dt
+        rows = np.arange(snum, dtype=np.float32)[:, None]
+        cols = np.arange(tnum, dtype=np.float32)[None, :]
+        z0 = (np.arange(nseeds) + 1) * (snum // (nseeds + 1))
+        x = (0.05 * np.random.default_rng(9).standard_normal((snum, tnum))).astype(np.float32)
+        for z in z0:                                                   # one Ricker-shaped layer per seed, gently dipping
+            u = (rows - (z + 0.002 * cols + 2. * np.sin(cols / 9.))) / 6.
+            x += (1. - 2. * u ** 2) * np.exp(-u ** 2)
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+        t0 = tnum // 2
+        seeds = (z0.tolist(), [t0] * nseeds)
+
+        def spread(fn, reps=7):
+            fn()
+            ts = []
+            for _ in range(reps):
+                a = time.perf_counter()
+                fn()
+                lib.impdar_ctx_sync(ctx)
+                ts.append((time.perf_counter() - a) * 1e3)
+            return {"median": float(np.median(ts)), "min": min(ts), "max": max(ts), "reps": reps}
+
+        def pcopy_ms(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8                          # a copy reads and writes: half the bytes each way
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+            ms = spread(lambda: lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8)))
+            a.free()
+            b.free()
+            return ms
+
+        auto_ms = spread(lambda: picking.auto_pick_dev(d_x, *seeds, plength, FWW, scst, pol))
+        steps = max(t0 + 1, tnum - t0)                                 # the longer of a seed's two walks
+        step_ns = auto_ms["median"] * 1e6 / steps
+        mid = picking.midpoints(tnum, int(z0[3]), int(z0[3]) + 20)
+        guided_ms = spread(lambda: picking.pick_dev(d_x, 0, mid, plength, FWW, scst, pol))
+        guided_bytes = plength * tnum * 4
+        s = np.zeros(tnum, dtype=np.int32)
+        b = np.full(tnum, snum, dtype=np.int32)
+        cont_ms = spread(lambda: picking.continuity_dev(d_x, s, b, None))
+        cont_bytes = snum * tnum * 4
+        copies = {"guided": pcopy_ms(guided_bytes), "continuity": pcopy_ms(cont_bytes)}
+        cb = None
+        if not args.no_cpu:
+            m = min(tnum, 2000)
+
+            def np_packet(trace, midpoint):                            # the reference's packet_pick, restated
+                top = int(midpoint - plength / 2.)
+                pk = trace[top:int(midpoint + plength / 2.)]
+                c = int(np.argmax(pk[scst + 1:scst + FWW + 1] * pol) + scst + 1)
+                t = int(np.argmin(pk[c - FWW:c] * pol)) + c - FWW if c > FWW else (0 if c <= 1 else int(np.argmin(pk[:c] * pol)))
+                bo = int(np.argmin(pk[c + 1:c + FWW + 1] * pol)) + c + 1 if c + FWW < plength else plength - 1
+                return t + top, c + top, bo + top, np.sum(pk[t:bo + 1] ** 2.) / (bo - t + 1)
+            a = time.perf_counter()
+            midpoint = int(z0[0])
+            for j in range(m):                                         # one seed, one direction
+                t, _, bo, _ = np_packet(x[:, j], midpoint)
+                midpoint = (t + bo) // 2
+            el = time.perf_counter() - a
+            cb = {"seconds": el * tnum / m * nseeds, "kind": "reference", "cores": 1,
+                  "sample": "the reference's per-trace loop restated in NumPy, one seed over %d of %d traces, scaled to %d seeds "
+                            "over all" % (m, tnum, nseeds), "us_per_trace_and_seed": el / m * 1e6}
+        d_x.free()
+        print(json.dumps({"path": "autopick %d x %d float32, %d seeds" % (snum, tnum, nseeds),
+                          "config": "plength %d, FWW %d, scst %d; every seed starts at trace %d: two walks of %d and %d steps, one "
+                                    "wave each" % (plength, FWW, scst, t0, t0 + 1, tnum - t0),
+                          "device_ms": auto_ms["median"], "device_ms_spread": auto_ms,
+                          "trace_step": {"ns": step_ns, "cycles_at_2.4GHz": step_ns * 2.4, "hbm_miss_cycles_guide": 900,
+                                         "note": "time per call over the steps of the longer walk: an upper bound on a step, "
+                                                 "it holds the seed upload, the launch and the download of the picks"},
+                          "guided_pick_ms": guided_ms, "continuity_ms": cont_ms,
+                          "algorithmic_bytes": {"guided": guided_bytes, "continuity": cont_bytes},
+                          "hbm_frac": {"guided": guided_bytes / guided_ms["median"] / 1e6 / 8000.0,
+                                       "continuity": cont_bytes / cont_ms["median"] / 1e6 / 8000.0},
+                          "copy_same_bytes_ms": copies,
+                          "time_over_copy": {"guided": guided_ms["median"] / copies["guided"]["median"],
+                                             "continuity": cont_ms["median"] / copies["continuity"]["median"]},
+                          "roofline": {"bound": "latency", "note": "time per call (host clock around a device synchronise), with the "
+                                       "table uploads and the download of the result.  The chain is bound by the latency of a "
+                                       "step, not by bytes; the guided pick reads plength rows of every trace, the continuity "
+                                       "index every sample once"},
+                          "cpu_baseline": cb}), flush=True)
+
 
 if __name__ == '__main__':
     main()

@@ -129,6 +129,12 @@ SIGNATURES = {
     'impdar_apres_stack_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_apres_phase_diff': (_i, [_p, _dp, _dp, _i, _i, _i, _dp]),
     'impdar_apres_phase_diff_dev': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'impdar_auto_pick': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
+    'impdar_auto_pick_dev': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
+    'impdar_pick_guided': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _dp, _ip]),
+    'impdar_pick_guided_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _dp, _ip]),
+    'impdar_continuity': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _i, _d, _dp]),
+    'impdar_continuity_dev': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _i, _d, _dp]),
     'impdar_comm_unique_id': (_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),

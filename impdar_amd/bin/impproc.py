@@ -1,7 +1,9 @@
 #! /usr/bin/env python
 """``impproc migrate`` (and the steps usually run around it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise``,
 ``interp``, ``hbp``, ``lp``, ``crop``, ``nmo``, ``elev``, ``rev``, ``hcrop``, ``restack``, ``rgain`` and ``agc``) on the
-MI355X engine.
+MI355X engine, and ``autopick``, an extension: ``impproc autopick files --snums S ... --tnums T ... [--freq F] [--pol +-1]
+[--picknums N ...]`` picks one layer per seed (the reference's ``picklib.auto_pick``, which its GUI drives) and
+writes ``<name>_picked.mat``; the files come before the seed lists, which take every number that follows them.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
@@ -143,6 +145,21 @@ def _get_args():
     parser_agc.add_argument('-window', type=int, default=50, help='Number of samples to average')
     _add_def_args(parser_agc)
 
+    parser_autopick = subparsers.add_parser('autopick', help='(extension) Pick layers from seed points, as the last '
+                                                             'step of a chain')
+    parser_autopick.set_defaults(func=autopick, name='picked')
+    parser_autopick.add_argument('--snums', type=int, nargs='+', required=True,
+                                 help='Sample number of every seed (0 indexed)')
+    parser_autopick.add_argument('--tnums', type=int, nargs='+', required=True,
+                                 help='Trace number of every seed (0 indexed), as many as --snums')
+    parser_autopick.add_argument('--freq', type=float, default=None,
+                                 help='Pick frequency in MHz (default: that of the file\'s picks, else 4)')
+    parser_autopick.add_argument('--pol', type=int, default=None, choices=[1, -1],
+                                 help='Polarity of the centre peak (default: that of the file\'s picks, else 1)')
+    parser_autopick.add_argument('--picknums', type=int, nargs='+', default=None,
+                                 help='Numbers of the new picks (default: continue after the largest present)')
+    _add_def_args(parser_autopick)
+
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
@@ -270,6 +287,11 @@ def rgain(dat, slope=0.1, **kwargs):
 def agc(dat, window=50, scale_factor=50, **kwargs):
     """Automatic gain control.  ``scale_factor`` is forwarded as ``scaling_factor``, as in the reference."""
     dat.agc(window=window, scaling_factor=scale_factor)
+
+
+def autopick(dat, snums=(), tnums=(), picknums=None, freq=None, pol=None, **kwargs):
+    """(extension) Pick one layer per seed on the device and keep the picks for ``save``."""
+    dat.pick_layers(snums, tnums, picknums=picknums, freq=freq, pol=pol)
 
 
 def interp(dats, spacing, gps_fn=None, offset=0.0, minmove=1.0e-2, extrapolate=False, **kwargs):

@@ -14,8 +14,12 @@ axis: ``crop``, ``nmo``, ``constant_sample_depth_spacing`` and ``elev_correct``
 (``_RadarDataProcessing.py:50-337, 585-632``), the steps that change the
 trace axis, ``reverse``, ``hcrop`` and ``restack`` (``:20-47, 340-453``), the
 gains ``rangegain`` and ``agc`` (``:456-496``) and ``winavg_hfilt``
-(``_RadarDataFiltering.py:353-440``).  Everything else in the reference's
-class (picks, GPS, plotting) is out of scope.
+(``_RadarDataFiltering.py:353-440``), and picking as the last step of a chain:
+``pick_layers`` and ``continuity_index`` (``_RadarDataPicking.py``), after which
+``picks`` is a ``Picks`` object that ``save()`` writes.  A loaded ``picks``
+struct is still carried as ``_picks_struct`` until something picks.  Everything
+else in the reference's class (moving picks with the data, GPS, plotting) is
+out of scope.
 """
 import numpy as np
 
@@ -30,6 +34,7 @@ from ._RadarDataProcessing import constant_sample_depth_spacing as _constant_sam
 from ._RadarDataProcessing import elev_correct as _elev_correct, nmo as _nmo
 from ._RadarDataProcessing import hcrop as _hcrop, restack as _restack, reverse as _reverse
 from ._RadarDataProcessing import agc as _agc, rangegain as _rangegain
+from ._RadarDataPicking import continuity_index as _continuity_index, pick_layers as _pick_layers
 from ... import resident as _resident
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -61,6 +66,8 @@ class RadarData(object):
     rangegain = _rangegain
     agc = _agc
     winavg_hfilt = _winavg_hfilt
+    pick_layers = _pick_layers
+    continuity_index = _continuity_index
     to_device = _resident.to_device
     from_device = _resident.from_device
 
@@ -159,7 +166,9 @@ class RadarData(object):
         for attr in self.attrs_optional + self.stodeep_attrs:
             if getattr(self, attr, None) is not None:
                 mat[attr] = getattr(self, attr)
-        if self._picks_struct is not None:
+        if hasattr(self.picks, 'to_struct'):
+            mat['picks'] = self.picks.to_struct()
+        elif self._picks_struct is not None:
             mat['picks'] = self._picks_struct
         mat['flags'] = (self.flags if self.flags is not None else RadarFlags()).to_matlab()
         want = getattr(self, 'data_dtype', None)

@@ -421,6 +421,46 @@ int impdar_restack_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum,
 int impdar_reverse_dev(impdar_ctx *ctx, void *d_data_inout, int dtype, int snum, int tnum);
 int impdar_hcrop_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int lo, int hi, void *d_out);
 
+/* ---- layer picking (csrc/pick.hip) ------------------------------------------
+ * The reference's picker (src/impdar/lib/picklib.py) and its continuity index
+ * (src/impdar/lib/analysis/continuity_index.py) on a (snum, tnum) radargram,
+ * float32 or float64.  The *_dev forms take a resident array; picks, outcomes
+ * and the index always come back into host arrays.
+ * The packet rule (picklib.packet_pick:139-199) with the pick parameters
+ * plength, FWW, scst (PickParameters.freq_update) and pol (1 or -1): the packet
+ * is trace[slice(trunc(mid - plength / 2.), trunc(mid + plength / 2.))]; a pick
+ * is {top, centre, bottom, NaN, power}.  Outcomes: 0 picked, 1 packet shorter
+ * than scst + FWW (the reference's 'frequency is too high' ValueError), 2 / 3
+ * an empty argmax / argmin slice (NumPy's ValueError).
+ * impdar_auto_pick: picklib.auto_pick (:51-93).  Seed k starts at row
+ * seed_snum[k] of trace seed_tnum[k] (0 <= seed_tnum[k] < tnum), walks to trace
+ * 0 and then from seed_tnum[k] + 1 to tnum - 1, each midpoint (top + bottom) // 2
+ * of the pick before.  out: (nseeds, 5, tnum) host doubles; status: (nseeds, 2)
+ * host ints, {outcome, trace} of the first pick that failed in the reference's
+ * order (left walk first), {0, -1} if none did.  A walk stops where it fails;
+ * what it did not reach is NaN.
+ * impdar_pick_guided: picklib.pick (:16-48) on traces t0 ... t0 + n - 1, trace
+ * t0 + i around row mid[i].  out: (5, n) host doubles, NaN where a pick failed;
+ * status: {outcome, trace} of the first failing trace, {0, -1} if none.
+ * impdar_continuity: continuity_index (:27-81).  s, b: tnum host ints, the
+ * bounds of slice(surface, bed).indices(snum), or -1 for a NaN pick; cut_mode 1
+ * takes int(len * cutoff_ratio) rows off both ends (none left when that is 0, as
+ * the reference's p_ext[cut:-cut]).  out: tnum host doubles. */
+int impdar_auto_pick(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int nseeds,
+                     const int *seed_snum, const int *seed_tnum, int plength, int FWW, int scst, int pol,
+                     double *out, int *status);
+int impdar_auto_pick_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int nseeds,
+                         const int *seed_snum, const int *seed_tnum, int plength, int FWW, int scst, int pol,
+                         double *out, int *status);
+int impdar_pick_guided(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int t0, int n,
+                       const int *mid, int plength, int FWW, int scst, int pol, double *out, int *status);
+int impdar_pick_guided_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int t0, int n,
+                           const int *mid, int plength, int FWW, int scst, int pol, double *out, int *status);
+int impdar_continuity(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const int *s,
+                      const int *b, int cut_mode, double cutoff_ratio, double *out);
+int impdar_continuity_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const int *s,
+                          const int *b, int cut_mode, double cutoff_ratio, double *out);
+
 /* ---- quad-polarised ApRES (csrc/quadpol.hip) --------------------------------
  * The reference's second native hook (src/impdar/lib/ApresData/coherence.h:13,
  * called at _QuadPolProcessing.py:139-146): the hhvv coherence of two padded
