@@ -59,6 +59,7 @@ SIGNATURES = {
     'impdar_kirch_plan_tnum_pad': (_i, [_p]),
     'impdar_kirch_plan_xnoise': (_d, [_p]),
     'impdar_kirch_plan_kernel': (_i, [_p]),
+    'impdar_kirch_queue_policy': (_i, [_i, _i]),
     'impdar_kirch_prep': (_i, [_p, _p, _i, _i, _i]),
     'impdar_kirch_allgather': (_i, [_p]),
     'impdar_kirch_exchange': (_i, [_p, _i, _ip, _ip, _ip, _i, _ip, _ip, _ip]),
@@ -214,6 +215,14 @@ def check(rc, what=''):
     if rc == ERR_NODEV:
         raise HipUnavailableError(msg)
     raise RuntimeError('impdar HIP error %d: %s' % (rc, msg))
+
+
+def apply_queue_policy():
+    """Hand $IMPDAR_KIRCH_ORDER (chunk | packed) and $IMPDAR_KIRCH_G (1 | 2 | 4) to the library before a Kirchhoff plan is
+    created (impdar_kirch_queue_policy: the library itself does not read them).  Unset, or anything else: its own choice."""
+    order = {'chunk': 1, 'packed': 2}.get(os.environ.get('IMPDAR_KIRCH_ORDER', ''), 0)
+    gang = {'1': 1, '2': 2, '4': 4}.get(os.environ.get('IMPDAR_KIRCH_G', ''), 0)
+    check(load().impdar_kirch_queue_policy(order, gang), 'impdar_kirch_queue_policy')
 
 
 def device_count():

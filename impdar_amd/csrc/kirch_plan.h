@@ -47,6 +47,9 @@ struct impdar_kirch_plan : KirchGeometry, KirchRoute {
     DevBuf d_tilemap;           // ring kernels: (chunk, slot, XCD) -> output tile, balanced over the XCDs
     std::vector<short> h_tilemap;
     int tm_key[5] = {-1, -1, -1, -1, -1};   // (xlo, xhi, tile width, G, tiles_per_xcd) the cached map was built for
+    DevBuf d_items;             // ... persistent workgroups: the XCDs' item lists (FastParams::items)
+    std::vector<int> h_items;
+    int gm_key[5] = {-1, -1, -1, -1, -1};   // (xlo, xhi, tile width, gang size, order) the cached lists were built for
     // float32 data on a non-uniform (sorted) dist[]: kirch_gen_kernel (kirch_gen.h)
     DevBuf d_ga32, d_ga2_32, d_alo2, d_jr;
     std::vector<double> h_dist, h_zs2min;   // host copies for the per-(chunk, tile) input trace ranges

@@ -19,9 +19,11 @@ struct FastParams {
     int parts_log2;                // persistent ring kernels: every tile's walk as 1 << parts_log2 queue items (pieces)
     void *partial;                 // ... their partial images [piece][snum][ldo] (element type = image type)
     size_t part_stride;            // ... elements per partial image
-    int *queue;                    // quad kernel, persistent workgroups: 8 item counters (one per XCD, 64 bytes apart), zeroed
+    int *queue;                    // ring kernels, persistent workgroups: 8 item counters (one per XCD, 64 bytes apart), zeroed
                                    // before the launch; null = one item per block
-    const short *tilemap;          // ring kernels: [nchunks][tiles_per_xcd][8] output tile of (chunk, slot, XCD), -1 = none
+    const int *items;              // ... and the XCDs' lists of items (chunk << 16 | tile, kirch_gangmap): [0..7] their lengths,
+                                   // [8..15] where each starts, then the lists
+    const short *tilemap;          // one item per block: [nchunks][tiles_per_xcd][8] output tile of (chunk, slot, XCD), -1 = none
                                    // (host-balanced over the XCDs by step count, build_tilemap); null: arithmetic rule
     // tab kernel only:
     const int *klo, *khi;          // per (chunk, |n|) first / last sample a trace at offset n is asked for
@@ -97,10 +99,12 @@ typedef double kd_d2 __attribute__((ext_vector_type(2)));
 // (Two functions, and the kernels leave differently after each -- the item loop after the queue, the kernel after the block
 // rule: one function with one way out is the same program but not the same instruction stream.)
 // P.queue != null: persistent workgroups.  As many workgroups as fit the chip are launched, and each keeps
-// pulling (chunk, tile) items: first from the list of the XCD it runs on (the balanced tile map, longest
-// first), then, when that is empty, from the other XCDs' lists.  The XCDs of one MI355X differ by ~3 % in
-// speed on this loop and blocks are dealt to them statically, so with one item per block the slowest XCD set
-// the kernel's end; the queue also closes the gaps between workgroups and shortens the tail.
+// pulling (chunk, tile) items: first from the list of the XCD it runs on (kirch_gangmap: gangs of adjacent tiles
+// in consecutive positions, so the workgroups of an XCD that pull together walk neighbouring tiles of one chunk
+// in phase), then, when that is empty, the next unread item of the other XCDs' lists in turn.  The XCDs of one
+// MI355X differ by ~3 % in speed on this loop and blocks are dealt to them statically, so with one item per block
+// the slowest XCD set the kernel's end; the queue also closes the gaps between workgroups and shortens the tail.
+// The item is what the list holds: lists differ in length and say nothing about the chunk by position.
 // `item_slot`: three ints of LDS behind the image(s).
 __device__ __forceinline__ int kirch_ring_queue_item(const FastParams &P, int *item_slot, int &part)
 {
@@ -108,21 +112,14 @@ __device__ __forceinline__ int kirch_ring_queue_item(const FastParams &P, int *i
     if (threadIdx.x == 0) {
         unsigned xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        const int total = P.nchunks * P.tiles_per_xcd;
         int it = -1;
         for (int v = 0; v < 8 && it < 0; ++v) {
             const int x = (int)((xcc + v) & 7u);
-            for (;;) {
-                const int i2 = atomicAdd(P.queue + x * 16, 1);
-                const int i = i2 >> P.parts_log2;            // many-rank plans: 2 or 4 queue items per tile
-                if (i >= total) break;
-                item_slot[2] = i2 & ((1 << P.parts_log2) - 1);
-                const int t = (int)P.tilemap[(size_t)i * 8 + x];
-                if (t >= 0 && t < P.nxt) {
-                    it = ((i / P.tiles_per_xcd) << 16) | t;
-                    break;
-                }
-            }
+            const int i2 = atomicAdd(P.queue + x * 16, 1);
+            const int i = i2 >> P.parts_log2;                // many-rank plans: 2 or 4 queue items per tile
+            if (i >= P.items[x]) continue;
+            item_slot[2] = i2 & ((1 << P.parts_log2) - 1);
+            it = P.items[P.items[8 + x] + i];
         }
         item_slot[0] = it;
     }
@@ -252,6 +249,30 @@ static int build_tilemap(impdar_kirch_plan *p, FastParams &P, int tile_w, int al
     return IMPDAR_OK;
 }
 
+// The queue lists of a launch (kirch_gangmap, kirch_route.h) in the layout of FastParams::items, kept with the plan under the
+// key they were built for: the output block, the tile width and the plan's two queue knobs as this launch resolves them.
+static int build_gangmap(impdar_kirch_plan *p, FastParams &P, int tile_w, int align_mask, int ring_blocks, int step_block, hipStream_t st)
+{
+    P.items = nullptr;
+    const int key[5] = {P.xlo, P.xhi, tile_w, kirch_gang_size(*p, P.nxt), kirch_queue_order(*p, P.nxt)};
+    if (memcmp(key, p->gm_key, sizeof(key)) != 0 || p->h_items.empty()) {
+        const KirchGangMap M = kirch_gangmap(p->h_hmax, p->tnum, P.xlo, P.xhi, tile_w, align_mask, ring_blocks, step_block, key[3], key[4], P.nchunks);
+        if (M.items() == 0) return IMPDAR_OK;
+        std::vector<int> flat(16);
+        for (int x = 0; x < 8; ++x) {
+            flat[x] = (int)M.list[x].size();
+            flat[8 + x] = (int)flat.size();
+            flat.insert(flat.end(), M.list[x].begin(), M.list[x].end());
+        }
+        p->h_items.swap(flat);
+        memcpy(p->gm_key, key, sizeof(key));
+        IMPDAR_HIP_CHECK(p->d_items.ensure(p->h_items.size() * sizeof(int)));
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(p->d_items.p, p->h_items.data(), p->h_items.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    P.items = p->d_items.as<int>();
+    return IMPDAR_OK;
+}
+
 // Workgroup slots the persistent ring kernels leave EMPTY in a multi-rank plan.  They launch exactly as many
 // workgroups as are resident at once and keep them until the diffraction sum ends; RCCL's send/recv and all-gather
 // are kernels too (ncclDevKernel_Generic: workgroups of their own, with LDS).  Measured on one GPU with a rank of an
@@ -320,9 +341,12 @@ static int launch_ring(impdar_kirch_plan *p, const FastParams &P0, hipStream_t s
     FastParams P = P0;
     const int ntiles = (P.xhi - (P.xlo & ~K::align_mask) + XB * NH - 1) / (XB * NH);      // workgroup tiles start at a multiple of 8 (4)
     P.nxt = ntiles;
-    // groups of 4 adjacent tiles per XCD share staging lines in L2 (same-box A/B at config 3: 1.2-1.6 %
-    // faster than 1, L2 misses -36 %; 6 / 8 / 12 are slower), but the XCDs only stay balanced when each gets many
-    // groups: with the 45-70 tiles of an 8-rank block groups of 4 leave half of the XCDs with twice the work (-16 %).
+    // P.G: the groups of the one-item-per-block launch (tile map / arithmetic rule) and the padding of its grid.
+    // Groups of 4 adjacent tiles per XCD share staging lines in L2 (same-box A/B at config 3 with 250 tiles of 40: 1.2-1.6 %
+    // faster than 1, L2 misses -36 %; 6 / 8 / 12 are slower), but with blocks dealt statically the XCDs only stay balanced
+    // when each gets many groups: with the 45-70 tiles of an 8-rank block groups of 4 leave half of the XCDs with twice
+    // the work (-16 %).  The persistent launch has its own gangs and order: kirch_gang_size, kirch_gangmap
+    // (profiles/kirch_gangs.txt).
     P.G = ntiles >= 256 ? 4 : 1;
     const int per = 8 * P.G;
     const int nxt_pad = ((ntiles + per - 1) / per) * per;
@@ -359,7 +383,11 @@ static int launch_ring(impdar_kirch_plan *p, const FastParams &P0, hipStream_t s
         const int pl2 = NH == 1 ? p->walk_parts_log2 : 0;
         const size_t nout = (size_t)P.snum * P.ldo, esz = impdar_dtype_size(p->dtype);
         const bool pieces = pl2 > 0 && p->slots > 0 && p->d_partial.ensure((nout << pl2) * esz) == hipSuccess;
-        if (p->slots > 0 && (p->slots < nblk || pieces) && p->d_queue.ensure(8 * 64) == hipSuccess) {
+        if (p->slots > 0 && (p->slots < nblk || pieces)) {
+            const int grc = build_gangmap(p, P, XB * NH, K::align_mask, K::ring_blocks, K::step_block, st);
+            if (grc) return grc;
+        }
+        if (P.items && p->d_queue.ensure(8 * 64) == hipSuccess) {
             IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_queue.p, 0, 8 * 64, st));
             P.queue = p->d_queue.as<int>();
             if (pieces) {
@@ -413,6 +441,7 @@ static FastParams kirch_ring_params(impdar_kirch_plan *p, void *d_out, int xlo, 
     P.mrow0 = p->mrow0;
     P.tilemap = nullptr;
     P.queue = nullptr;
+    P.items = nullptr;
     P.parts_log2 = 0;
     P.partial = nullptr;
     P.part_stride = 0;

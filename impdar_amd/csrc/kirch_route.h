@@ -48,6 +48,22 @@ static_assert(kd_ring_slots(20) == 28 && kd_piece_bytes(20) == 7424 && kd_ring_s
 #ifndef KQ_DEFAULT_LK
 #define KQ_DEFAULT_LK 0     // extra ring groups / blocks of staging lookahead with NH >= 2 (IMPDAR_KIRCH_LK overrides)
 #endif
+// The queue lists of the persistent ring kernels (kirch_gangmap): their order, and the adjacent tiles per gang where a
+// launch has tiles enough for KQ_GANG_MIN_GROUPS gangs per chunk on every XCD (kirch_queue_order, kirch_gang_size).  Same-box
+// A/B at config 3 (157 workgroup tiles; profiles/kirch_gangs.txt): packed order with gangs of 4 is 2.7-3.1 % faster than the chunk
+// order without gangs; the order alone gives 1.5 %, gangs of 4 alone 1.1 %, gangs of 2 half of that; the float64 ring (250
+// tiles) gains 2.4 %.  Launches too short for gangs keep the chunk order: on the block of a rank of a 4-rank plan (63 tiles,
+// walks in 2 pieces) the packed order measured 3.4 % SLOWER, of an 8-rank plan (32 tiles, 4 pieces) the same.
+enum { KIRCH_ORDER_AUTO = -1, KIRCH_ORDER_CHUNK = 0, KIRCH_ORDER_PACKED = 1 };
+#ifndef KQ_DEFAULT_ORDER
+#define KQ_DEFAULT_ORDER KIRCH_ORDER_AUTO       // packed where the launch has tiles for gangs, else chunk; impdar_kirch_queue_policy overrides
+#endif
+#ifndef KQ_DEFAULT_GANG
+#define KQ_DEFAULT_GANG 4                       // of the packed order; impdar_kirch_queue_policy overrides
+#endif
+#ifndef KQ_GANG_MIN_GROUPS
+#define KQ_GANG_MIN_GROUPS 4
+#endif
 // Row stride of the step-block pick table in 16-byte entries.  Not snum: with snum a power of two a chunk's
 // slice of consecutive rows (256 entries out of every snum) lands on 1/16 of the L2's sets (and of whatever else
 // indexes by address bits); the odd number of 256-byte lines of padding walks the slice over all of them.
@@ -76,6 +92,19 @@ struct KirchKnobs {
     int impl = IMPL_DEFAULT;            // IMPDAR_KIRCH_IMPL = tab | gen
     int exact_impl = EXACT_DEFAULT;     // IMPDAR_KIRCH_EXACT_IMPL = tab | pair: keeps the float64 ring out
     bool tiefix_off = false;            // IMPDAR_KIRCH_TIEFIX = 0 (diagnostic)
+    // The two queue knobs are no environment variables of the library (it reads 20, and that is its limit): the caller hands
+    // them over with impdar_kirch_queue_policy, process-wide, and a plan takes what stands when it is created.  The Python
+    // host side does that from IMPDAR_KIRCH_ORDER / IMPDAR_KIRCH_G (impdar_amd._hip.apply_queue_policy).
+    enum { ORDER_DEFAULT = 0, ORDER_CHUNK = 1, ORDER_PACKED = 2 };
+    bool g_set = false;
+    int g = 0;                          // 1 | 2 | 4: adjacent tiles per gang of the queue lists (kirch_gangmap)
+    int order = ORDER_DEFAULT;          // chunk | packed: the order of the queue lists
+    // (order, gang) as impdar_kirch_queue_policy left them: ORDER_*, and 0 = the library's choice.  One instance per library.
+    __attribute__((visibility("hidden"))) static int *queue_policy()
+    {
+        static int v[2] = {ORDER_DEFAULT, 0};
+        return v;
+    }
 
     static KirchKnobs from_env()
     {
@@ -94,13 +123,16 @@ struct KirchKnobs {
         K.impl = !ie ? IMPL_DEFAULT : (!strcmp(ie, "tab") ? IMPL_TAB : (!strcmp(ie, "gen") ? IMPL_GEN : IMPL_DEFAULT));
         K.exact_impl = !ee ? EXACT_DEFAULT : (!strcmp(ee, "pair") ? EXACT_PAIR : EXACT_TAB);
         K.tiefix_off = te && !strcmp(te, "0");
+        K.order = queue_policy()[0];
+        K.g = queue_policy()[1];
+        K.g_set = K.g != 0;
         return K;
     }
     bool operator==(const KirchKnobs &o) const
     {
         return xb_set == o.xb_set && nh_set == o.nh_set && lk_set == o.lk_set && parts_set == o.parts_set && nhd_set == o.nhd_set &&
                xbd_set == o.xbd_set && xb == o.xb && nh == o.nh && lk == o.lk && parts == o.parts && nhd == o.nhd && xbd == o.xbd &&
-               impl == o.impl && exact_impl == o.exact_impl && tiefix_off == o.tiefix_off;
+               impl == o.impl && exact_impl == o.exact_impl && tiefix_off == o.tiefix_off && g_set == o.g_set && g == o.g && order == o.order;
     }
 };
 
@@ -191,8 +223,10 @@ struct KirchRoute {
     bool xtab_off = false;
     bool tie_ambiguous = false;     // more rounding-noise ties than the list holds: per-pair kernel only
     bool want_tie_groups = false;   // (kirch_route_after_ties) the downloaded list is to be grouped and kept
+    int order = KIRCH_ORDER_AUTO;   // ring kernels, queue lists: KIRCH_ORDER_CHUNK | _PACKED (kirch_gangmap); _AUTO: by the launch (kirch_queue_order)
+    int gang = 0;                   // ... adjacent tiles per gang, 1 | 2 | 4; 0: by the tile count of the launch (kirch_gang_size)
 
-    int kernel() const              // what impdar_kirch_plan_kernel reports
+    int kernel() const             // what impdar_kirch_plan_kernel reports
     {
         if (gen) return IMPDAR_KERNEL_GEN;
         if (mode == IMPDAR_KIRCH_FAST) return quad ? IMPDAR_KERNEL_QUAD : IMPDAR_KERNEL_TAB;
@@ -278,6 +312,8 @@ static inline KirchRoute kirch_route(const KirchGeometry &G, int dtype, int snum
     // fixed order, so launches stay bit-reproducible (against whole walks the sum differs by rounding).
     const int parts = K.parts_set ? K.parts : (nranks >= 8 ? 4 : (nranks >= 4 ? 2 : 1));
     R.walk_parts_log2 = parts == 4 ? 2 : (parts == 2 ? 1 : 0);
+    R.order = K.order == KirchKnobs::ORDER_CHUNK ? KIRCH_ORDER_CHUNK : (K.order == KirchKnobs::ORDER_PACKED ? KIRCH_ORDER_PACKED : KQ_DEFAULT_ORDER);
+    R.gang = (K.g_set && (K.g == 1 || K.g == 2 || K.g == 4)) ? K.g : 0;
     R.nh = nhq;
     R.lk = lkq;
     R.quadW = wq;
@@ -548,6 +584,93 @@ static inline std::vector<short> kirch_tilemap(const std::vector<int> &h_hmax, i
     return map;
 }
 
+// The order of the queue lists of a launch of `ntiles` tiles per chunk under route R (the knob's, else packed where the
+// launch gets gangs), and its adjacent tiles per gang.  The chunk order keeps the rule the tile map
+// always had (groups of 4 from 256 tiles).  The packed order gangs KQ_DEFAULT_GANG tiles where every XCD still gets
+// KQ_GANG_MIN_GROUPS gangs of each chunk (config 3: 157 tiles -> 4.9 gangs of 4), else none: with fewer, whole gangs are
+// too coarse a unit to balance the XCDs' lists, and stealing moves a gang's tiles off the XCD that shares their lines.
+static inline int kirch_queue_order(const KirchRoute &R, int ntiles)
+{
+    if (R.order != KIRCH_ORDER_AUTO) return R.order;
+    return ntiles >= 8 * KQ_DEFAULT_GANG * KQ_GANG_MIN_GROUPS ? KIRCH_ORDER_PACKED : KIRCH_ORDER_CHUNK;
+}
+static inline int kirch_gang_size(const KirchRoute &R, int ntiles)
+{
+    if (R.gang) return R.gang;
+    if (kirch_queue_order(R, ntiles) == KIRCH_ORDER_CHUNK) return ntiles >= 256 ? 4 : 1;
+    return ntiles >= 8 * KQ_DEFAULT_GANG * KQ_GANG_MIN_GROUPS ? KQ_DEFAULT_GANG : 1;
+}
+
+// The work lists of the persistent ring kernels: one list of items (chunk << 16 | tile) per XCD, pulled front to back by the
+// workgroups running there (kirch_ring_queue_item), then stolen by the others.  The tiles of a chunk form gangs of G
+// adjacent tiles; a gang goes whole to one XCD and sits in consecutive positions, so the workgroups that pull it start
+// together, walk in phase, and meet each other's pick rows and staged trace groups in that XCD's L2.
+// KIRCH_ORDER_CHUNK: the order of kirch_tilemap read slot by slot -- chunk by chunk, longest first inside a chunk.
+// KIRCH_ORDER_PACKED: all gangs of all chunks in ONE order, longest first by the tile map's cost model (ties: chunk, then
+// tile), each dealt to the XCD with the least accumulated cost.  Costs then never rise along a list, the lists' costs differ
+// by at most one gang's, and what the XCDs pull last are the shortest items of the launch (the tail of the chunk order is a
+// whole chunk's mix).  No list at all: no queue (more tiles or chunks than an item encodes).
+struct __attribute__((visibility("hidden"))) KirchGangMap {
+    std::vector<int> list[8];
+    size_t items() const
+    {
+        size_t n = 0;
+        for (const auto &l : list) n += l.size();
+        return n;
+    }
+};
+static inline KirchGangMap kirch_gangmap(const std::vector<int> &h_hmax, int tnum, int xlo, int xhi, int tile_w, int align_mask, int ring_blocks,
+                                         int step_block, int G, int order, int nchunks)
+{
+    KirchGangMap M;
+    const int x00 = xlo & ~align_mask, nxt = (xhi - x00 + tile_w - 1) / tile_w;
+    if (G < 1 || nxt < 1 || nxt > 32767 || nchunks < 1 || nchunks > 32767 || (int)h_hmax.size() != nchunks) return M;
+    const int units = (nxt + G - 1) / G;
+    if (order != KIRCH_ORDER_PACKED) {
+        const int tpx = ((units + 7) / 8) * G;
+        const std::vector<short> map = kirch_tilemap(h_hmax, tnum, xlo, xhi, tile_w, align_mask, ring_blocks, step_block, G, tpx, nchunks);
+        for (size_t i = 0; i < map.size(); ++i)
+            if (map[i] >= 0) M.list[i & 7].push_back((int)((i / 8 / tpx) << 16) | map[i]);
+        return M;
+    }
+    // A gang's tiles run side by side, so it is as long as its longest tile (`len`: the order -- a short gang at the profile's
+    // end, or one with clipped apertures, must not wait among the short walks of shallow chunks); its weight `w` on the XCD's
+    // list is the sum.
+    struct Gang {
+        double len, w;
+        int c, u;
+    };
+    std::vector<Gang> gangs;
+    gangs.reserve((size_t)nchunks * units);
+    for (int c = 0; c < nchunks; ++c) {
+        const int hm = h_hmax[c];
+        for (int u = 0; u < units; ++u) {
+            double w = 0, len = 0;
+            for (int t = u * G; t < std::min((u + 1) * G, nxt); ++t) {      // (the cost of a tile as kirch_tilemap counts it)
+                const int x0 = x00 + t * tile_w;
+                const int nlo = std::max(-hm, -(x0 + tile_w - 1)), nhi = std::min(hm, tnum - 1 - x0);
+                const int blocks = std::max(0, nhi - nlo + step_block) / step_block;
+                const double wt = ((blocks + ring_blocks - 1) / ring_blocks) * ring_blocks + 8;
+                w += wt;
+                len = std::max(len, wt);
+            }
+            gangs.push_back({len, w, c, u});
+        }
+    }
+    std::sort(gangs.begin(), gangs.end(), [](const Gang &a, const Gang &b) {
+        return a.len > b.len || (a.len == b.len && (a.c < b.c || (a.c == b.c && a.u < b.u)));
+    });
+    double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (const Gang &g : gangs) {
+        int best = 0;
+        for (int x = 1; x < 8; ++x)
+            if (load[x] < load[best]) best = x;
+        for (int t = g.u * G; t < std::min((g.u + 1) * G, nxt); ++t) M.list[best].push_back((g.c << 16) | t);
+        load[best] += g.w;
+    }
+    return M;
+}
+
 // How the one-shot entry point (impdar_kirchhoff, kirch_oneshot.hip) takes a large radargram through in pieces.  OUTPUT
 // traces in blocks [cut[i], cut[i + 1]), one launch each; block i reads the input traces up to its right edge + the
 // aperture half width `halo` only, so its launch starts when input traces [0, need[i]) are on the device and the rest of
@@ -584,7 +707,7 @@ static inline KirchOneShotCuts kirch_oneshot_cuts(int tnum, int halo, bool two)
 // knobs[15]: xb_set, xb, nh_set, nh, lk_set, lk, parts_set, parts, nhd_set, nhd, xbd_set, xbd, impl, exact_impl, tiefix_off.
 // tie_count >= 0: kirch_route_after_ties(route, tie_count, tie_cap) is applied.
 // ints[32]: status, mode, kernel, tnum_pad, gen, genW, quad, dquad, xb, nh, lk, quadW, quadSH, walk_parts_log2, want_tie_scan, xtab_off,
-// tie_ambiguous, want_tie_groups, increasing, uni_t, uni_t11, uni_x, dist_sorted; dbls[16]: tmax, dt, dx, xnoise, sa, alpha, hest,
+// tie_ambiguous, want_tie_groups, increasing, uni_t, uni_t11, uni_x, dist_sorted, order, gang (the probe's knobs leave both at their defaults); dbls[16]: tmax, dt, dx, xnoise, sa, alpha, hest,
 // gen_need, err_limit, err_sa.
 static inline KirchKnobs kirch_probe_knobs(const int *k)
 {
@@ -606,6 +729,7 @@ extern "C" int impdar_kirch_route_probe(int dtype, int snum, int tnum, const dou
                        G.uni_t11, G.uni_x, G.dist_sorted};
     const double D[10] = {G.tmax, G.dt, G.dx, G.xnoise, G.sa, G.alpha, G.hest, G.gen_need, R.err_limit, R.err_sa};
     std::copy(I, I + 23, ints);
+    ints[23] = R.order, ints[24] = R.gang;
     std::copy(D, D + 10, dbls);
     return 0;
 }
@@ -669,6 +793,25 @@ extern "C" int impdar_kirch_tilemap_probe(const int *h_hmax, int nchunks, int tn
                                                step_block, G, tiles_per_xcd, nchunks);
     std::copy(m.begin(), m.end(), map);
     return (int)m.size();
+}
+
+// The queue lists of a launch: lens[8], and the lists one behind the other in items[] (at most nchunks * tiles entries);
+// returns the number of items (0: no queue).  G = 0 / order = -1: what kirch_gang_size / kirch_queue_order give a route that
+// leaves them to the launch.
+extern "C" int impdar_kirch_gangmap_probe(const int *h_hmax, int nchunks, int tnum, int xlo, int xhi, int tile_w, int align_mask, int ring_blocks,
+                                          int step_block, int G, int order, int *lens, int *items)
+{
+    KirchRoute R;
+    R.order = order;
+    R.gang = G;
+    const int ntiles = (xhi - (xlo & ~align_mask) + tile_w - 1) / tile_w;
+    const KirchGangMap M = kirch_gangmap(std::vector<int>(h_hmax, h_hmax + nchunks), tnum, xlo, xhi, tile_w, align_mask, ring_blocks, step_block,
+                                         kirch_gang_size(R, ntiles), kirch_queue_order(R, ntiles), nchunks);
+    for (int x = 0; x < 8; ++x) {
+        lens[x] = (int)M.list[x].size();
+        items = std::copy(M.list[x].begin(), M.list[x].end(), items);
+    }
+    return (int)M.items();
 }
 
 // returns the number of blocks; cut[blocks + 1], need[blocks] (at most 8 blocks)

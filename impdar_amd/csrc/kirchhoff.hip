@@ -221,6 +221,14 @@ extern "C" int impdar_kirch_plan_mode(const impdar_kirch_plan *p) { return p ? p
 extern "C" double impdar_kirch_plan_xnoise(const impdar_kirch_plan *p) { return p ? p->xnoise : -1.0; }
 extern "C" int impdar_kirch_plan_tnum_pad(const impdar_kirch_plan *p) { return p ? p->tnum_pad : IMPDAR_ERR_ARG; }
 extern "C" int impdar_kirch_plan_kernel(const impdar_kirch_plan *p) { return p ? p->kernel() : IMPDAR_ERR_ARG; }
+extern "C" int impdar_kirch_queue_policy(int order, int gang)
+{
+    if (order < KirchKnobs::ORDER_DEFAULT || order > KirchKnobs::ORDER_PACKED || !(gang == 0 || gang == 1 || gang == 2 || gang == 4))
+        return IMPDAR_ERR_ARG;
+    KirchKnobs::queue_policy()[0] = order;
+    KirchKnobs::queue_policy()[1] = gang;
+    return IMPDAR_OK;
+}
 
 // `more`: further input traces of the radargram whose first traces an earlier prep took, AFTER a migrate that reads
 // only those has been enqueued (the pipelined one-shot call): same buffer set, and no wait for that migrate -- it does

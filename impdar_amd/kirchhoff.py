@@ -25,6 +25,7 @@ class KirchhoffPlan(object):
         modes = {'auto': _hip.KIRCH_AUTO, 'exact': _hip.KIRCH_EXACT, 'fast': _hip.KIRCH_FAST}
         self._keep = [tt_sec, dist, ga, gb, gc]
         self.h = _hip._p()
+        _hip.apply_queue_policy()
         rc = self.lib.impdar_kirch_plan_create(
             ctx, _hip.dtype_code(self.dtype), self.snum, self.tnum, _hip.as_dp(dist)[1], _hip.as_dp(tt_sec)[1],
             float(vel), int(bool(nearfield)), int(uniform), h, _hip.as_dp(ga)[1], _hip.as_dp(gb)[1],

@@ -149,6 +149,7 @@ def migrationKirchhoff(dat, vel=1.69e8, nearfield=False, mode=None, ngpus=None):
     ka, p_ga = _hip.as_dp(ga)
     kb, p_gb = _hip.as_dp(gb)
     kc, p_gc = _hip.as_dp(gc)
+    _hip.apply_queue_policy()
     rc = lib.impdar_kirchhoff(ctx, data.ctypes.data_as(C.c_void_p), code, dat.snum, dat.tnum, p_dist, p_tt,
                               float(vel), int(bool(nearfield)), int(uniform), h, p_ga, p_gb, p_gc,
                               _MODES[mode], out.ctypes.data_as(_hip._dp))

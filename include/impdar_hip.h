@@ -152,6 +152,13 @@ typedef enum impdar_kirch_kernel {
     IMPDAR_KERNEL_GEN = 5           /* float32, non-uniform (sorted) dist: picks computed per pair, LDS-staged     */
 } impdar_kirch_kernel;
 int impdar_kirch_plan_kernel(const impdar_kirch_plan *plan);
+/* How the persistent ring kernels hand out their (chunk, tile) items, for every plan created after the call (process-wide;
+ * the plans that impdar_kirchhoff and mig_kirch_loop keep are rebuilt when it changes).  It changes no bit of an image.
+ *   order: 0 the library's choice by the launch, 1 chunk by chunk (longest first inside a chunk), 2 packed (one
+ *          longest-first order across all chunks)
+ *   gang : adjacent tiles of a chunk that go to one XCD together, 1, 2 or 4; 0 the library's choice
+ * Anything else is IMPDAR_ERR_ARG and changes nothing. */
+int impdar_kirch_queue_policy(int order, int gang);
 int impdar_kirch_prep(impdar_kirch_plan *plan, const void *d_data, int ld, int jlo, int nloc);
 int impdar_kirch_allgather(impdar_kirch_plan *plan);
 /* Halo form of the exchange ("grouped ncclSend/ncclRecv of halos when H < shard"): this rank sends
