@@ -31,6 +31,9 @@ sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.abspath(_
 FIELD = (4096, 10000)           # snum x tnum of the "stolt 4096 x 10000" line: the headline radargram's shape
 
 
+SPECTRA = (4096, 10000)                      # snum, tnum of the "spectra" line
+
+
 def stolt_first_call_child():
     """`bench_paths.py --stolt-first-call`: a fresh process, as `impproc migrate file.mat` is -- import, context, the FIRST Stolt
     call of the process on a host array under the IMPDAR_STOLT_FFT of the environment, a second call for contrast.  One JSON line."""
@@ -117,6 +120,36 @@ def apres_first_call():
     return {"cold": recs[0], "warm_cache": recs[1]}
 
 
+def spectra_first_call_child():
+    """`bench_paths.py --spectra-first-call`: a fresh process -- import, context, upload, the FIRST vertical spectrum of the process
+    on the resident radargram of the "spectra" line (nothing to compile or plan at an own-transform length), a second for contrast."""
+    from impdar_amd import _hip, spectra
+    snum, tnum = SPECTRA
+    x = np.random.default_rng(11).standard_normal((snum, tnum)).astype(np.float32)
+    t0 = time.perf_counter()
+    _hip.load()
+    d_x = _hip.DeviceArray.from_host(_hip.context(), x)
+    up = (time.perf_counter() - t0) * 1e3
+    walls = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        out = spectra.mean_spectrum_dev(d_x, 0)
+        walls.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"first_call_ms": walls[0], "second_call_ms": walls[1], "load_context_upload_ms": up,
+                      "finite": bool(np.isfinite(out).all())}))
+
+
+def spectra_first_call():
+    import os
+    import subprocess
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), '--spectra-first-call'], capture_output=True, text=True, timeout=240)
+        line = [l for l in r.stdout.splitlines() if l.startswith('{"first_call_ms"')]
+        return json.loads(line[-1]) if line else {"error": (r.stderr or r.stdout)[-300:]}
+    except Exception as exc:
+        return {"error": "%s: %s" % (type(exc).__name__, exc)}
+
+
 def stolt_first_calls(children=3):
     """The first-call children of the "stolt 4096 x 10000" line, started before this process touches the GPU.  Per form
     (the default route: the own mixed-radix transforms; IMPDAR_STOLT_FFT=rocfft: the plans) one process against an empty rocFFT
@@ -151,6 +184,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--stolt-first-call', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--apres-first-call', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--spectra-first-call', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--stolt', type=int, default=4096)
     ap.add_argument('--phsh', type=int, default=8192)
     ap.add_argument('--chain', type=str, default='4096x10000', help='snum x tnum of the band-pass / re-spacing lines')
@@ -162,8 +196,11 @@ def main():
         return stolt_first_call_child()
     if args.apres_first_call:
         return apres_first_call_child()
+    if args.spectra_first_call:
+        return spectra_first_call_child()
     field_first = stolt_first_calls() if 'field' not in args.skip else None        # (children first: this process has not opened the GPU yet)
     apres_first = apres_first_call() if 'apres' not in args.skip else None
+    spectra_first = spectra_first_call() if 'spectra' not in args.skip else None
     from impdar_amd import _hip, synth
     from impdar_amd.lib.RadarData import RadarData
     from impdar_amd.lib import migrationlib
@@ -1111,6 +1148,74 @@ def main():
                                        "table uploads and the download of the result.  The chain is bound by the latency of a "
                                        "step, not by bytes; the guided pick reads plength rows of every trace, the continuity "
                                        "index every sample once"},
+                          "cpu_baseline": cb}), flush=True)
+
+    if 'spectra' not in args.skip:
+        # spectra of the resident radargram: the mean spectrum along the samples (ft: transpose + 10000 rows of 4096), along the
+        # traces (hft: 4096 rows of 10000 = 2^4 5^4, the own mixed-radix transform) and the periodogram of every trace
+        import ctypes
+        import scipy.signal
+        from impdar_amd import spectra
+        snum, tnum = SPECTRA
+        ctx, lib = _hip.context(), _hip.load()
+        fs = 1.0e8
+        x = np.random.default_rng(11).standard_normal((snum, tnum)).astype(np.float32)
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+
+        def spread(fn, reps=7):
+            fn()
+            ts = []
+            for _ in range(reps):
+                a = time.perf_counter()
+                fn()
+                lib.impdar_ctx_sync(ctx)
+                ts.append((time.perf_counter() - a) * 1e3)
+            return {"median": float(np.median(ts)), "min": min(ts), "max": max(ts), "reps": reps}
+
+        def pcopy_ms(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8                          # a copy reads and writes: half the bytes each way
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+            ms = spread(lambda: lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8)))
+            a.free()
+            b.free()
+            return ms
+
+        def pgram():
+            spectra.periodogram_dev(d_x, fs, window='hann', scaling='spectrum', resident=True)[1].free()
+        ms = {"ft": spread(lambda: spectra.mean_spectrum_dev(d_x, 0)), "hft": spread(lambda: spectra.mean_spectrum_dev(d_x, 1)),
+              "periodogram": spread(pgram)}
+        nbytes = {"ft": snum * tnum * 4, "hft": snum * tnum * 4, "periodogram": snum * tnum * 4 + (snum // 2 + 1) * tnum * 8}
+        copies = {"ft": pcopy_ms(nbytes["ft"]), "periodogram": pcopy_ms(nbytes["periodogram"])}
+        copies["hft"] = copies["ft"]
+        d_x.free()
+        cb = None
+        if not args.no_cpu:
+            cb = {"kind": "reference", "cores": 1, "sample": "the reference's expressions on the float32 array, whole"}
+            a = time.perf_counter()
+            np.mean(np.abs(np.fft.fft(x, axis=0)) ** 2.0, axis=1)
+            cb["ft_seconds"] = time.perf_counter() - a
+            a = time.perf_counter()
+            np.mean(np.abs(np.fft.fft(x, axis=1)) ** 2.0, axis=0)
+            cb["hft_seconds"] = time.perf_counter() - a
+            a = time.perf_counter()
+            for t in range(tnum):
+                scipy.signal.periodogram(x[:, t], fs=fs, window='hann', scaling='spectrum')
+            cb["periodogram_seconds"] = time.perf_counter() - a
+        print(json.dumps({"path": "spectra %d x %d float32" % (snum, tnum),
+                          "config": "ft: transpose to float64 + %d rows of %d (own power-of-two transform); hft: %d rows of %d (own "
+                                    "mixed-radix transform); periodogram: hann, 'spectrum', the image stays resident" % (tnum, snum, snum, tnum),
+                          "device_ms": {k: v["median"] for k, v in ms.items()}, "device_ms_spread": ms,
+                          "compulsory_bytes": nbytes,
+                          "hbm_frac": {k: nbytes[k] / ms[k]["median"] / 1e6 / 8000.0 for k in ms},
+                          "copy_same_bytes_ms": copies,
+                          "time_over_copy": {k: ms[k]["median"] / copies[k]["median"] for k in ms},
+                          "first_call": spectra_first,
+                          "roofline": {"bound": "memory", "note": "time per call (host clock around a device synchronise), with the "
+                                       "download of the mean spectrum.  Compulsory bytes: the float32 radargram once, plus the float64 "
+                                       "image for the periodogram; the column-wise cases move it twice more through the float64 "
+                                       "transpose (write and read of 8 bytes per sample)"},
                           "cpu_baseline": cb}), flush=True)
 
 

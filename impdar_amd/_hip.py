@@ -136,7 +136,12 @@ SIGNATURES = {
     'impdar_pick_guided_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_continuity': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _i, _d, _dp]),
     'impdar_continuity_dev': (_i, [_p, _p, _i, _i, _i, _ip, _ip, _i, _d, _dp]),
-    'impdar_comm_unique_id': (_i, [C.c_char_p]),
+    'impdar_mean_spectrum': (_i, [_p, _p, _i, _i, _i, _i, _dp]),
+    'impdar_mean_spectrum_dev': (_i, [_p, _p, _i, _i, _i, _i, _dp]),
+    'impdar_periodogram': (_i, [_p, _p, _i, _i, _i, _dp, _d, _p]),
+    'impdar_periodogram_dev': (_i, [_p, _p, _i, _i, _i, _dp, _d, _p]),
+    'impdar_spec_route_probe': (_i, [_i, C.c_longlong, _ip]),
+    'impdar_comm_unique_id':(_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),
     'impdar_comm_size': (_i, [_p]),

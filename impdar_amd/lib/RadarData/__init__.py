@@ -17,9 +17,12 @@ gains ``rangegain`` and ``agc`` (``:456-496``) and ``winavg_hfilt``
 (``_RadarDataFiltering.py:353-440``), and picking as the last step of a chain:
 ``pick_layers`` and ``continuity_index`` (``_RadarDataPicking.py``), after which
 ``picks`` is a ``Picks`` object that ``save()`` writes.  A loaded ``picks``
-struct is still carried as ``_picks_struct`` until something picks.  Everything
-else in the reference's class (moving picks with the data, GPS, plotting) is
-out of scope.
+struct is still carried as ``_picks_struct`` until something picks, and the
+spectra behind the reference's ``plot_ft``, ``plot_hft`` and
+``plot_spectrogram``: ``vertical_spectrum``, ``horizontal_spectrum`` and
+``spectrogram`` (``_RadarDataSpectra.py``; drawn by ``lib/plot.py``).  Everything
+else in the reference's class (moving picks with the data, GPS, the other
+plots) is out of scope.
 """
 import numpy as np
 
@@ -35,6 +38,8 @@ from ._RadarDataProcessing import elev_correct as _elev_correct, nmo as _nmo
 from ._RadarDataProcessing import hcrop as _hcrop, restack as _restack, reverse as _reverse
 from ._RadarDataProcessing import agc as _agc, rangegain as _rangegain
 from ._RadarDataPicking import continuity_index as _continuity_index, pick_layers as _pick_layers
+from ._RadarDataSpectra import horizontal_spectrum as _horizontal_spectrum, spectrogram as _spectrogram
+from ._RadarDataSpectra import vertical_spectrum as _vertical_spectrum
 from ... import resident as _resident
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -68,6 +73,9 @@ class RadarData(object):
     winavg_hfilt = _winavg_hfilt
     pick_layers = _pick_layers
     continuity_index = _continuity_index
+    vertical_spectrum = _vertical_spectrum
+    horizontal_spectrum = _horizontal_spectrum
+    spectrogram = _spectrogram
     to_device = _resident.to_device
     from_device = _resident.from_device
 

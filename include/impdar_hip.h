@@ -468,6 +468,36 @@ int impdar_continuity(impdar_ctx *ctx, const void *data, int dtype, int snum, in
 int impdar_continuity_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const int *s,
                           const int *b, int cut_mode, double cutoff_ratio, double *out);
 
+/* ---- spectra (csrc/spectrum.hip) ---------------------------------------------
+ * Diagnostics of a (snum, tnum) radargram, float32 or float64, host (no suffix)
+ * or resident (_dev).  Data of either dtype is widened to float64 on load;
+ * transforms, powers and sums run in float64 and the results are float64.
+ * Sums are formed in a fixed order without atomics: two calls on the same data
+ * give the same bits.  Any snum, tnum >= 1.
+ * impdar_mean_spectrum: src/impdar/lib/plot.py:310-312 (axis 0) and :346-347
+ * (axis 1): out[k] = mean over the other axis of |fft(data, axis)[k]|^2, the
+ * unnormalised forward transform, k in numpy.fft.fftfreq order.  out: snum
+ * (axis 0) or tnum (axis 1) host doubles in both forms, the upper half filled
+ * by out[n - k] = out[k] (exact for real data).
+ * impdar_periodogram: plot.py:654-674, scipy.signal.periodogram of every trace:
+ * the trace's mean is subtracted, sample j multiplied by window[j] (snum host
+ * doubles; null: a boxcar), and out[k, t] = |rfft|^2 * scale, doubled for every
+ * k except 0 and, for even snum, snum / 2.  The caller derives `scale` from the
+ * window and the sampling rate (1 / sum(w)^2 or 1 / (fs sum(w^2))).  out:
+ * (snum / 2 + 1, tnum) float64, host for the host form, device for _dev (which
+ * enqueues on the context's compute stream and returns without waiting).
+ * impdar_spec_route_probe: what csrc/spec_route.h decides for `rows` sequences
+ * of length n: out[0] = 0 own power-of-two transform, 1 own mixed-radix
+ * transform, 2 rocFFT; out[1] workgroups; out[2] rows per workgroup; out[3]
+ * bytes of LDS per workgroup.  No device call. */
+int impdar_mean_spectrum(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int axis, double *out);
+int impdar_mean_spectrum_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int axis, double *out);
+int impdar_periodogram(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, const double *window,
+                       double scale, void *out);
+int impdar_periodogram_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, const double *window,
+                           double scale, void *d_out);
+int impdar_spec_route_probe(int n, long long rows, int *out);
+
 /* ---- quad-polarised ApRES (csrc/quadpol.hip) --------------------------------
  * The reference's second native hook (src/impdar/lib/ApresData/coherence.h:13,
  * called at _QuadPolProcessing.py:139-146): the hhvv coherence of two padded
