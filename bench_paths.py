@@ -1218,6 +1218,72 @@ def main():
                                        "transpose (write and read of 8 bytes per sample)"},
                           "cpu_baseline": cb}), flush=True)
 
+    if 'display' not in args.skip:
+        # what a plot reads from the resident radargram: the (10, 90) colour limits of all of it (4 histogram passes over the
+        # float32 samples), the (1, 99) limits of a 100-trace window (plot_traces), and the flattened image (a gather, one store pass)
+        import ctypes
+        from impdar_amd import display
+        snum, tnum = SPECTRA
+        ctx, lib = _hip.context(), _hip.load()
+        x = np.random.default_rng(13).standard_normal((snum, tnum)).astype(np.float32)
+        d_x = _hip.DeviceArray.from_host(ctx, x)
+        shift = np.round(200.0 * np.sin(np.arange(tnum) / 700.0)).astype(np.int32)
+        t0 = 5000
+
+        def spread(fn, reps=7):
+            fn()
+            ts = []
+            for _ in range(reps):
+                a = time.perf_counter()
+                fn()
+                lib.impdar_ctx_sync(ctx)
+                ts.append((time.perf_counter() - a) * 1e3)
+            return {"median": float(np.median(ts)), "min": min(ts), "max": max(ts), "reps": reps}
+
+        def dcopy_ms(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8                          # a copy reads and writes: half the bytes each way
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+            ms = spread(lambda: lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8)))
+            a.free()
+            b.free()
+            return ms
+
+        def flat():
+            display.flatten_dev(d_x, shift, resident=True).free()
+        passes = 4                                                     # one per 8-bit digit of a float32 key
+        ms = {"clims_10_90": spread(lambda: display.percentile_dev(d_x, (10, 90))),
+              "traces_1_99": spread(lambda: display.percentile_dev(d_x, (1, 99), x_range=(t0, t0 + 100), skip_nan=False)),
+              "flatten": spread(flat)}
+        got = display.percentile_dev(d_x, (10, 90))
+        nbytes = {"clims_10_90": snum * tnum * 4, "traces_1_99": snum * 100 * 4, "flatten": 2 * snum * tnum * 4}
+        copies = {k: dcopy_ms(max(v, 4096)) for k, v in nbytes.items()}
+        d_x.free()
+        cb = None
+        if not args.no_cpu:
+            cb = {"kind": "reference", "cores": 1, "sample": "np.percentile as the reference calls it, on the float32 array"}
+            a = time.perf_counter()
+            want = np.percentile(x[~np.isnan(x)], (10, 90))
+            cb["clims_10_90_seconds"] = time.perf_counter() - a
+            cb["same_bits"] = bool(np.array_equal(want, got))
+            a = time.perf_counter()
+            np.percentile(x[:, t0:t0 + 100], (1, 99))
+            cb["traces_1_99_seconds"] = time.perf_counter() - a
+        print(json.dumps({"path": "display %d x %d float32" % (snum, tnum),
+                          "config": "clims: (10, 90) of the whole radargram, NaNs skipped; traces: (1, 99) of traces %d-%d; flatten: every "
+                                    "trace shifted by up to 200 rows, the image stays resident" % (t0, t0 + 100),
+                          "device_ms": {k: v["median"] for k, v in ms.items()}, "device_ms_spread": ms,
+                          "compulsory_bytes": nbytes, "histogram_passes": passes,
+                          "hbm_frac": {k: nbytes[k] / ms[k]["median"] / 1e6 / 8000.0 for k in ms},
+                          "copy_same_bytes_ms": copies,
+                          "time_over_copy": {k: ms[k]["median"] / copies[k]["median"] for k in ms},
+                          "roofline": {"bound": "memory", "note": "time per call (host clock around a device synchronise).  Compulsory "
+                                       "bytes: the window once for the limits (the select streams it once per digit, %d times, with a "
+                                       "download of the histograms and a host step between the passes); the radargram read and the image "
+                                       "written once for the flatten" % passes},
+                          "cpu_baseline": cb}), flush=True)
+
 
 if __name__ == '__main__':
     main()

@@ -141,6 +141,11 @@ SIGNATURES = {
     'impdar_periodogram': (_i, [_p, _p, _i, _i, _i, _dp, _d, _p]),
     'impdar_periodogram_dev': (_i, [_p, _p, _i, _i, _i, _dp, _d, _p]),
     'impdar_spec_route_probe': (_i, [_i, C.c_longlong, _ip]),
+    'impdar_order_stats': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _dp, _i, _i, C.POINTER(C.c_longlong), _p]),
+    'impdar_order_stats_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _dp, _i, _i, C.POINTER(C.c_longlong), _p]),
+    'impdar_flatten': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _p]),
+    'impdar_flatten_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _p]),
+    'impdar_window_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'impdar_comm_unique_id':(_i, [C.c_char_p]),
     'impdar_comm_init': (_i, [_p, C.c_char_p, _i, _i]),
     'impdar_comm_rank': (_i, [_p]),

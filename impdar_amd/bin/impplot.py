@@ -1,10 +1,14 @@
 #! /usr/bin/env python
 # -*- coding: utf-8 -*-
-"""``impplot`` for the spectra this engine computes: ``ft``, ``hft`` and ``spectrogram``, with the reference's option
-names (``src/impdar/bin/impplot.py``).  The spectra are computed on the MI355X (``impdar_amd/lib/plot.py``); the
-reference's other sub-commands (rg, traces, power) are not part of this engine.
+"""``impplot``: ``rg``, ``traces``, ``power``, ``ft``, ``hft`` and ``spectrogram``, with the reference's option names
+(``src/impdar/bin/impplot.py``).  What reads the whole radargram -- colour limits, the flattened image, the spectra -- is
+computed on the MI355X (``impdar_amd/lib/plot.py``).
 
-    python -m impdar_amd.bin.impplot ft [-s] [-o OUT] [--o_fmt png] [-dpi 300] files
+    python -m impdar_amd.bin.impplot rg [-s] [-o OUT] [--o_fmt png] [-dpi 300] [-xd] [-yd | -dualy] [-picks] [-clims LO HI]
+                                        [-flatten_layer N] [-cmap gray] files
+    python -m impdar_amd.bin.impplot traces [-yd | -dualy] ... files T_START T_END
+    python -m impdar_amd.bin.impplot power ... files LAYER
+    python -m impdar_amd.bin.impplot ft ... files
     python -m impdar_amd.bin.impplot hft ... files
     python -m impdar_amd.bin.impplot spectrogram files FREQ_LOWER FREQ_UPPER [-window W] [-scaling spectrum|density]
 """
@@ -17,6 +21,19 @@ from ..lib.load import FILETYPE_OPTIONS
 def _get_args():
     parser = argparse.ArgumentParser()
     subparsers = parser.add_subparsers(help='sub-command help')
+    rg = _add_parser(subparsers, 'rg', 'Plot radargram', plot_radargram)
+    rg.add_argument('-xd', action='store_true', help='Plot the dist rather than the trace number')
+    _add_depth_args(rg)
+    rg.add_argument('-picks', action='store_true', help='Plot picks')
+    rg.add_argument('-clims', nargs=2, type=float, help='Color limits')
+    rg.add_argument('-flatten_layer', type=int, default=None, help='Distort plot so this layer is flat')
+    rg.add_argument('-cmap', type=str, default='gray', help='Color map name')
+    traces = _add_parser(subparsers, 'traces', 'Plot traces vs depth', plot_traces)
+    _add_depth_args(traces)
+    traces.add_argument('t_start', type=int, help='Starting trace number')
+    traces.add_argument('t_end', type=int, help='Ending trace number')
+    power = _add_parser(subparsers, 'power', 'Plot power on a layer', plot_power)
+    power.add_argument('layer', type=int, help='Layer upon which to plot the power')
     _add_parser(subparsers, 'ft', 'Plot the power spectrum in the vertical', plot_ft)
     _add_parser(subparsers, 'hft', 'Plot the power spectrum in the horizontal', plot_hft)
     spec = _add_parser(subparsers, 'spectrogram', 'Plot spectrogram for all traces', plot_spectrogram)
@@ -38,6 +55,32 @@ def _add_parser(subparsers, name, helpstr, func):
     parser.add_argument('-dpi', type=int, default=300, help='Save file with this resolution (default 300)')
     parser.add_argument('--in_fmt', type=str, help='Type of file', default='mat', choices=FILETYPE_OPTIONS)
     return parser
+
+
+def _add_depth_args(parser):
+    parser.add_argument('-yd', action='store_true', help='Plot the depth rather than travel time')
+    parser.add_argument('-dualy', action='store_true', help='Primary y axis is TWTT, secondary is depth')
+
+
+def plot_radargram(fns=None, s=False, o=None, xd=False, yd=False, o_fmt='png', dpi=300, in_fmt='mat', picks=False, clims=None,
+                   cmap='gray', flatten_layer=None, dualy=False, **kwargs):
+    """Plot the data as a radio echogram, with its picks and with a picked layer made flat if asked for."""
+    from ..lib import plot
+    plot.plot(fns, xd=xd, yd=yd, s=s, o=o, ftype=o_fmt, dpi=dpi, filetype=in_fmt, pick_colors=picks, cmap=cmap, clims=clims,
+              flatten_layer=flatten_layer, dualy=dualy)
+
+
+def plot_traces(fns=None, t_start=None, t_end=None, yd=False, dualy=False, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat',
+                **kwargs):
+    """Plot traces t_start to t_end as amplitude against travel time or depth."""
+    from ..lib import plot
+    plot.plot(fns, tr=(t_start, t_end), yd=yd, s=s, o=o, ftype=o_fmt, dpi=dpi, dualy=dualy, filetype=in_fmt)
+
+
+def plot_power(fns=None, layer=None, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat', **kwargs):
+    """Plot the power returned from a picked layer, all files on one axis."""
+    from ..lib import plot
+    plot.plot(fns, power=layer, s=s, o=o, ftype=o_fmt, dpi=dpi, filetype=in_fmt)
 
 
 def plot_ft(fns=None, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat', **kwargs):

@@ -181,6 +181,7 @@ void impdar_quadpol_forget(impdar_ctx *ctx);       // quadpol.hip
 void impdar_apres_forget(impdar_ctx *ctx);         // apres.hip
 void impdar_pick_forget(impdar_ctx *ctx);          // pick.hip
 void impdar_spectrum_forget(impdar_ctx *ctx);      // spectrum.hip
+void impdar_display_forget(impdar_ctx *ctx);       // display.hip
 
 void impdar_kirch_trim();    // kirch_oneshot.hip
 void impdar_stolt_trim();    // stolt.hip
@@ -626,6 +627,7 @@ extern "C" void impdar_ctx_destroy(impdar_ctx *ctx)
     impdar_apres_forget(ctx);
     impdar_pick_forget(ctx);
     impdar_spectrum_forget(ctx);
+    impdar_display_forget(ctx);
     impdar_devcache_trim(ctx->device);
     pinned_adopt(ctx);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);

@@ -20,9 +20,11 @@ gains ``rangegain`` and ``agc`` (``:456-496``) and ``winavg_hfilt``
 struct is still carried as ``_picks_struct`` until something picks, and the
 spectra behind the reference's ``plot_ft``, ``plot_hft`` and
 ``plot_spectrogram``: ``vertical_spectrum``, ``horizontal_spectrum`` and
-``spectrogram`` (``_RadarDataSpectra.py``; drawn by ``lib/plot.py``).  Everything
-else in the reference's class (moving picks with the data, GPS, the other
-plots) is out of scope.
+``spectrogram`` (``_RadarDataSpectra.py``; drawn by ``lib/plot.py``), and what
+its ``plot_radargram`` and ``plot_traces`` read: ``percentiles``, ``window``
+and ``flattened`` (``_RadarDataDisplay.py``).  Everything else in the
+reference's class (moving picks with the data, GPS, the ApRES plots) is out
+of scope.
 """
 import numpy as np
 
@@ -40,6 +42,7 @@ from ._RadarDataProcessing import agc as _agc, rangegain as _rangegain
 from ._RadarDataPicking import continuity_index as _continuity_index, pick_layers as _pick_layers
 from ._RadarDataSpectra import horizontal_spectrum as _horizontal_spectrum, spectrogram as _spectrogram
 from ._RadarDataSpectra import vertical_spectrum as _vertical_spectrum
+from ._RadarDataDisplay import flattened as _flattened, percentiles as _percentiles, window as _window
 from ... import resident as _resident
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -76,6 +79,9 @@ class RadarData(object):
     vertical_spectrum = _vertical_spectrum
     horizontal_spectrum = _horizontal_spectrum
     spectrogram = _spectrogram
+    percentiles = _percentiles
+    window = _window
+    flattened = _flattened
     to_device = _resident.to_device
     from_device = _resident.from_device
 

@@ -621,6 +621,40 @@ int impdar_apres_phase_diff(impdar_ctx *ctx, const double *s1, const double *s2,
 int impdar_apres_phase_diff_dev(impdar_ctx *ctx, const double *d_s1, const double *d_s2, int len, int win, int step,
                                 double *d_co);
 
+/* ---- what a plot reads from the radargram (csrc/display.hip) ----
+ * data: (snum, tnum) float32 / float64, row-major; a window is rows [y0, y1),
+ * traces [x0, x1) of it, 0 <= y0 <= y1 <= snum, 0 <= x0 <= x1 <= tnum.
+ * impdar_order_stats: the neighbours of np.percentile's linear method.
+ * counts[0] = N, the elements of the window; counts[1] = how many are NaN.
+ * With n = N - counts[1] and, in float64, lo = floor((n - 1) (q[i] / 100)),
+ * hi = min(lo + 1, n - 1): vals[2 i] and vals[2 i + 1] (of the data's dtype)
+ * are the values of rank lo and hi among the window's n values that are no
+ * NaN -- exactly, as a sort would place them (-0.0 and 0.0 count as equal).
+ * 1 <= nq <= 8, 0 <= q[i] <= 100.  Where n == 0, or skip_nan == 0 and the
+ * window holds a NaN, vals are NaN and the call succeeds: the counts say so.
+ * Integer atomics only: two calls give the same bits.
+ * impdar_flatten: out is (snum, x1 - x0) of the data's dtype,
+ *   out[i, j] = data[i - shift[j], x0 + j]   where 0 <= i - shift[j] < snum,
+ * NaN elsewhere and in every column with shift[j] == IMPDAR_FLATTEN_NONE
+ * (plot.py:240-254 with shift = int(offset), NONE for a NaN offset).  shift:
+ * x1 - x0 host values; x1 > x0.
+ * impdar_window_dev: the window of a resident array into the dense
+ * (y1 - y0, x1 - x0) host array `out`; waits for the copy.
+ * The *_dev forms take device arrays; counts, vals, q and shift stay host
+ * arrays.  impdar_order_stats_dev waits for its result; impdar_flatten_dev
+ * enqueues on the context's compute stream and returns. */
+#define IMPDAR_FLATTEN_NONE (-2147483647 - 1)
+int impdar_order_stats(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int y0, int y1, int x0, int x1,
+                       const double *q, int nq, int skip_nan, long long *counts, void *vals);
+int impdar_order_stats_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int y0, int y1, int x0,
+                           int x1, const double *q, int nq, int skip_nan, long long *counts, void *vals);
+int impdar_flatten(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int x0, int x1, const int *shift,
+                   void *out);
+int impdar_flatten_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int x0, int x1,
+                       const int *shift, void *d_out);
+int impdar_window_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int y0, int y1, int x0, int x1,
+                      void *out);
+
 /* float32 <-> float64 conversion of a resident array of `n` elements (NumPy's astype, on the device) */
 int impdar_cast_dev(impdar_ctx *ctx, const void *d_src, int src_dtype, void *d_dst, int dst_dtype, size_t n);
 
