@@ -1058,6 +1058,72 @@ def main():
                                                "spec, data (n bins) and Rfine (nf bins); stacking reads data once"},
                           "cpu_baseline": cb}), flush=True)
 
+        # ApRES load at the same size: an instrument's uint16 counts (synthesised in memory) to resident float64 chirps.  Per call
+        # with spreads: today's route (the reference's host decode, then the float64 upload), the counts route (counts upload in
+        # pieces + device decode), the decode kernel alone (one piece, the context's kernel timer) against HBM at 10 B per sample
+        # and against a device copy of the same bytes; then .DAT files on a tmpfs path to the stacked profile on both routes
+        import os
+        import shutil
+        import tempfile
+        from impdar_amd.lib.ApresData import load_apres as la
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+        import apres_io_ref as io_ref
+        total = rows * snum
+        counts = np.random.default_rng(11).integers(0, 65536, size=total, dtype=np.uint16)
+        d_volts = _hip.DeviceArray(ctx, (rows, snum), np.float64)
+        cptr = counts.ctypes.data_as(ctypes.c_void_p)
+
+        def host_route():
+            d = _hip.DeviceArray.from_host(ctx, (counts.astype(float) * 2.5 / 2**16.).reshape(rows, snum))
+            d.free()
+
+        def counts_route():
+            _hip.check(lib.impdar_apres_decode_dev(ctx, cptr, 0, total, 1., d_volts.ptr), 'impdar_apres_decode_dev')
+
+        host_ms, counts_ms = aspread(host_route), aspread(counts_route)
+        kernel = []
+        for _ in range(6):                                   # the counts in one piece: the kernel stands alone between its events
+            _hip.check(lib.impdar_apres_decode_pieces_dev(ctx, cptr, 0, total, 1., d_volts.ptr, total), 'impdar_apres_decode_pieces_dev')
+            ms = ctypes.c_float()
+            _hip.check(lib.impdar_ctx_last_kernel_ms(ctx, ctypes.byref(ms)), 'impdar_ctx_last_kernel_ms')
+            kernel.append(ms.value)
+        kernel = sorted(kernel[1:])
+        kernel_ms = {"min": kernel[0], "median": kernel[len(kernel) // 2], "max": kernel[-1]}
+        d_volts.free()
+        copy_decode = ap_copy(total * 10)
+        folder = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
+        try:
+            per = cnum * snum
+            fns = [io_ref.write_dat(os.path.join(folder, 'b%02d.DAT' % b),
+                                    [io_ref.burst_bytes(counts[b * per:(b + 1) * per], nsub=cnum, natt=1, snum=snum)]) for b in range(bnum)]
+
+            def flow(drop_counts):
+                t0 = time.perf_counter()
+                acq = la.load_apres(fns)
+                if drop_counts:
+                    acq.data = acq.data                    # the float64 chirps on the host, as the reference holds them
+                apm.chain(acq, p, max_range)
+                return (time.perf_counter() - t0) * 1e3
+            flow(False)
+            flow_ms = {"counts": sorted(flow(False) for _ in range(3)), "float64": sorted(flow(True) for _ in range(3))}
+        finally:
+            shutil.rmtree(folder)
+        print(json.dumps({"path": "apres load %d x %d x %d uint16" % (bnum, cnum, snum),
+                          "config": "%d MB of counts to %d MB of resident float64 chirps" % ((total * 2) >> 20, (total * 8) >> 20),
+                          "host_decode_upload_ms": host_ms, "counts_upload_device_decode_ms": counts_ms,
+                          "device_ms": kernel_ms["median"], "device_ms_spread": kernel_ms,
+                          "algorithmic_bytes": total * 10, "copy_same_bytes_ms": copy_decode,
+                          "kernel_events_over_copy_host_clock": kernel_ms["median"] / copy_decode["median"],
+                          "files_to_stacked_profile_ms": flow_ms,
+                          "roofline": {"bound": "hbm", "achieved": total * 10 / kernel_ms["median"] / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                       "frac": hbm(total * 10, kernel_ms["median"]),
+                                       "note": "the kernel alone from events on the stream, the counts uploaded in one piece; the copy of equal bytes on the "
+                                               "host clock around its allocation, launch and synchronise, as on the other lines: not like for like, the "
+                                               "quotient flatters the kernel; the two "
+                                               "routes per call on the host clock around a device synchronise, the counts route in "
+                                               "8 MiB pieces through two pinned slots; files on a tmpfs path where there is one"}}),
+              flush=True)
+
     if 'autopick' not in args.skip:
         # layer picking on the resident radargram: 16 seeds walked over every trace (a chain of dependent steps per
         # seed and direction), then the two trace-parallel readers, the guided pick and the continuity index

@@ -130,6 +130,9 @@ SIGNATURES = {
     'impdar_apres_stack_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'impdar_apres_phase_diff': (_i, [_p, _dp, _dp, _i, _i, _i, _dp]),
     'impdar_apres_phase_diff_dev': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'impdar_apres_decode': (_i, [_p, _p, _i, C.c_longlong, _d, _dp]),
+    'impdar_apres_decode_dev': (_i, [_p, _p, _i, C.c_longlong, _d, _p]),
+    'impdar_apres_decode_pieces_dev': (_i, [_p, _p, _i, C.c_longlong, _d, _p, C.c_longlong]),
     'impdar_auto_pick': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_auto_pick_dev': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_pick_guided': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _dp, _ip]),

@@ -12,7 +12,9 @@ thousand elements: they are NumPy / SciPy on the host, the reference's expressio
 exception types and quirks.  :func:`single_processing` and :func:`time_diff_processing` are the reference's two
 full flows.
 
-All data is float64 / complex128, as in the reference.  Loaders and savers are not here.
+All data is float64 / complex128, as in the reference.  Loaders and savers are not here: they are
+``impdar_amd/lib/ApresData``, whose raw acquisitions keep the instrument's counts so that :func:`chain` can upload
+those (:func:`decode_dev`) instead of float64 chirps.
 
 Reference: ``src/impdar/lib/ApresData/_ApresDataProcessing.py:24-222``,
 ``src/impdar/lib/ApresData/_TimeDiffProcessing.py:57-247``, ``src/impdar/bin/apdar.py:337-354``.
@@ -265,6 +267,71 @@ def phase_diff_host(s1, s2, win, step):
     return co
 
 
+# ------------------------------------------------------------------------------------------------ counts to volts
+_COUNT_KINDS = {np.dtype('<u2'): 0, np.dtype('<u4'): 1}
+
+
+def _counts(counts):
+    """``(flat C-contiguous array, kind)`` of an instrument's counts: little-endian uint16 or uint32."""
+    counts = np.asarray(counts)
+    if counts.dtype not in _COUNT_KINDS:
+        raise TypeError('counts are little-endian uint16 or uint32, got %s' % counts.dtype)
+    return np.ascontiguousarray(counts).reshape(-1), _COUNT_KINDS[counts.dtype]
+
+
+def decode_host(counts, divisor=1.):
+    """``counts.astype(float) * 2.5 / 2**16.`` (``/ divisor`` unless that is 1) of uint16 or uint32 counts, computed
+    on the device from the counts as they are (reference ``load_apres.py:391-395``): float64 of the counts' shape,
+    bit for bit NumPy's."""
+    flat, kind = _counts(counts)
+    out = np.empty(flat.shape, dtype=np.float64)
+    rc = _hip.load().impdar_apres_decode(_hip.context(), flat.ctypes.data_as(C.c_void_p), kind, flat.size, float(divisor),
+                                        _hip.as_dp(out)[1])
+    _hip.check(rc, 'impdar_apres_decode')
+    return out.reshape(np.shape(counts))
+
+
+def decode_dev(counts, divisor=1., shape=None, ctx=None, piece=0):
+    """New resident float64 array of ``shape`` (default: ``(1, counts.size)`` for flat counts, else the counts' shape
+    folded to two axes) with the volts of host ``counts``: what :func:`range_dev` reads, without the float64 chirps
+    ever existing on the host.  ``piece`` counts go up at a time (0: the library's choice, 8 MiB of them); the result
+    does not depend on it."""
+    flat, kind = _counts(counts)
+    if shape is None:
+        last = np.shape(counts)[-1] if np.ndim(counts) else 1
+        shape = (flat.size // last if last else 0, last)
+    if int(np.prod(shape)) != flat.size:
+        raise ValueError('%d counts do not fill %s' % (flat.size, (shape,)))
+    with _hip.new_device_array(ctx or _hip.context(), shape, np.float64) as d_out:
+        rc = _hip.load().impdar_apres_decode_pieces_dev(d_out.ctx, flat.ctypes.data_as(C.c_void_p), kind, flat.size,
+                                                       float(divisor), d_out.ptr, int(piece))
+        _hip.check(rc, 'impdar_apres_decode')
+    return d_out
+
+
+def raw_counts(dat):
+    """``(counts, divisor)`` of an acquisition that still holds the instrument's counts in place of float64 chirps
+    (``lib.ApresData.ApresData`` after ``load_apres`` of ``.DAT`` files), shaped (bnum, cnum, snum); else None."""
+    get = getattr(dat, 'raw_counts', None)
+    held = get() if callable(get) else None
+    if held is not None:
+        shape = (int(dat.bnum), int(dat.cnum), int(dat.snum))
+        if held[0].shape != shape:
+            raise ValueError('counts are %s, not (bnum, cnum, snum) = %s' % (held[0].shape, shape))
+    return held
+
+
+def range_counts(counts, divisor, t, chunk=0):
+    """:func:`range_host` of the chirps that ``counts`` decode to: the counts go up and are widened in HBM."""
+    held = [decode_dev(counts, divisor, shape=(counts.size // t.snum, t.snum))]
+    try:
+        held.extend(range_dev(held[0], t, chunk))
+        return tuple(_to_host(d) for d in held[1:])
+    finally:
+        for d in held:
+            d.free()
+
+
 # ------------------------------------------------------------------------------------------------ resident
 def range_dev(d_raw, t, chunk=0):
     """Three new resident arrays ``(spec, data, Rfine)`` of resident (rows, snum) float64 chirps."""
@@ -355,7 +422,11 @@ def apres_range(dat, p, max_range=4000, winfun='blackman'):
     """Range conversion (reference :24-123): leaves ``data``, ``spec``, ``Rcoarse``, ``Rfine``, ``phiref``, ``snum``,
     ``data_dtype`` and ``flags.range``."""
     t = range_tables(dat, p, max_range, winfun)
-    _set_range(dat, t, *range_host(raw_rows(dat), t))
+    held = raw_counts(dat)
+    if held is not None:
+        _set_range(dat, t, *range_counts(held[0], held[1], t))
+    else:
+        _set_range(dat, t, *range_host(raw_rows(dat), t))
 
 
 def stacking(dat, num_chirps=None):
@@ -472,16 +543,25 @@ def bed_pick(diff, sample_threshold=50, coherence_threshold=0.9, filt_kernel=201
     diff.bed = np.array([bed_samp, bed_range, bed_coherence, bed_power])
 
 
-def chain(dat, p, max_range=4000, winfun='blackman', num_chirps=None):
+def chain(dat, p, max_range=4000, winfun='blackman', num_chirps=None, d_raw=None):
     """Range conversion then stacking with the converted data resident in HBM in between: the raw chirps go up once.
-    Leaves what the two calls leave, bit for bit."""
+    Leaves what the two calls leave, bit for bit.  With ``d_raw``, a resident (bnum cnum, snum) float64 array of the
+    chirps (:func:`decode_dev`), nothing is uploaded and ``dat.data`` is not read; the array stays the caller's."""
     t = range_tables(dat, p, max_range, winfun)
-    raw = raw_rows(dat)
     ctx = _hip.context()
     held = []
     try:
-        held.append(_hip.DeviceArray.from_host(ctx, raw))
-        products = range_dev(held[0], t)
+        if d_raw is None:
+            counts = raw_counts(dat)
+            if counts is not None:
+                held.append(decode_dev(counts[0], counts[1], shape=(int(dat.bnum) * int(dat.cnum), int(dat.snum)), ctx=ctx))
+            else:
+                held.append(_hip.DeviceArray.from_host(ctx, raw_rows(dat)))
+            d_raw = held[0]
+        elif d_raw.dtype != np.float64 or d_raw.shape != (int(dat.bnum) * int(dat.cnum), int(dat.snum)):
+            raise ValueError('d_raw is %s %s, not float64 (bnum cnum, snum) = %s'
+                             % (d_raw.dtype, d_raw.shape, (int(dat.bnum) * int(dat.cnum), int(dat.snum))))
+        products = range_dev(d_raw, t)
         held.extend(products)
         _set_range(dat, t, *[_to_host(d) for d in products])
         num_chirps, groups, m, per_burst = stack_plan(int(dat.bnum), int(dat.cnum), num_chirps)

@@ -134,7 +134,7 @@ extern "C" int impdar_ctx_last_ms(impdar_ctx *ctx, float *ms)
 extern "C" int impdar_ctx_last_kernel_ms(impdar_ctx *ctx, float *ms)
 {
     IMPDAR_ARG_CHECK(ctx && ms, "null context/pointer");
-    IMPDAR_ARG_CHECK(ctx->ktimed, "the last timed call on this context bracketed no kernel (only impdar_phaseshift[_dev] does)");
+    IMPDAR_ARG_CHECK(ctx->ktimed, "the last timed call on this context bracketed no kernel (impdar_phaseshift[_dev] and impdar_apres_decode[_dev] do)");
     IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
     IMPDAR_HIP_CHECK(hipEventSynchronize(ctx->ev_ktoc));
     IMPDAR_HIP_CHECK(hipEventElapsedTime(ms, ctx->ev_ktic, ctx->ev_ktoc));

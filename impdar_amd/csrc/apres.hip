@@ -24,6 +24,9 @@
 //       running differences); 0 / 0 is NaN in both parts.  ap_phase_diff_thread_kernel gives a window to a thread
 //       (neighbouring threads read windows `step` samples apart: the same cache lines) up to AP_PD_THREAD_MAX
 //       terms, ap_phase_diff_wave_kernel gives it to a wavefront above that.
+//   * decode (load_apres.py:391-395): ap_decode_kernel, a burst's uint16 / uint32 counts to float64 volts, bit for bit
+//       NumPy's expression; the counts go up as they are, in pieces, the kernel of one piece under the copy of the
+//       next (impdar_apres_decode_dev at the end of this file).
 //
 // Everything is float64 / complex128 (interleaved (re, im) doubles), row-major.  Compiled with -ffp-contract=off.
 #include <algorithm>
@@ -37,6 +40,8 @@
 #define AP_PD_THREAD_MAX 64                         // terms of a window that one thread still sums alone
 #define AP_SCRATCH_BYTES ((size_t)256 << 20)        // padded rows + spectra of one chunk, the library's choice of chunk
 #define AP_MAX_PLANS 4
+#define AP_DEC_VEC 8                                // counts per thread in the body of the decode
+#define AP_DEC_PIECE_BYTES ((size_t)8 << 20)        // counts of one upload piece, the library's choice
 
 __global__ __launch_bounds__(AP_BLOCK) void ar_prep_kernel(const double *__restrict__ raw, const double *__restrict__ win,
                                                            double *__restrict__ pad, int snum, int N)
@@ -144,6 +149,46 @@ __global__ __launch_bounds__(AP_BLOCK) void ap_phase_diff_wave_kernel(const doub
     if (lane == 0) co[i] = ap_quotient(s);
 }
 
+// The instrument's counts as volts: (double)c * 2.5 / 65536., then / divisor where the burst is a sum of chirps -- NumPy's
+// `counts.astype(float) * 2.5 / 2**16.` and `/= n` (load_apres.py:391-395), operation for operation.  c 2.5 is exact (c has at
+// most 32 bits, 2.5 two), / 65536 moves the exponent, and the last division is IEEE's, correctly rounded here as there.
+template <typename T> __device__ __forceinline__ double ap_volts(T c, double divisor, int divide)
+{
+    const double v = (double)c * 2.5 / 65536.0;
+    return divide ? v / divisor : v;
+}
+
+// One flat run of n counts.  `head` < 8 elements bring in + head to a 16-byte and out + head to a 64-byte boundary (the
+// caller places the counts so that both hold at once); from there a thread takes AP_DEC_VEC counts in one (uint16) or
+// two (uint32) 16-byte loads and writes them as four 16-byte stores.  The first block also does the head and the
+// (n - head) % 8 elements of the tail, one element per thread.
+template <typename T>
+__global__ __launch_bounds__(AP_BLOCK) void ap_decode_kernel(const T *__restrict__ in, double *__restrict__ out, size_t n,
+                                                             unsigned head, double divisor, int divide)
+{
+    const size_t body = (n - head) / AP_DEC_VEC;
+    const size_t v = (size_t)blockIdx.x * AP_BLOCK + threadIdx.x;
+    if (v < body) {
+        union {
+            uint4 q[sizeof(T) * AP_DEC_VEC / 16];
+            T c[AP_DEC_VEC];
+        } u;
+        const T(&c)[AP_DEC_VEC] = u.c;
+        const uint4 *src = reinterpret_cast<const uint4 *>(in + head + v * AP_DEC_VEC);
+#pragma unroll
+        for (unsigned q = 0; q < sizeof(u.q) / 16; ++q) u.q[q] = src[q];
+        double2 *dst = reinterpret_cast<double2 *>(out + head + v * AP_DEC_VEC);
+#pragma unroll
+        for (int j = 0; j < AP_DEC_VEC / 2; ++j)
+            dst[j] = make_double2(ap_volts(c[2 * j], divisor, divide), ap_volts(c[2 * j + 1], divisor, divide));
+    }
+    if (blockIdx.x == 0 && threadIdx.x < AP_DEC_VEC) {
+        const size_t t = threadIdx.x, tail = head + body * AP_DEC_VEC + t;
+        if (t < head) out[t] = ap_volts(in[t], divisor, divide);
+        if (tail < n) out[tail] = ap_volts(in[tail], divisor, divide);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 struct ApPlan {
@@ -156,6 +201,8 @@ struct ApBufs {
     std::vector<std::unique_ptr<ApPlan>> plans;    // real-to-complex plans per (N, batch), oldest first
     std::vector<hipEvent_t> ev;                    // stage boundaries of the last range conversion (impdar_apres_range_last_ms)
     size_t ev_used = 0;
+    DevBuf cnt;                                    // the decode's two slots of counts
+    hipEvent_t dec_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // slot s uploaded: s, decoded: 2 + s; a call's start: 4
     void release()
     {
         for (DevBuf &b : in) b.release();
@@ -167,6 +214,11 @@ struct ApBufs {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         ev.clear();
         ev_used = 0;
+        cnt.release();
+        for (hipEvent_t &e : dec_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
     }
 };
 static StepScratch<ApBufs> g_ap;
@@ -405,4 +457,111 @@ extern "C" int impdar_apres_phase_diff(impdar_ctx *ctx, const double *s1, const 
     rc = impdar_apres_phase_diff_dev(ctx, g_ap.in[0].as<double>(), g_ap.in[1].as<double>(), len, win, step, g_ap.out[0].as<double>());
     if (rc) return rc;
     return impdar_download(ctx, co, g_ap.out[0].p, nwin * 16, ctx->stream);
+}
+
+// ---- the instrument's counts to volts ----------------------------------------------------------------------------
+
+static int decode_check(impdar_ctx *ctx, const void *counts, int kind, long long n, double divisor, const void *volts)
+{
+    IMPDAR_ARG_CHECK(ctx, "impdar_apres_decode: null context");
+    IMPDAR_ARG_CHECK(n >= 0 && n <= (1LL << 36), "impdar_apres_decode: %lld counts", n);
+    IMPDAR_ARG_CHECK(kind == 0 || kind == 1, "impdar_apres_decode: kind %d (0: uint16, 1: uint32)", kind);
+    IMPDAR_ARG_CHECK(divisor > 0.0 && divisor <= 1.7976931348623157e308, "impdar_apres_decode: divisor %g", divisor);
+    IMPDAR_ARG_CHECK(n == 0 || (counts && volts), "impdar_apres_decode: null argument");
+    return IMPDAR_OK;
+}
+
+// Piece i of the counts: host memcpy into slot i % 2 of the context's pinned staging buffer (the counts sit at any
+// byte offset of a file's image), a copy on the producer stream to slot i % 2 of g_ap.cnt, the kernel on the compute
+// stream after it: the kernel of piece i runs under the copy of piece i + 1.  Inside its slot a piece starts as many
+// elements past a 16-byte boundary as its first output element lies past a 64-byte one.
+static int decode_pieces(impdar_ctx *ctx, const char *counts, char *stage, size_t el, size_t total, size_t piece, size_t slot,
+                         double divisor, double *d_volts)
+{
+    const int divide = divisor != 1.0;
+    int rk = IMPDAR_OK;
+    size_t i = 0;
+    for (size_t off = 0; off < total; off += piece, ++i) {
+        const size_t now = std::min(piece, total - off), s = i & 1;
+        double *out = d_volts + off;
+        const size_t phase = ((uintptr_t)out / 8) % AP_DEC_VEC;
+        const unsigned head = (unsigned)std::min<size_t>((AP_DEC_VEC - phase) % AP_DEC_VEC, now);
+        char *d_in = g_ap.cnt.as<char>() + s * slot + phase * el;
+        const char *src = counts + off * el;
+        if (i >= 2) {
+            IMPDAR_HIP_CHECK(hipEventSynchronize(g_ap.dec_ev[s]));                       // the pinned slot has gone up
+            IMPDAR_HIP_CHECK(hipStreamWaitEvent(ctx->aux, g_ap.dec_ev[2 + s], 0));       // the device slot has been read
+        }
+        if (stage) {
+            memcpy(stage + s * slot, src, now * el);
+            src = stage + s * slot;
+        }
+        IMPDAR_HIP_CHECK(hipMemcpyAsync(d_in, src, now * el, hipMemcpyHostToDevice, ctx->aux));
+        IMPDAR_HIP_CHECK(hipEventRecord(g_ap.dec_ev[s], ctx->aux));
+        IMPDAR_HIP_CHECK(hipStreamWaitEvent(ctx->stream, g_ap.dec_ev[s], 0));
+        const dim3 grid = ap_grid(std::max<size_t>((now - head) / AP_DEC_VEC, 1));
+        if (i == 0 && (rk = impdar_ctx_ktic(ctx))) return rk;    // first kernel's start to last kernel's end: impdar_ctx_last_kernel_ms
+        if (el == 4)
+            hipLaunchKernelGGL(ap_decode_kernel<uint32_t>, grid, dim3(AP_BLOCK), 0, ctx->stream, (const uint32_t *)d_in, out, now, head,
+                               divisor, divide);
+        else
+            hipLaunchKernelGGL(ap_decode_kernel<uint16_t>, grid, dim3(AP_BLOCK), 0, ctx->stream, (const uint16_t *)d_in, out, now, head,
+                               divisor, divide);
+        IMPDAR_HIP_CHECK(hipGetLastError());
+        IMPDAR_HIP_CHECK(hipEventRecord(g_ap.dec_ev[2 + s], ctx->stream));
+    }
+    return impdar_ctx_ktoc(ctx);
+}
+
+// `piece` counts go up at a time, 0 for AP_DEC_PIECE_BYTES of them (the argument is for tests and for timing the kernel alone)
+extern "C" int impdar_apres_decode_pieces_dev(impdar_ctx *ctx, const void *counts, int kind, long long n, double divisor,
+                                              void *d_volts, long long piece_counts)
+{
+    const auto lock = g_ap.lock();
+    const int rc = decode_check(ctx, counts, kind, n, divisor, d_volts);
+    if (rc) return rc;
+    IMPDAR_ARG_CHECK(((uintptr_t)d_volts & 7) == 0, "impdar_apres_decode: the output is not aligned to 8 bytes");
+    IMPDAR_ARG_CHECK(piece_counts >= 0, "impdar_apres_decode: pieces of %lld counts", piece_counts);
+    if (n == 0) return IMPDAR_OK;
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_ap.bind(ctx);
+    const size_t el = kind ? 4 : 2, total = (size_t)n;
+    size_t piece = piece_counts ? (size_t)piece_counts : AP_DEC_PIECE_BYTES / el;
+    piece = std::min(piece, total);
+    piece = (piece + AP_DEC_VEC - 1) / AP_DEC_VEC * AP_DEC_VEC;          // every piece starts at the same phase of the output
+    const size_t slot = ((piece + AP_DEC_VEC) * el + 255) & ~(size_t)255;
+    IMPDAR_HIP_CHECK(g_ap.cnt.ensure(2 * slot));
+    for (hipEvent_t &e : g_ap.dec_ev)
+        if (!e) IMPDAR_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    std::lock_guard<std::mutex> pin(ctx->pinned_mu);
+    char *stage = reinterpret_cast<char *>(impdar_ctx_pinned(ctx, 2 * slot));   // (null: straight from the caller's memory)
+    // an earlier call's kernels may still read the slots
+    IMPDAR_HIP_CHECK(hipEventRecord(g_ap.dec_ev[4], ctx->stream));
+    IMPDAR_HIP_CHECK(hipStreamWaitEvent(ctx->aux, g_ap.dec_ev[4], 0));
+    const int rp = decode_pieces(ctx, reinterpret_cast<const char *>(counts), stage, el, total, piece, slot, divisor,
+                                 reinterpret_cast<double *>(d_volts));
+    // Whatever became of the pieces, their copies leave the pinned slots and the caller's counts before pinned_mu is
+    // released and this call returns: another call may overwrite or free that buffer.
+    const hipError_t drained = hipStreamSynchronize(ctx->aux);
+    if (rp) return rp;
+    IMPDAR_HIP_CHECK(drained);
+    return impdar_ctx_mark_produced(ctx);
+}
+
+extern "C" int impdar_apres_decode_dev(impdar_ctx *ctx, const void *counts, int kind, long long n, double divisor, void *d_volts)
+{
+    return impdar_apres_decode_pieces_dev(ctx, counts, kind, n, divisor, d_volts, 0);
+}
+
+extern "C" int impdar_apres_decode(impdar_ctx *ctx, const void *counts, int kind, long long n, double divisor, double *volts)
+{
+    const int rc = decode_check(ctx, counts, kind, n, divisor, volts);
+    if (rc || n == 0) return rc;
+    const auto held = g_ap.lock();
+    IMPDAR_HIP_CHECK(hipSetDevice(ctx->device));
+    g_ap.bind(ctx);
+    IMPDAR_HIP_CHECK(g_ap.out[0].ensure((size_t)n * 8));
+    const int rd = impdar_apres_decode_dev(ctx, counts, kind, n, divisor, g_ap.out[0].p);
+    if (rd) return rd;
+    return impdar_download(ctx, volts, g_ap.out[0].p, (size_t)n * 8, ctx->stream);
 }

@@ -68,7 +68,8 @@ int impdar_ctx_sync(impdar_ctx *ctx);
  * impdar_phaseshift[_dev] call on this context; blocks until they have completed */
 int impdar_ctx_last_ms(impdar_ctx *ctx, float *ms);
 /* ... and of the frequency-sum kernels alone (the rotate-accumulate work of mig_python.py:396-487, without the
- * transforms and transposes around it) of the last impdar_phaseshift[_dev] call */
+ * transforms and transposes around it) of the last impdar_phaseshift[_dev] call; after impdar_apres_decode[_dev] the
+ * time from its first kernel's start to its last kernel's end */
 int impdar_ctx_last_kernel_ms(impdar_ctx *ctx, float *ms);
 /* One JSON object about the last migration entry point that ran on this context (impdar_kirchhoff, impdar_stolt,
  * impdar_phaseshift[_ffd], impdar_taper): {"entry", "kernel" (the kernel that did the sums), "device", "kernel_ms",
@@ -620,6 +621,36 @@ int impdar_apres_stack_dev(impdar_ctx *ctx, const double *d_data, int is_complex
 int impdar_apres_phase_diff(impdar_ctx *ctx, const double *s1, const double *s2, int len, int win, int step, double *co);
 int impdar_apres_phase_diff_dev(impdar_ctx *ctx, const double *d_s1, const double *d_s2, int len, int win, int step,
                                 double *d_co);
+
+/* ---- an ApRES burst's counts to volts (csrc/apres.hip) ----
+ * load_apres.py:391-395: volts[i] = (double)counts[i] * 2.5 / 65536., then
+ * / divisor unless divisor == 1 (the reference's n_subbursts n_attenuators of
+ * an averaged burst).  counts: `n` little-endian elements in HOST memory at
+ * any byte offset (a file's image as it was read), uint16 (kind 0) or uint32
+ * (kind 1, Average=2).  One flat run: rows do not matter.  Bit for bit NumPy's
+ * expression: the product is exact, / 65536 moves the exponent, the last
+ * division is IEEE's, and nothing is a reciprocal product.
+ * The counts go up as they are, 2 (4) bytes per sample, in pieces through two
+ * slots of the context's pinned staging buffer; the kernel of one piece runs
+ * under the copy of the next.  impdar_apres_decode writes host memory and
+ * waits; impdar_apres_decode_dev writes `n` doubles of an 8-byte aligned
+ * device array -- the (rows, snum) chirps impdar_apres_range_dev reads -- and
+ * returns once the counts have left the host (the last kernels still run on
+ * the compute stream).  impdar_ctx_last_kernel_ms after either gives the time
+ * from the first kernel's start to the last one's end: the kernel alone when
+ * the counts went up in one piece.
+ * n < 0, another kind, a null pointer with n > 0, a divisor that is not
+ * finite and positive are IMPDAR_ERR_ARG before any device work; n == 0
+ * succeeds and touches nothing.  Not here: Average=1 (the reference cannot read
+ * it either), formats 2-4 of the burst header.
+ * impdar_apres_decode_pieces_dev: impdar_apres_decode_dev with `piece_counts`
+ * counts going up at a time (rounded up to a multiple of 8), 0 for the
+ * library's choice, 8 MiB of counts: for tests, and for timing the kernel
+ * alone.  The result does not depend on it. */
+int impdar_apres_decode(impdar_ctx *ctx, const void *counts_host, int kind, long long n, double divisor, double *volts_host);
+int impdar_apres_decode_dev(impdar_ctx *ctx, const void *counts_host, int kind, long long n, double divisor, void *d_volts);
+int impdar_apres_decode_pieces_dev(impdar_ctx *ctx, const void *counts_host, int kind, long long n, double divisor,
+                                   void *d_volts, long long piece_counts);
 
 /* ---- what a plot reads from the radargram (csrc/display.hip) ----
  * data: (snum, tnum) float32 / float64, row-major; a window is rows [y0, y1),
