@@ -60,7 +60,13 @@ static inline void impdar_ctx_note(impdar_ctx *ctx, const char *entry, const cha
     ctx->m_extra[0] = 0;
 }
 
-// the staging ring of impdar_download_blocks_f64
+// The staging buffer of a download (download.hip) is a RING of at most 64 MB, not the whole image: pinning costs 0.22 ms
+// per MB -- the 164 MB of a config-3 Kirchhoff image, the 268 MB of an 8192^2 float32 one (59 ms) were the largest term of
+// a process's first call.  Pieces of <= 16 MB go round it, up to four DMAs in flight: the copy of a piece is enqueued as
+// soon as the host threads have copied (or widened) the piece that held its room out of the ring.
+// (same-box A/B of the steady call at config 3, ring 32 / 64 / 96 / 128 MB / whole image: 16.4 / 13.2 / 12.9 / 13.0 / 13.0 ms;
+// the first call of a process: 52 ms with 64 MB, 66 ms with 96 MB -- more than the call can pin behind its plan
+// before the first block is ready to leave.  64 MB.)
 constexpr size_t IMPDAR_STAGE_RING_BYTES = (size_t)64 << 20;
 // start allocating a pinned staging buffer of `bytes` unless the context has one (impdar_ctx_pinned adopts it)
 void impdar_ctx_pinned_prefetch(impdar_ctx *ctx, size_t bytes);
@@ -74,18 +80,15 @@ int impdar_ctx_ktoc(impdar_ctx *ctx);
 // record "everything enqueued on ctx->stream so far produces data a later call may read" (see impdar_kirch_prep)
 int impdar_ctx_mark_produced(impdar_ctx *ctx);
 
-// grow-only pinned staging buffer of the context; nullptr when the allocation fails (callers fall back to a
-// direct pageable copy)
+// grow-only pinned staging buffer of the context; nullptr when the allocation fails (callers fall back to pageable
+// memory).  Callers hold ctx->pinned_mu.
 void *impdar_ctx_pinned(impdar_ctx *ctx, size_t bytes);
-// copy (or convert float -> double) `n` elements from pinned staging into pageable memory on a few threads
-void impdar_host_copy_f64(double *dst, const void *src, size_t n, bool src_is_f32);
-// device -> host through the pinned staging buffer and a threaded copy (falls back to a plain D2H); synchronises `st`
+// the context is going away: its staging buffer, and one on its way, are freed
+void impdar_ctx_pinned_release(impdar_ctx *ctx);
+// device -> host through the staging ring and a threaded copy (below 1 MiB: a plain D2H); synchronises `st`
 int impdar_download(impdar_ctx *ctx, void *host_dst, const void *dev_src, size_t bytes, hipStream_t st);
-// a (rows x width) device block of `dtype` into columns [col0, col0 + width) of a (rows x ld) float64 host array, on `st`
-int impdar_download_block_f64(impdar_ctx *ctx, double *dst_host, size_t ld, size_t col0, const void *src_dev, int dtype,
-                              size_t rows, size_t width, hipStream_t st);
-
 // several output-trace blocks of one image, each after its own event, copies and host widening pipelined across blocks
+// (one block with width == ld: a flat array)
 int impdar_download_blocks_f64(impdar_ctx *ctx, double *dst_host, size_t ld, size_t rows, int dtype, int nblk,
                                const size_t *col0, const size_t *width, const void *const *src, const hipEvent_t *after,
                                hipStream_t st);
@@ -192,8 +195,8 @@ template <int N> static int impdar_upload_tables(impdar_ctx *ctx, DevBuf &buf, c
     return IMPDAR_OK;
 }
 
-// What a processing step (preproc.hip, hfilt.hip, denoise.hip, hpass.hip, vaxis.hip, gain.hip, taxis.hip) keeps
-// between calls: its buffers -- `Bufs`, with a release() that frees every one of them -- and the context they
+// What a unit of processing steps (preproc.hip, hfilt.hip, denoise.hip, hpass.hip, vaxis.hip, gain.hip, taxis.hip,
+// quadpol.hip, apres.hip, pick.hip, spectrum.hip, display.hip) keeps between calls: its buffers -- `Bufs`, with a release() that frees every one of them -- and the context they
 // belong to.  One set per process and step: entry points of different contexts / threads take turns, each holding
 // lock() from its argument check to its return (re-entrant because the host-buffer forms call the resident ones).
 template <class Bufs> struct StepScratch : Bufs {
