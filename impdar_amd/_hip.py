@@ -60,6 +60,8 @@ SIGNATURES = {
     'impdar_kirch_plan_xnoise': (_d, [_p]),
     'impdar_kirch_plan_kernel': (_i, [_p]),
     'impdar_kirch_queue_policy': (_i, [_i, _i]),
+    'impdar_kirch_window_policy': (_i, [_i]),
+    'impdar_kirch_plan_window': (_i, [_p]),
     'impdar_kirch_prep': (_i, [_p, _p, _i, _i, _i]),
     'impdar_kirch_allgather': (_i, [_p]),
     'impdar_kirch_exchange': (_i, [_p, _i, _ip, _ip, _ip, _i, _ip, _ip, _ip]),
@@ -236,6 +238,9 @@ def apply_queue_policy():
     order = {'chunk': 1, 'packed': 2}.get(os.environ.get('IMPDAR_KIRCH_ORDER', ''), 0)
     gang = {'1': 1, '2': 2, '4': 4}.get(os.environ.get('IMPDAR_KIRCH_G', ''), 0)
     check(load().impdar_kirch_queue_policy(order, gang), 'impdar_kirch_queue_policy')
+    # ... and $IMPDAR_KIRCH_WINDOW (slide | quad), the output window of the float32 ring kernel's tiles
+    window = {'slide': 1, 'quad': 2}.get(os.environ.get('IMPDAR_KIRCH_WINDOW', ''), 0)
+    check(load().impdar_kirch_window_policy(window), 'impdar_kirch_window_policy')
 
 
 def device_count():

@@ -220,8 +220,9 @@ extern "C" int impdar_kirchhoff(impdar_ctx *ctx, const void *data, int dtype, in
     // IMPDAR_KIRCH_EXACT_IMPL=pair, holds 1e-12 on any profile)
     const bool offset_weighted = kern == IMPDAR_KERNEL_DQUAD || kern == IMPDAR_KERNEL_EXACT_TAB;
     snprintf(ctx->m_extra, sizeof ctx->m_extra,
-             "\"plan\": \"%s\", \"launches\": %d, \"plan_ms\": %.3f, \"call_ms\": %.3f, \"xnoise\": %.3g, \"parity_bar\": %.3g",
+             "\"plan\": \"%s\", \"launches\": %d, \"plan_ms\": %.3f, \"call_ms\": %.3f, \"xnoise\": %.3g, \"window\": \"%s\", \"parity_bar\": %.3g",
              hit ? "cached" : "new", nlaunch, ms(t0, t0b), ms(t0, t2), p->xnoise,
+             kern != IMPDAR_KERNEL_QUAD ? "" : (p->window == KIRCH_WINDOW_QUAD ? "quad" : "slide"),
              dtype == IMPDAR_F32 && p->mode == IMPDAR_KIRCH_FAST ? 1e-4 : (offset_weighted ? std::max(1e-12, 0.1 * p->xnoise) : 1e-12));
     rc = done(IMPDAR_OK);
     return rc;

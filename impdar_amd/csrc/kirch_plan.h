@@ -44,6 +44,7 @@ struct impdar_kirch_plan : KirchGeometry, KirchRoute {
     DevBuf d_queue;             // quad kernel, persistent workgroups: per-XCD item counters
     int slots = 0;              // ... and how many of them are resident at once (occupancy query, cached)
     DevBuf d_partial;           // the partial images of the pieces of a walk (walk_parts_log2)
+    DevBuf d_side_l, d_side_r;  // quad-aligned window: the tiles' sums of the columns they share with a neighbour (FastParams::side_l)
     DevBuf d_tilemap;           // ring kernels: (chunk, slot, XCD) -> output tile, balanced over the XCDs
     std::vector<short> h_tilemap;
     int tm_key[5] = {-1, -1, -1, -1, -1};   // (xlo, xhi, tile width, G, tiles_per_xcd) the cached map was built for

@@ -19,6 +19,12 @@ struct FastParams {
     int parts_log2;                // persistent ring kernels: every tile's walk as 1 << parts_log2 queue items (pieces)
     void *partial;                 // ... their partial images [piece][snum][ldo] (element type = image type)
     size_t part_stride;            // ... elements per partial image
+    // quad kernel, quad-aligned window (KIRCH_WINDOW_QUAD): tiles start at x00 + multiples of the tile; what a tile holds of the
+    // three columns left of its own start and of the next tile's -- raw sums [piece][tile][3][snum], sample-major -- goes to
+    // side_l / side_r; kirch_fixup_kernel adds the two.  Null under the sliding window.
+    int x00;
+    float *side_l, *side_r;
+    size_t side_stride;            // ... elements per piece
     int *queue;                    // ring kernels, persistent workgroups: 8 item counters (one per XCD, 64 bytes apart), zeroed
                                    // before the launch; null = one item per block
     const int *items;              // ... and the XCDs' lists of items (chunk << 16 | tile, kirch_gangmap): [0..7] their lengths,
@@ -86,6 +92,10 @@ __host__ __device__ static inline unsigned kq_row_offset(int r, int ps)
 #define KQ_ZERO 1024        // byte offset of the all-zero row (spare row of piece 0, group 0; + g * KQ_GS)
 #ifndef KQ_PER
 #define KQ_PER 4            // quads per interleave slice (1..7 all measure within 2 %; 4 keeps 97 VGPRs)
+#endif
+#ifndef KQ_PER_WIN
+#define KQ_PER_WIN 2        // ... under the quad-aligned window: with slices of 4 the two-tile kernel of 32 traces (128 VGPRs at 4
+                            // waves per SIMD) spills pick rows inside the step loop, and each reload drains the staging DMA
 #endif
 typedef float kq_f4 __attribute__((ext_vector_type(4)));
 typedef unsigned kq_u4 __attribute__((ext_vector_type(4)));
@@ -164,28 +174,12 @@ __device__ __forceinline__ int kirch_ring_sigma(int lane)
 // Plans of 4+ ranks cut every walk into 2 or 4 pieces at fixed offsets (n = 1 and n = 1 -+ U k, U = NB S: whole ring
 // revolutions, the same for every tile of a chunk) -- one walk of a shallow chunk is as long as such a rank's whole step
 // should be.  A piece writes its sums to its own partial image; kirch_combine_kernel adds the pieces in a fixed order.
-template <int S, int NB, int XB, int NH>
+// (The arithmetic is kirch_walk_range's, kirch_route.h: the host-side cover of the quad-aligned window walks by it too.  WX: the
+// 3 further steps of that window, else 0.)
+template <int S, int NB, int XB, int NH, int WX = 0>
 __device__ __forceinline__ bool kirch_ring_walk(const FastParams &P, int hmax, int x0w, int part, int &nlo, int &nhi)
 {
-    int nlo_ = max(-hmax, -(x0w + XB - 1));
-    nlo_ -= (nlo_ - 1) & (S - 1);
-    int nhi_ = min(hmax + (NH - 1) * XB, P.tnum - 1 - x0w);
-    bool empty_part = false;
-    if (P.parts_log2) {
-        // piece boundaries (all = 1 mod S): ..., 1 - U k | 1 - U k .. 0 | 1 .. U k | 1 + U k, ...   (2 pieces: n <= 0 | n >= 1)
-        const int uk = (NB * S) * max(1, (hmax + NB * S) / (2 * NB * S));
-        const int inner = P.parts_log2 == 2 ? uk : (1 << 28);
-        const int side = P.parts_log2 == 2 ? (part >> 1) : part;          // 0: n <= 0, 1: n >= 1
-        const bool far = P.parts_log2 == 2 && ((part & 1) ^ side) == 0;    // pieces 0 and 3 are the outer ones
-        const int lo = side == 0 ? (far ? -(1 << 28) : 1 - inner) : (far ? 1 + inner : 1);
-        const int hi = side == 0 ? (far ? -inner : 0) : (far ? (1 << 28) : inner);
-        nlo_ = max(nlo_, lo);
-        nhi_ = min(nhi_, hi);
-        empty_part = nhi_ < nlo_;
-    }
-    nlo = nlo_;
-    nhi = nhi_;
-    return empty_part;
+    return kirch_walk_range(hmax, x0w, P.tnum, S, NB, XB, NH, P.parts_log2, part, WX, nlo, nhi);
 }
 
 // Raw buffer over an image, based at the group of trace jbase - 1 (the workgroup's first group), as four scalar words
@@ -238,7 +232,7 @@ static int build_tilemap(impdar_kirch_plan *p, FastParams &P, int tile_w, int al
     const size_t n = (size_t)P.nchunks * P.tiles_per_xcd * 8;
     if (memcmp(key, p->tm_key, sizeof(key)) != 0 || p->h_tilemap.size() != n) {
         std::vector<short> map = kirch_tilemap(p->h_hmax, p->tnum, P.xlo, P.xhi, tile_w, align_mask, ring_blocks, step_block, P.G,
-                                               P.tiles_per_xcd, P.nchunks);
+                                               P.tiles_per_xcd, P.nchunks, p->window);
         if (map.empty()) return IMPDAR_OK;
         p->h_tilemap.swap(map);
         memcpy(p->tm_key, key, sizeof(key));
@@ -256,7 +250,7 @@ static int build_gangmap(impdar_kirch_plan *p, FastParams &P, int tile_w, int al
     P.items = nullptr;
     const int key[5] = {P.xlo, P.xhi, tile_w, kirch_gang_size(*p, P.nxt), kirch_queue_order(*p, P.nxt)};
     if (memcmp(key, p->gm_key, sizeof(key)) != 0 || p->h_items.empty()) {
-        const KirchGangMap M = kirch_gangmap(p->h_hmax, p->tnum, P.xlo, P.xhi, tile_w, align_mask, ring_blocks, step_block, key[3], key[4], P.nchunks);
+        const KirchGangMap M = kirch_gangmap(p->h_hmax, p->tnum, P.xlo, P.xhi, tile_w, align_mask, ring_blocks, step_block, key[3], key[4], P.nchunks, p->window);
         if (M.items() == 0) return IMPDAR_OK;
         std::vector<int> flat(16);
         for (int x = 0; x < 8; ++x) {
@@ -333,14 +327,18 @@ static int prep_table_ring(impdar_kirch_plan *p, int b, hipStream_t st, Kernel k
 
 // What launch_ring needs of a ring kernel's instantiation K (RingF32 / RingF64 of the two units): the element type, the kernel
 // in its near-field (one tile per workgroup, one workgroup per CU) and far-field forms, where tiles may start, and the ring
-// as the tile map's cost model sees it.
+// as the tile map's cost model sees it; its window kind and, for KIRCH_WINDOW_QUAD, the launch of the fix-up behind the kernel.
 template <typename K>
 static int launch_ring(impdar_kirch_plan *p, const FastParams &P0, hipStream_t st)
 {
     constexpr int XB = K::XB, NH = K::NH;
     FastParams P = P0;
-    const int ntiles = (P.xhi - (P.xlo & ~K::align_mask) + XB * NH - 1) / (XB * NH);      // workgroup tiles start at a multiple of 8 (4)
+    // workgroup tiles start at a multiple of 8 (4); under the quad-aligned window at multiples of the workgroup tile, and the
+    // tile right of the block's last column is part of the launch (kirch_tile_origin, kirch_tile_count)
+    const int window = K::window;
+    const int ntiles = kirch_tile_count(P.xlo, P.xhi, XB * NH, K::align_mask, window);
     P.nxt = ntiles;
+    P.x00 = kirch_tile_origin(P.xlo, XB * NH, K::align_mask, window);
     // P.G: the groups of the one-item-per-block launch (tile map / arithmetic rule) and the padding of its grid.
     // Groups of 4 adjacent tiles per XCD share staging lines in L2 (same-box A/B at config 3 with 250 tiles of 40: 1.2-1.6 %
     // faster than 1, L2 misses -36 %; 6 / 8 / 12 are slower), but with blocks dealt statically the XCDs only stay balanced
@@ -368,6 +366,21 @@ static int launch_ring(impdar_kirch_plan *p, const FastParams &P0, hipStream_t s
     auto k = K::far_kernel();
     IMPDAR_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     int grid = nblk;
+    if (window == KIRCH_WINDOW_QUAD) {
+        // the side sums of every tile of the launch, per piece of a walk; an empty piece writes none, so they start as zeros
+        const size_t np = (size_t)1 << (NH == 1 ? p->walk_parts_log2 : 0), side = (size_t)ntiles * NH * 3 * P.snum;
+        if (p->d_side_l.ensure(side * np * sizeof(float)) != hipSuccess || p->d_side_r.ensure(side * np * sizeof(float)) != hipSuccess) {
+            impdar_set_error("hipMalloc of the %zu-byte side sums failed", side * np * sizeof(float));
+            return IMPDAR_ERR_HIP;
+        }
+        P.side_l = p->d_side_l.as<float>();
+        P.side_r = p->d_side_r.as<float>();
+        P.side_stride = side;
+        if (np > 1) {
+            IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_side_l.p, 0, side * np * sizeof(float), st));
+            IMPDAR_HIP_CHECK(hipMemsetAsync(p->d_side_r.p, 0, side * np * sizeof(float), st));
+        }
+    }
     if (P.tilemap) {
         // persistent workgroups: as many as are resident at once, each pulling items from the per-XCD queues
         if (p->slots <= 0) {        // resident workgroups of this plan's kernel on this device: asked once
@@ -401,6 +414,9 @@ static int launch_ring(impdar_kirch_plan *p, const FastParams &P0, hipStream_t s
         }
     }
     hipLaunchKernelGGL(k, dim3(grid), dim3(KF_THREADS * NH), shmem, st, P, W);
+    // the columns two tiles share under the quad-aligned window (kirch_fixup_kernel), in front of the sum of the pieces
+    if constexpr (K::window == KIRCH_WINDOW_QUAD)
+        if (ntiles * NH > 1) K::launch_fixup(P, ntiles * NH, st);
     if (P.parts_log2) kirch_launch_combine<typename K::elem>(P, st);      // (a ring's element type is its plan's dtype)
     IMPDAR_HIP_CHECK(hipGetLastError());
     return IMPDAR_OK;
@@ -442,6 +458,9 @@ static FastParams kirch_ring_params(impdar_kirch_plan *p, void *d_out, int xlo, 
     P.tilemap = nullptr;
     P.queue = nullptr;
     P.items = nullptr;
+    P.x00 = 0;
+    P.side_l = P.side_r = nullptr;
+    P.side_stride = 0;
     P.parts_log2 = 0;
     P.partial = nullptr;
     P.part_stride = 0;

@@ -3,6 +3,7 @@
 //                        block as the LDS offset of the picked row.
 //   kirch_quad_kernel    the MI355X hot path.  A workgroup owns 256 output samples x 24-40 output traces; input
 //                        traces stream by LDS-DMA through an LDS ring read with ds_read_b128; picks come from the table.
+//   kirch_fixup_kernel   the columns two tiles of kirch_quad_kernel share under its quad-aligned window.
 //   kirch_table_kernel / kirch_tab_kernel
 //                        same idea with a trace-major ring, ds_read_b32 and an fp32 weight table, for geometries
 //                        whose moveout does not fit the quad ring.
@@ -289,9 +290,26 @@ __global__ __launch_bounds__(KF_THREADS, OCC) void kirch_tab_kernel(FastParams P
 // and window lookups are ordinary loads the compiler counts; their pipeline is deepened to PD blocks so that
 // each is older than everything the block's wait leaves in flight (the compiler then adds no waits of its own,
 // which would drain the younger DMA as well).
-template <int XB, bool NEAR, int OCC, int SH, int NH, int LK>
+//
+// WK = KIRCH_WINDOW_QUAD (far field): the output window moves instead of the read window.  At step pm (offset n, pm + 1 = n
+// mod 8) a tile reads the ALIGNED XB slots from slot pm + 1 - phi, phi = n & 3 -- XB/4 whole quads, none with an unused
+// component -- into the outputs [x0 - phi, x0 - phi + XB): XB + 3 accumulators, accumulator a = output x0 - 3 + a
+// (kq_win_first_quad, kq_win_acc, kirch_route.h).  phi is the same for every tile of a launch (tile starts and XB are multiples
+// of 8, every walk and walk piece starts at 1 mod 8), so at every offset the tiles still partition the output axis.  The
+// XB - 3 columns a tile holds at every phase go to the image; of the three on either side it holds the offsets of some
+// phases only, and those sums go to side_r / side_l for kirch_fixup_kernel.  The walk is 3 steps longer (outputs x0 - 3 ..
+// x0 - 1 at their last offsets; the traces beyond the profile are zero rows).
+// Ring safety of the aligned window: it begins up to 3 slots before the sliding one and ends with it or before.  Step
+// pm0 + 6 of a block reads from slot pm0 + 4, in the group this block's DMA re-fills -- issued behind the barrier that every
+// wave passes after its FMAs of step 6; steps pm0 + 7 .. pm0 + 10 (the first of them in flight across that barrier) read from
+// slot pm0 + 8, step 0 of an item from slot 0, the first trace of the first staged group.  A staged trace is read for up to
+// XB + 2 steps: its staging window covers them (kirch_ring_tables), and the route takes this form only where the ring's
+// rows hold that moveout (kirch_route).
+template <int XB, bool NEAR, int OCC, int SH, int NH, int LK, int WK = KIRCH_WINDOW_SLIDE>
 __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastParams P, int W)
 {
+    static_assert(WK == KIRCH_WINDOW_SLIDE || (WK == KIRCH_WINDOW_QUAD && !NEAR && XB % 8 == 0), "the quad-aligned window is the far field's");
+    constexpr int NA4 = XB / 4 + WK;          // accumulator quads
     constexpr int S = 8;
     constexpr int RG = kq_ring_slots(XB) + 8 * LK;     // ring slots
     constexpr int KQ_PS = kq_piece_bytes_lk(XB, LK);
@@ -299,7 +317,8 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
     static_assert(LK == 0 || LK == 1, "staging lookahead of one or two blocks");
     static_assert(LK == 0 || !NEAR, "the deeper ring is not laid out for the second (near field) image");
     constexpr int G0 = XB / 8;                // a block's new traces belong to image / ring group blk + G0
-    constexpr int KQ_PARTS = (XB / 4 + 1 + KQ_PER - 1) / KQ_PER;   // interleave slices per step
+    constexpr int PER = WK ? KQ_PER_WIN : KQ_PER;            // quads per interleave slice
+    constexpr int KQ_PARTS = (XB / 4 + (WK ? 0 : 1) + PER - 1) / PER;   // interleave slices per step
     constexpr int NB = RG / S;                // step blocks per ring revolution (unroll length)
     constexpr int NQ = RG / 4;                // slot quads
     static_assert(XB + 2 * S - 1 <= RG && RG % S == 0 && XB % 4 == 0, "ring too small");
@@ -324,7 +343,7 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
         return;
     }
     const int s0 = chunk * KF_THREADS;
-    const int x0w = (P.xlo & ~7) + xt * (XB * NH);   // workgroup's first output trace: a multiple of 8 (outputs left of xlo are not stored)
+    const int x0w = (WK ? P.x00 : (P.xlo & ~7)) + xt * (XB * NH);   // workgroup's first output trace: a multiple of 8 (outputs left of xlo are not stored)
     const int x0 = x0w + half * XB;
     const int snum = P.snum;
     const int lane = tid & 63;
@@ -334,7 +353,7 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
 
     const int hmax = P.hmax[chunk];
     int nlo, nhi;                                // tile 0's offsets: the ring clock
-    if (kirch_ring_walk<S, NB, XB, NH>(P, hmax, x0w, part, nlo, nhi)) continue;      // uniform; the partial images are zeroed before the launch
+    if (kirch_ring_walk<S, NB, XB, NH, WK ? KQ_WIN_EXTRA : 0>(P, hmax, x0w, part, nlo, nhi)) continue;      // uniform; the partial images are zeroed before the launch
     const int nsteps = nhi - nlo + 1;
     const int nblocks = (nsteps + S - 1) / S;
     // the main loop always runs whole ring revolutions (NB blocks); steps past the
@@ -408,9 +427,9 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
     for (int j = 0; j < PD; ++j) tkp[j] = picks(1 + j);
 
     // accumulators in quads: the ordering pin below takes them as XB/4 operands of ONE asm statement
-    kq_f4 acc4[XB / 4];
+    kq_f4 acc4[NA4];
 #pragma unroll
-    for (int i = 0; i < XB / 4; ++i) acc4[i] = kq_f4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < NA4; ++i) acc4[i] = kq_f4{0.f, 0.f, 0.f, 0.f};
 #define KQ_ACC(i) acc4[(i) >> 2][(i) & 3]
 
     // ---- staging by LDS-DMA: the 8 traces a block adds (one 8-row group of the image) go straight from
@@ -457,15 +476,18 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
     // ---- the resident ring is read software pipelined: the ds_read_b128 of step s+1 are in flight
     // while the FMAs of step s run (two statically indexed quad buffers), also across block ends
     kq_f4 va[NQ], vb[NQ], ua[NEAR ? NQ : 1], ub[NEAR ? NQ : 1];
-    auto needed = [](int pm, int qd) {
+    // position of quad qd in the step's run of needed quads (they are consecutive, cyclically; the aligned run starts at
+    // the same quad: kq_win_first_quad)
+    auto run_pos = [](int pm, int qd) { return (qd - ((pm + 1) % RG) / 4 + NQ) % NQ; };
+    static_assert(kq_win_first_quad(5, NQ) == 1 && kq_win_first_quad(RG - 1, NQ) == 0 && kq_win_first_quad(RG - 2, NQ) == NQ - 1, "");
+    auto needed = [&](int pm, int qd) {
+        if constexpr (WK) return run_pos(pm, qd) < XB / 4;
         bool any = false;
         for (int c = 0; c < 4; ++c) any = any || ((4 * qd + c - pm - 1 + 2 * RG) % RG) < XB;
         return any;
     };
     // pm = step index mod RG (a compile-time constant after unrolling), tk = the step's table entry =
     // byte offset of half 0 of the picked row; quad qd = ring slots 4 qd .. 4 qd + 3 = half qd & 1 of group qd >> 1
-    // position of quad qd in the step's run of 6-7 needed quads (they are consecutive, cyclically)
-    auto run_pos = [](int pm, int qd) { return (qd - ((pm + 1) % RG) / 4 + NQ) % NQ; };
     // `part` selects a slice of the run (KQ_PARTS slices; -1 = all): reads and FMAs are interleaved slice
     // by slice so that a wave's ds_read_b128 do not arrive at the LDS queue as one burst of 7
     auto load_step = [&](int pm, unsigned tk, kq_f4 (&v)[NQ], kq_f4 (&u)[NEAR ? NQ : 1], int part) {
@@ -475,7 +497,7 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
         const unsigned a0 = tk << SH, a1 = a0 ^ 16u;
 #pragma unroll
         for (int qd = 0; qd < NQ; ++qd)
-            if (needed(pm, qd) && (part < 0 || run_pos(pm, qd) / KQ_PER == part)) {
+            if (needed(pm, qd) && (part < 0 || run_pos(pm, qd) / PER == part)) {
                 // must stay a whole ds_read_b128 also for the partly used quads at the ends of
                 // the window: fma_step marks the unused components as used (empty asm)
                 const unsigned src = ((qd & 1) ? a1 : a0) + (qd >> 1) * KQ_GS;
@@ -486,7 +508,18 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
     auto fma_step = [&](int pm, float w, float w2, const kq_f4 (&v)[NQ], const kq_f4 (&u)[NEAR ? NQ : 1], int part) {
 #pragma unroll
         for (int qd = 0; qd < NQ; ++qd) {
-            if (part >= 0 && run_pos(pm, qd) / KQ_PER != part) continue;
+            if (part >= 0 && run_pos(pm, qd) / PER != part) continue;
+            if constexpr (WK) {
+                // every component of the run's quads feeds an accumulator
+                const int t = run_pos(pm, qd);
+                if (t < XB / 4) {
+                    KQ_ACC(kq_win_acc(pm, t, 0)) = fmaf(w, v[qd].x, KQ_ACC(kq_win_acc(pm, t, 0)));
+                    KQ_ACC(kq_win_acc(pm, t, 1)) = fmaf(w, v[qd].y, KQ_ACC(kq_win_acc(pm, t, 1)));
+                    KQ_ACC(kq_win_acc(pm, t, 2)) = fmaf(w, v[qd].z, KQ_ACC(kq_win_acc(pm, t, 2)));
+                    KQ_ACC(kq_win_acc(pm, t, 3)) = fmaf(w, v[qd].w, KQ_ACC(kq_win_acc(pm, t, 3)));
+                }
+                continue;
+            }
             // outputs served by slots 4qd .. 4qd+3 at this step
             const int i0 = (4 * qd + 0 - pm - 1 + 2 * RG) % RG;
             const int i1 = (4 * qd + 1 - pm - 1 + 2 * RG) % RG;
@@ -531,6 +564,7 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
             asm volatile("" : "+v"(acc4[0]), "+v"(acc4[1]), "+v"(acc4[2]), "+v"(acc4[3]), "+v"(acc4[4]), \
                               "+v"(acc4[5]), "+v"(acc4[XB >= 32 ? 6 : 0]), "+v"(acc4[XB >= 32 ? 7 : 0]),  \
                               "+v"(acc4[XB >= 40 ? 8 : 0]), "+v"(acc4[XB >= 40 ? 9 : 0]) :: "memory");    \
+        if (WK) asm volatile("" : "+v"(acc4[NA4 - 1]) :: "memory");       /* the quad of accumulators XB .. XB + 2 */    \
     } while (0)
 
     float n2c[S];                                  // n^2 of the current block's steps
@@ -614,26 +648,65 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_quad_kernel(FastPa
     if (ti_raw < snum) {
         float *o = (P.parts_log2 ? reinterpret_cast<float *>(P.partial) + (size_t)part * P.part_stride : P.out) +
                    (size_t)ti_raw * P.ldo + (x0 - P.xlo);
+        if constexpr (WK) {
+            // accumulators 3 .. XB - 1 are whole columns; 0 .. 2 (left of x0) and XB .. XB + 2 lack the offsets the neighbour
+            // tile took: raw sums, sample-major (lanes = consecutive samples), for kirch_fixup_kernel
 #pragma unroll
-        for (int i = 0; i < XB; ++i)
-            if (x0 + i >= P.xlo && x0 + i < P.xhi) o[i] = KQ_ACC(i) * fin;
+            for (int i = 0; i < XB - 3; ++i)
+                if (x0 + i >= P.xlo && x0 + i < P.xhi) o[i] = KQ_ACC(i + 3) * fin;
+            const size_t so = (size_t)part * P.side_stride + (size_t)(xt * NH + half) * 3 * snum + ti_raw;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                P.side_l[so + (size_t)c * snum] = KQ_ACC(c);
+                P.side_r[so + (size_t)c * snum] = KQ_ACC(XB + c);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < XB; ++i)
+                if (x0 + i >= P.xlo && x0 + i < P.xhi) o[i] = KQ_ACC(i) * fin;
+        }
     }
 #undef KQ_ACC
     if (!P.queue) break;
     }   // item loop
 }
 
+// The three columns left of every tile start under the quad-aligned window: the tile left of the start summed the offsets at
+// which its window still reached them (side_r), the tile right of it the rest (side_l).  One thread per (sample, tile start,
+// piece): out = (right tile's sum of the left tile + left-edge sum of the right tile) * fin, always in this order and without
+// atomics, so an image is the same from run to run and under any queue order.  `out`: the image, or the partial images of
+// the pieces of a walk (stride part_stride) in front of kirch_combine_kernel.
+__global__ __launch_bounds__(256) void kirch_fixup_kernel(FastParams P, int xb, int ntt, float *out)
+{
+    const int ti = blockIdx.y * 256 + threadIdx.x, b = blockIdx.x + 1, part = blockIdx.z;
+    if (ti >= P.snum || b >= ntt) return;
+    const float *r = P.side_r + (size_t)part * P.side_stride + (size_t)(b - 1) * 3 * P.snum + ti;
+    const float *l = P.side_l + (size_t)part * P.side_stride + (size_t)b * 3 * P.snum + ti;
+    const float fin = P.fin[ti];
+    float *o = out + (size_t)part * P.part_stride + (size_t)ti * P.ldo;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int x = P.x00 + b * xb - 3 + c;
+        if (x >= P.xlo && x < P.xhi) o[x - P.xlo] = (r[(size_t)c * P.snum] + l[(size_t)c * P.snum]) * fin;
+    }
+}
+
 // ===========================================================================
 // host side
 // ===========================================================================
 // a kirch_quad_kernel instantiation as launch_ring (kirch_ring.h) takes it
-template <int XB_, int OCC, int SH, int NH_ = 1, int LK = 0>
+template <int XB_, int OCC, int SH, int NH_ = 1, int LK = 0, int WK = KIRCH_WINDOW_SLIDE>
 struct RingF32 {
     typedef float elem;
-    static constexpr int XB = XB_, NH = NH_;
+    static constexpr int XB = XB_, NH = NH_, window = WK;
     static constexpr int align_mask = 7, step_block = 8, ring_blocks = (kq_ring_slots(XB) + 8 * LK) / 8, piece_bytes = kq_piece_bytes_lk(XB, LK);
     static auto near_kernel() { return kirch_quad_kernel<XB, true, 1, SH, 1, 0>; }
-    static auto far_kernel() { return kirch_quad_kernel<XB, false, OCC, SH, NH, LK>; }
+    static auto far_kernel() { return kirch_quad_kernel<XB, false, OCC, SH, NH, LK, WK>; }
+    static void launch_fixup(const FastParams &P, int ntt, hipStream_t st)      // ntt: tiles of the launch
+    {
+        hipLaunchKernelGGL(kirch_fixup_kernel, dim3(ntt - 1, (P.snum + 255) / 256, 1 << P.parts_log2), dim3(256), 0, st, P, XB, ntt,
+                           P.parts_log2 ? reinterpret_cast<float *>(P.partial) : P.out);
+    }
 };
 
 // kirch_tab_kernel: geometry-only pick/weight table, rebuilt with every prep (counted in prep time)
@@ -687,20 +760,16 @@ static int launch_tab(impdar_kirch_plan *p, const FastParams &P0, int nx, hipStr
 int kirch_launch_ring32(impdar_kirch_plan *p, void *d_out, int xlo, int xhi, hipStream_t st)
 {
     const FastParams P = kirch_ring_params(p, d_out, xlo, xhi);
+    // (the window kind is the route's: KIRCH_WINDOW_QUAD only for far-field plans)
+#define KQ_RING(...) (p->window == KIRCH_WINDOW_QUAD ? launch_ring<RingF32<__VA_ARGS__, KIRCH_WINDOW_QUAD>>(p, P, st) : launch_ring<RingF32<__VA_ARGS__>>(p, P, st))
     if (p->quad && p->quadSH == 0)
-        return p->xb == 40 ? launch_ring<RingF32<40, 2, 0>>(p, P, st)
-               : p->xb == 32 ? launch_ring<RingF32<32, 2, 0>>(p, P, st)
-                             : launch_ring<RingF32<24, 3, 0>>(p, P, st);
-    if (p->quad && p->nh == 2 && p->xb == 32)
-        return launch_ring<RingF32<32, 4, 4, 2, 0>>(p, P, st);      // 70 KB of LDS: two workgroups of 8 waves per CU
-    if (p->quad && p->nh == 2 && p->xb == 40)
-        return p->lk ? launch_ring<RingF32<40, 2, 4, 2, 1>>(p, P, st) : launch_ring<RingF32<40, 2, 4, 2, 0>>(p, P, st);
-    if (p->quad && p->nh == 3 && p->xb == 40)
-        return p->lk ? launch_ring<RingF32<40, 3, 4, 3, 1>>(p, P, st) : launch_ring<RingF32<40, 3, 4, 3, 0>>(p, P, st);
-    if (p->quad)
-        return p->xb == 40 ? launch_ring<RingF32<40, 2, 4>>(p, P, st)
-               : p->xb == 32 ? launch_ring<RingF32<32, 2, 4>>(p, P, st)
-                             : launch_ring<RingF32<24, 2, 4>>(p, P, st);      // steep moveout: two workgroups per CU
+        return p->xb == 40 ? KQ_RING(40, 2, 0, 1, 0) : p->xb == 32 ? KQ_RING(32, 2, 0, 1, 0) : KQ_RING(24, 3, 0, 1, 0);
+    if (p->quad && p->nh == 2 && p->xb == 32) return KQ_RING(32, 4, 4, 2, 0);      // 70 KB of LDS: two workgroups of 8 waves per CU
+    if (p->quad && p->nh == 2 && p->xb == 40) return p->lk ? KQ_RING(40, 2, 4, 2, 1) : KQ_RING(40, 2, 4, 2, 0);
+    if (p->quad && p->nh == 3 && p->xb == 40) return p->lk ? KQ_RING(40, 3, 4, 3, 1) : KQ_RING(40, 3, 4, 3, 0);
+    if (p->quad)      // steep moveout: two workgroups per CU
+        return p->xb == 40 ? KQ_RING(40, 2, 4, 1, 0) : p->xb == 32 ? KQ_RING(32, 2, 4, 1, 0) : KQ_RING(24, 2, 4, 1, 0);
+#undef KQ_RING
     return launch_tab<16, 4, 4>(p, P, xhi - xlo, st);
 }
 

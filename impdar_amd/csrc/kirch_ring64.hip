@@ -312,7 +312,7 @@ __global__ __launch_bounds__(KF_THREADS * NH, OCC) void kirch_dquad_kernel(FastP
 template <int XB_, int SH, int NH_ = 1>
 struct RingF64 {
     typedef double elem;
-    static constexpr int XB = XB_, NH = NH_;
+    static constexpr int XB = XB_, NH = NH_, window = KIRCH_WINDOW_SLIDE;
     static constexpr int align_mask = 3, step_block = 4, ring_blocks = kd_ring_slots(XB) / 4, piece_bytes = kd_piece_bytes(XB);
     static auto near_kernel() { return kirch_dquad_kernel<XB, true, 1, SH, 1>; }
     static auto far_kernel() { return kirch_dquad_kernel<XB, false, (NH > 1 ? 4 : 2), SH, NH>; }

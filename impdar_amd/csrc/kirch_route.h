@@ -64,6 +64,52 @@ enum { KIRCH_ORDER_AUTO = -1, KIRCH_ORDER_CHUNK = 0, KIRCH_ORDER_PACKED = 1 };
 #ifndef KQ_GANG_MIN_GROUPS
 #define KQ_GANG_MIN_GROUPS 4
 #endif
+// The output window of a tile of kirch_quad_kernel (far field).  SLIDE: outputs [x0, x0 + XB) at every step; a lane's XB
+// ring slots start on a quad boundary one step in four, and it reads XB/4 + 1 quads at the other three.  QUAD: at offset n
+// the outputs [x0 - (n & 3), x0 - (n & 3) + XB), read from the ALIGNED XB slots -- XB/4 quads at every step, XB + 3
+// accumulators, and the three columns left of every tile start are the sum of two tiles' partial sums (kirch_quadwin_cover
+// below, kirch_fixup_kernel).  Tiles then start at multiples of the workgroup tile from trace 0, whatever the output block,
+// so that a block of a launch still equals the same columns of the whole image bit for bit.
+enum { KIRCH_WINDOW_SLIDE = 0, KIRCH_WINDOW_QUAD = 1 };
+#define KQ_WIN_EXTRA 3      // steps a staged trace stays in use longer, and a walk runs longer, under KIRCH_WINDOW_QUAD
+#ifndef KQ_DEFAULT_WINDOW
+#define KQ_DEFAULT_WINDOW KIRCH_WINDOW_QUAD     // where it is routed (kirch_route); impdar_kirch_window_policy overrides
+#endif
+// One step of the quad-aligned window, as kirch_quad_kernel's load_step / fma_step and the host-side cover
+// (kirch_quadwin_cover) both take it.  pm: the step's index mod the ring slots (a multiple of 8); a walk starts at an offset
+// nlo = 1 (mod 8) and relative trace q sits in ring slot q + 1, so pm + 1 = n (mod 8).
+KIRCH_HD constexpr int kq_win_phase(int pm) { return (pm + 1) & 3; }                            // n & 3
+KIRCH_HD constexpr int kq_win_first_quad(int pm, int nq) { return ((pm + 1) >> 2) % nq; }       // the run is XB/4 quads long
+// component c of the t-th quad of the run feeds accumulator a of XB + 3; accumulator a is output x0 - 3 + a
+KIRCH_HD constexpr int kq_win_acc(int pm, int t, int c) { return 4 * t + c + 3 - kq_win_phase(pm); }
+
+// The trace offsets nlo .. nhi an item of a ring kernel walks (kirch_ring_walk, kirch_ring.h, documents them); returns true
+// for an empty piece.  wx: KQ_WIN_EXTRA under KIRCH_WINDOW_QUAD -- outputs x0w - 3 .. x0w - 1 see their last offsets.
+KIRCH_HD static inline bool kirch_walk_range(int hmax, int x0w, int tnum, int S, int NB, int XB, int NH, int parts_log2, int part, int wx,
+                                             int &nlo, int &nhi)
+{
+    auto mx = [](int a, int b) { return a > b ? a : b; };
+    auto mn = [](int a, int b) { return a < b ? a : b; };
+    int nlo_ = mx(-hmax, -(x0w + XB - 1));
+    nlo_ -= (nlo_ - 1) & (S - 1);
+    int nhi_ = mn(hmax + (NH - 1) * XB, tnum - 1 - x0w + wx);
+    bool empty_part = false;
+    if (parts_log2) {
+        // piece boundaries (all = 1 mod S): ..., 1 - U k | 1 - U k .. 0 | 1 .. U k | 1 + U k, ...   (2 pieces: n <= 0 | n >= 1)
+        const int uk = (NB * S) * mx(1, (hmax + NB * S) / (2 * NB * S));
+        const int inner = parts_log2 == 2 ? uk : (1 << 28);
+        const int side = parts_log2 == 2 ? (part >> 1) : part;          // 0: n <= 0, 1: n >= 1
+        const bool far = parts_log2 == 2 && ((part & 1) ^ side) == 0;    // pieces 0 and 3 are the outer ones
+        const int lo = side == 0 ? (far ? -(1 << 28) : 1 - inner) : (far ? 1 + inner : 1);
+        const int hi = side == 0 ? (far ? -inner : 0) : (far ? (1 << 28) : inner);
+        nlo_ = mx(nlo_, lo);
+        nhi_ = mn(nhi_, hi);
+        empty_part = nhi_ < nlo_;
+    }
+    nlo = nlo_;
+    nhi = nhi_;
+    return empty_part;
+}
 // Row stride of the step-block pick table in 16-byte entries.  Not snum: with snum a power of two a chunk's
 // slice of consecutive rows (256 entries out of every snum) lands on 1/16 of the L2's sets (and of whatever else
 // indexes by address bits); the odd number of 256-byte lines of padding walks the slice over all of them.
@@ -74,9 +120,10 @@ KIRCH_HD static inline size_t kq_tkb_stride(int snum) { return (size_t)snum + KQ
 
 // Ring rows (samples per slot, whole 32-row pieces) of a workgroup with nh tiles of xb traces and step blocks of S traces
 // at a moveout of sa samples per trace.  (A moveout no ring can hold -- NaN included -- gives a size that fits nothing.)
-static inline int kirch_ring_rows(double sa, int xb, int nh, int S)
+// (`extra`: further traces of moveout a staged trace stays in use for -- the quad-aligned window, KIRCH_WINDOW_QUAD)
+static inline int kirch_ring_rows(double sa, int xb, int nh, int S, int extra = 0)
 {
-    const double m = std::ceil(sa * (xb * nh + S - 2));
+    const double m = std::ceil(sa * (xb * nh + S - 2 + extra));
     if (!(std::fabs(m) < 1e9)) return 1 << 30;
     return ((KF_THREADS + (int)m + 8 + 31) / 32) * 32;
 }
@@ -106,6 +153,15 @@ struct KirchKnobs {
         return v;
     }
 
+    // The window kind of the quad kernel comes the same way (impdar_kirch_window_policy; IMPDAR_KIRCH_WINDOW on the Python side).
+    enum { WINDOW_DEFAULT = 0, WINDOW_SLIDE = 1, WINDOW_QUAD = 2 };
+    int window = WINDOW_DEFAULT;
+    __attribute__((visibility("hidden"))) static int *window_policy()
+    {
+        static int v = WINDOW_DEFAULT;
+        return &v;
+    }
+
     static KirchKnobs from_env()
     {
         KirchKnobs K;
@@ -126,13 +182,15 @@ struct KirchKnobs {
         K.order = queue_policy()[0];
         K.g = queue_policy()[1];
         K.g_set = K.g != 0;
+        K.window = *window_policy();
         return K;
     }
     bool operator==(const KirchKnobs &o) const
     {
         return xb_set == o.xb_set && nh_set == o.nh_set && lk_set == o.lk_set && parts_set == o.parts_set && nhd_set == o.nhd_set &&
                xbd_set == o.xbd_set && xb == o.xb && nh == o.nh && lk == o.lk && parts == o.parts && nhd == o.nhd && xbd == o.xbd &&
-               impl == o.impl && exact_impl == o.exact_impl && tiefix_off == o.tiefix_off && g_set == o.g_set && g == o.g && order == o.order;
+               impl == o.impl && exact_impl == o.exact_impl && tiefix_off == o.tiefix_off && g_set == o.g_set && g == o.g && order == o.order &&
+               window == o.window;
     }
 };
 
@@ -225,6 +283,7 @@ struct KirchRoute {
     bool want_tie_groups = false;   // (kirch_route_after_ties) the downloaded list is to be grouped and kept
     int order = KIRCH_ORDER_AUTO;   // ring kernels, queue lists: KIRCH_ORDER_CHUNK | _PACKED (kirch_gangmap); _AUTO: by the launch (kirch_queue_order)
     int gang = 0;                   // ... adjacent tiles per gang, 1 | 2 | 4; 0: by the tile count of the launch (kirch_gang_size)
+    int window = KIRCH_WINDOW_SLIDE;    // quad kernel, far field: KIRCH_WINDOW_QUAD where the ring holds its 3 further traces of moveout
 
     int kernel() const             // what impdar_kirch_plan_kernel reports
     {
@@ -320,6 +379,17 @@ static inline KirchRoute kirch_route(const KirchGeometry &G, int dtype, int snum
     R.quadSH = ring32(xbq, nhq, lkq) <= 65535 ? 0 : 4;
     R.quad = mode == IMPDAR_KIRCH_FAST && !R.gen && quad_ok && !(K.impl == KirchKnobs::IMPL_TAB && tab_ok);
     R.xb = R.gen ? 32 : (R.quad ? xbq : 16);
+    // The quad-aligned window keeps a staged trace in use for 3 more steps: routed only where the ring has the rows for
+    // that moveout already (the slot size, and with it every recorded route, stays what it was); else the sliding form.
+    // The rows must hold it for one, two and three tiles per workgroup alike: the window kind then depends on the geometry
+    // and the tile width alone, and the tiles per workgroup still change no bit of an image.
+    {
+        const int want = K.window == KirchKnobs::WINDOW_SLIDE ? KIRCH_WINDOW_SLIDE
+                         : (K.window == KirchKnobs::WINDOW_QUAD ? KIRCH_WINDOW_QUAD : KQ_DEFAULT_WINDOW);
+        bool rows_hold = kirch_ring_rows(sa, xbq, nhq, 8, KQ_WIN_EXTRA) == wq;
+        for (int nh = 1; nh <= 3; ++nh) rows_hold = rows_hold && kirch_ring_rows(sa, xbq, nh, 8, KQ_WIN_EXTRA) == kirch_ring_rows(sa, xbq, nh, 8);
+        if (want == KIRCH_WINDOW_QUAD && R.quad && !nearfield && rows_hold) R.window = KIRCH_WINDOW_QUAD;
+    }
     // float64 data in exact mode on uniform grids: the same ring in float64 (20 or 16 output traces per lane, step blocks
     // of 4) when its window fits; otherwise (and for IMPDAR_KIRCH_EXACT_IMPL = tab | pair) the global-memory kernels.
     // The table-driven float64 kernels weight a pair by its trace OFFSET (n dx); the reference by dist[j] - dist[xi].
@@ -499,7 +569,8 @@ static inline KirchRingTables kirch_ring_tables(const KirchGeometry &G, const Ki
     T.win.resize((size_t)nch * T.nrows * 2);
     for (int r = 0; r < T.nrows; ++r) {
         // (with nh tiles on one ring the later tiles read the same traces (nh - 1) xb offsets earlier)
-        const long long nz = (long long)ringS * (r - T.mrow0) + 1 + R.xb + ringS - 2;
+        // (the quad-aligned window reads a trace up to 3 steps after the sliding one dropped it)
+        const long long nz = (long long)ringS * (r - T.mrow0) + 1 + R.xb + ringS - 2 + (R.window == KIRCH_WINDOW_QUAD ? KQ_WIN_EXTRA : 0);
         const long long na = (long long)ringS * (r - T.mrow0) + 1 - (long long)(R.nh - 1) * R.xb;
         const long long lo = (na <= 0 && nz >= 0) ? 0 : std::min(std::llabs(na), std::llabs(nz));
         const long long hi = std::max(std::llabs(na), std::llabs(nz));
@@ -544,10 +615,22 @@ static inline KirchTieGroups kirch_group_ties(std::vector<KirchTie> &list)
 // share staging lines in the XCD's L2) are handed out per chunk, longest first, each to the XCD with the least
 // accumulated walk so far (steps rounded up to ring revolutions, plus a prologue's worth).  -1 = empty slot.
 // An empty map: keep the arithmetic rule.
-static inline std::vector<short> kirch_tilemap(const std::vector<int> &h_hmax, int tnum, int xlo, int xhi, int tile_w, int align_mask,
-                                               int ring_blocks, int step_block, int G, int tiles_per_xcd, int nchunks)
+// (first tile start and tile count of a launch: kirch_tile_origin / kirch_tile_count; `window`: KIRCH_WINDOW_*)
+static inline int kirch_tile_origin(int xlo, int tile_w, int align_mask, int window)
 {
-    const int x00 = xlo & ~align_mask, nxt = (xhi - x00 + tile_w - 1) / tile_w;
+    return window == KIRCH_WINDOW_QUAD ? (xlo / tile_w) * tile_w : (xlo & ~align_mask);
+}
+// (the quad-aligned window: the tile right of the block's last column holds part of its last three columns' sums)
+static inline int kirch_tile_count(int xlo, int xhi, int tile_w, int align_mask, int window)
+{
+    return (xhi + (window == KIRCH_WINDOW_QUAD ? KQ_WIN_EXTRA : 0) - kirch_tile_origin(xlo, tile_w, align_mask, window) + tile_w - 1) / tile_w;
+}
+static inline std::vector<short> kirch_tilemap(const std::vector<int> &h_hmax, int tnum, int xlo, int xhi, int tile_w, int align_mask,
+                                               int ring_blocks, int step_block, int G, int tiles_per_xcd, int nchunks,
+                                               int window = KIRCH_WINDOW_SLIDE)
+{
+    const int x00 = kirch_tile_origin(xlo, tile_w, align_mask, window), nxt = kirch_tile_count(xlo, xhi, tile_w, align_mask, window);
+    const int wx = window == KIRCH_WINDOW_QUAD ? KQ_WIN_EXTRA : 0;
     const int units = (nxt + G - 1) / G, cap = tiles_per_xcd / G;
     if (nxt > 32767 || units > 8 * cap || (int)h_hmax.size() != nchunks) return {};
     std::vector<short> map((size_t)nchunks * tiles_per_xcd * 8, (short)-1);
@@ -559,7 +642,7 @@ static inline std::vector<short> kirch_tilemap(const std::vector<int> &h_hmax, i
             double w = 0;
             for (int t = u * G; t < std::min((u + 1) * G, nxt); ++t) {
                 const int x0 = x00 + t * tile_w;
-                const int nlo = std::max(-hm, -(x0 + tile_w - 1)), nhi = std::min(hm, tnum - 1 - x0);
+                const int nlo = std::max(-hm, -(x0 + tile_w - 1)), nhi = std::min(hm, tnum - 1 - x0 + wx);
                 const int blocks = std::max(0, nhi - nlo + step_block) / step_block;
                 w += ((blocks + ring_blocks - 1) / ring_blocks) * ring_blocks + 8;
             }
@@ -620,15 +703,16 @@ struct __attribute__((visibility("hidden"))) KirchGangMap {
     }
 };
 static inline KirchGangMap kirch_gangmap(const std::vector<int> &h_hmax, int tnum, int xlo, int xhi, int tile_w, int align_mask, int ring_blocks,
-                                         int step_block, int G, int order, int nchunks)
+                                         int step_block, int G, int order, int nchunks, int window = KIRCH_WINDOW_SLIDE)
 {
     KirchGangMap M;
-    const int x00 = xlo & ~align_mask, nxt = (xhi - x00 + tile_w - 1) / tile_w;
+    const int x00 = kirch_tile_origin(xlo, tile_w, align_mask, window), nxt = kirch_tile_count(xlo, xhi, tile_w, align_mask, window);
+    const int wx = window == KIRCH_WINDOW_QUAD ? KQ_WIN_EXTRA : 0;
     if (G < 1 || nxt < 1 || nxt > 32767 || nchunks < 1 || nchunks > 32767 || (int)h_hmax.size() != nchunks) return M;
     const int units = (nxt + G - 1) / G;
     if (order != KIRCH_ORDER_PACKED) {
         const int tpx = ((units + 7) / 8) * G;
-        const std::vector<short> map = kirch_tilemap(h_hmax, tnum, xlo, xhi, tile_w, align_mask, ring_blocks, step_block, G, tpx, nchunks);
+        const std::vector<short> map = kirch_tilemap(h_hmax, tnum, xlo, xhi, tile_w, align_mask, ring_blocks, step_block, G, tpx, nchunks, window);
         for (size_t i = 0; i < map.size(); ++i)
             if (map[i] >= 0) M.list[i & 7].push_back((int)((i / 8 / tpx) << 16) | map[i]);
         return M;
@@ -648,7 +732,7 @@ static inline KirchGangMap kirch_gangmap(const std::vector<int> &h_hmax, int tnu
             double w = 0, len = 0;
             for (int t = u * G; t < std::min((u + 1) * G, nxt); ++t) {      // (the cost of a tile as kirch_tilemap counts it)
                 const int x0 = x00 + t * tile_w;
-                const int nlo = std::max(-hm, -(x0 + tile_w - 1)), nhi = std::min(hm, tnum - 1 - x0);
+                const int nlo = std::max(-hm, -(x0 + tile_w - 1)), nhi = std::min(hm, tnum - 1 - x0 + wx);
                 const int blocks = std::max(0, nhi - nlo + step_block) / step_block;
                 const double wt = ((blocks + ring_blocks - 1) / ring_blocks) * ring_blocks + 8;
                 w += wt;
@@ -707,11 +791,27 @@ static inline KirchOneShotCuts kirch_oneshot_cuts(int tnum, int halo, bool two)
 // knobs[15]: xb_set, xb, nh_set, nh, lk_set, lk, parts_set, parts, nhd_set, nhd, xbd_set, xbd, impl, exact_impl, tiefix_off.
 // tie_count >= 0: kirch_route_after_ties(route, tie_count, tie_cap) is applied.
 // ints[32]: status, mode, kernel, tnum_pad, gen, genW, quad, dquad, xb, nh, lk, quadW, quadSH, walk_parts_log2, want_tie_scan, xtab_off,
-// tie_ambiguous, want_tie_groups, increasing, uni_t, uni_t11, uni_x, dist_sorted, order, gang (the probe's knobs leave both at their defaults); dbls[16]: tmax, dt, dx, xnoise, sa, alpha, hest,
+// tie_ambiguous, want_tie_groups, increasing, uni_t, uni_t11, uni_x, dist_sorted, order, gang (the probe's knobs leave both at their defaults),
+// window (KIRCH_WINDOW_* under the probe's window kind, impdar_kirch_window_probe); dbls[16]: tmax, dt, dx, xnoise, sa, alpha, hest,
 // gen_need, err_limit, err_sa.
+// The window kind of the probe's routes: KirchKnobs::WINDOW_*.  It starts as the sliding window (the tables of a route are
+// then what they were before the aligned window existed) until impdar_kirch_window_probe names another.
+static inline int *kirch_probe_window()
+{
+    static int v = KirchKnobs::WINDOW_SLIDE;
+    return &v;
+}
+extern "C" int impdar_kirch_window_probe(int window)
+{
+    if (window < KirchKnobs::WINDOW_DEFAULT || window > KirchKnobs::WINDOW_QUAD) return -1;
+    *kirch_probe_window() = window;
+    return 0;
+}
+
 static inline KirchKnobs kirch_probe_knobs(const int *k)
 {
     KirchKnobs K;
+    K.window = *kirch_probe_window();
     K.xb_set = k[0], K.xb = k[1], K.nh_set = k[2], K.nh = k[3], K.lk_set = k[4], K.lk = k[5], K.parts_set = k[6], K.parts = k[7];
     K.nhd_set = k[8], K.nhd = k[9], K.xbd_set = k[10], K.xbd = k[11], K.impl = k[12], K.exact_impl = k[13], K.tiefix_off = k[14];
     return K;
@@ -729,7 +829,7 @@ extern "C" int impdar_kirch_route_probe(int dtype, int snum, int tnum, const dou
                        G.uni_t11, G.uni_x, G.dist_sorted};
     const double D[10] = {G.tmax, G.dt, G.dx, G.xnoise, G.sa, G.alpha, G.hest, G.gen_need, R.err_limit, R.err_sa};
     std::copy(I, I + 23, ints);
-    ints[23] = R.order, ints[24] = R.gang;
+    ints[23] = R.order, ints[24] = R.gang, ints[25] = R.window;
     std::copy(D, D + 10, dbls);
     return 0;
 }
@@ -812,6 +912,111 @@ extern "C" int impdar_kirch_gangmap_probe(const int *h_hmax, int nchunks, int tn
         items = std::copy(M.list[x].begin(), M.list[x].end(), items);
     }
     return (int)M.items();
+}
+
+// The cover of a launch of kirch_quad_kernel (far field), step by step as the kernel walks it: every tile of the block
+// [xlo, xhi) of a tnum-trace profile, chunk aperture hmax (with its guard), tiles of xb traces, nh per workgroup, lk extra ring
+// groups, walks in 1 << parts_log2 pieces, window KIRCH_WINDOW_*.  Per step: the quads read (kq_win_first_quad, or the sliding
+// window's run), the accumulator and with it the output each component feeds (kq_win_acc), and the ring group each read slot
+// lies in -- which must hold the trace the (output, offset) pair needs, staged by a DMA whose barrier the reading wave has
+// passed, and not be re-filled while the read is in flight (the model of the ring: groups staged in the prologue, block k's by
+// the DMA issued behind the barrier of block k - 2 - lk and landed by the barrier of block k - 1).
+//   count[(xhi - xlo) * (2 hmax + 1)]: how many (tile, step, accumulator) take the pair (output x, offset n), |n| <= hmax
+//   written[xhi - xlo]: how often the column is written -- by a tile's whole columns, or by the fix-up of a tile start
+//   stats[8]: tiles, steps, quad reads, components that feed no accumulator, reads off a staged group (must be 0), components
+//             whose slot holds another trace than their pair's (must be 0), largest accumulator index, tile starts fixed up
+// Returns 0, or -1 for arguments the kernel has no instantiation for.
+extern "C" int impdar_kirch_quadwin_cover_probe(int tnum, int xlo, int xhi, int xb, int nh, int lk, int hmax, int parts_log2, int window,
+                                                int *count, int *written, long long *stats)
+{
+    if (!(xb == 24 || xb == 32 || xb == 40) || nh < 1 || nh > 3 || lk < 0 || lk > 1 || parts_log2 < 0 || parts_log2 > 2 || hmax < 0 ||
+        tnum < 1 || xlo < 0 || xhi <= xlo || xhi > tnum || (parts_log2 && nh != 1))
+        return -1;
+    const int S = 8, RG = kq_ring_slots(xb) + 8 * lk, NB = RG / S, NQ = RG / 4, G0 = xb / 8, TW = xb * nh;
+    const int wx = window == KIRCH_WINDOW_QUAD ? KQ_WIN_EXTRA : 0;
+    const int x00 = kirch_tile_origin(xlo, TW, 7, window), nxt = kirch_tile_count(xlo, xhi, TW, 7, window);
+    const long long span = 2LL * hmax + 1;
+    for (int i = 0; i < 8; ++i) stats[i] = 0;
+    for (int part = 0; part < (1 << parts_log2); ++part)
+        for (int xt = 0; xt < nxt; ++xt) {
+            const int x0w = x00 + xt * TW;
+            int nlo, nhi;
+            if (kirch_walk_range(hmax, x0w, tnum, S, NB, xb, nh, parts_log2, part, wx, nlo, nhi)) continue;
+            ++stats[0];
+            const int nblocks = (nhi - nlo + 1 + S - 1) / S, nrev = (nblocks + NB - 1) / NB;
+            // ring group -> image group (relative to the group of trace jbase - 1) it holds, and the barriers a reader must have passed
+            std::vector<long long> holds(NB, -1), ready(NB, 0);
+            auto dma = [&](int blk_for) {
+                const int g = ((blk_for + G0) % NB + NB) % NB;
+                holds[g] = blk_for + G0;
+                ready[g] = std::max(blk_for, 0);
+            };
+            for (int pb = -G0; pb <= 0; ++pb) dma(pb);
+            for (int j = 0; j <= lk; ++j) dma(1 + j);
+            // one step's reads; `check_only`: the reads are in flight while the ring changes -- they must still find their traces
+            auto step = [&](long long p, bool check_only) {
+                const int pm = (int)(p % RG), blk = (int)(p / S);
+                for (int h = 0; h < nh; ++h) {
+                    const int x0 = x0w + h * xb, n = nlo - h * xb + (int)p;
+                    for (int qd = 0; qd < NQ; ++qd) {
+                        const int t = (qd - kq_win_first_quad(pm, NQ) + NQ) % NQ;
+                        bool any = false;
+                        int acc[4];
+                        for (int c = 0; c < 4; ++c) {
+                            if (window == KIRCH_WINDOW_QUAD) {
+                                acc[c] = t < xb / 4 ? kq_win_acc(pm, t, c) : -1;
+                            } else {
+                                const int i = (4 * qd + c - pm - 1 + 2 * RG) % RG;       // fma_step's i0 .. i3
+                                acc[c] = i < xb ? i + 3 : -1;                            // (numbered like the aligned window's)
+                            }
+                            any = any || acc[c] >= 0;
+                        }
+                        if (!any) continue;
+                        if (!check_only && h == 0) ++stats[2];
+                        for (int c = 0; c < 4; ++c) {
+                            if (acc[c] < 0) {
+                                if (!check_only && h == 0) ++stats[3];
+                                continue;
+                            }
+                            const int x = x0 - 3 + acc[c];
+                            // the relative trace the pair (x, n) needs, and the one ring slot 4 qd + c stands for at this step
+                            const long long q = (long long)x + n - (x0w + nlo);
+                            if (((q + 1) % RG + RG) % RG != 4 * qd + c) {
+                                ++stats[5];
+                                continue;
+                            }
+                            const int g = (4 * qd + c) / 8;
+                            if (q + 1 < 0 || holds[g] != (q + 1) / 8 || ready[g] > blk) ++stats[4];
+                            if (check_only) continue;
+                            stats[6] = std::max<long long>(stats[6], acc[c]);
+                            if (blk < nblocks && x >= xlo && x < xhi && n >= -hmax && n <= hmax) ++count[(x - xlo) * span + n + hmax];
+                        }
+                    }
+                }
+            };
+            step(0, false);
+            for (int blk = 0; blk < nrev * NB; ++blk) {
+                for (int s = 1; s < S; ++s) step((long long)blk * S + s, false);      // issued in front of the block's barrier
+                dma(blk + 2 + lk);                                                    // behind it
+                step((long long)blk * S + 7, true);                                   // step 7's reads cross the barrier
+                if (blk + 1 < nrev * NB) step((long long)(blk + 1) * S, false);
+            }
+            stats[1] += (long long)nrev * NB * S;
+            for (int h = 0; h < nh; ++h) {
+                const int x0 = x0w + h * xb;
+                for (int i = 0; i < xb - wx; ++i)      // (the aligned window: the last three are the next tile start's)
+                    if (x0 + i >= xlo && x0 + i < xhi) ++written[x0 + i - xlo];
+            }
+        }
+    if (wx)
+        for (int b = 1; b < nxt * nh; ++b) {
+            ++stats[7];
+            for (int c = 0; c < 3; ++c) {
+                const int x = x00 + b * xb - 3 + c;
+                if (x >= xlo && x < xhi) written[x - xlo] += 1 << parts_log2;
+            }
+        }
+    return 0;
 }
 
 // returns the number of blocks; cut[blocks + 1], need[blocks] (at most 8 blocks)

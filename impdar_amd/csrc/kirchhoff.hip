@@ -230,6 +230,14 @@ extern "C" int impdar_kirch_queue_policy(int order, int gang)
     return IMPDAR_OK;
 }
 
+extern "C" int impdar_kirch_window_policy(int window)
+{
+    if (window < KirchKnobs::WINDOW_DEFAULT || window > KirchKnobs::WINDOW_QUAD) return IMPDAR_ERR_ARG;
+    *KirchKnobs::window_policy() = window;
+    return IMPDAR_OK;
+}
+extern "C" int impdar_kirch_plan_window(const impdar_kirch_plan *p) { return p ? p->window : IMPDAR_ERR_ARG; }
+
 // `more`: further input traces of the radargram whose first traces an earlier prep took, AFTER a migrate that reads
 // only those has been enqueued (the pipelined one-shot call): same buffer set, and no wait for that migrate -- it does
 // not read the rows written here.

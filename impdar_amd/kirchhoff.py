@@ -34,6 +34,7 @@ class KirchhoffPlan(object):
         self.mode = MODE_NAMES[self.lib.impdar_kirch_plan_mode(self.h)]
         self.tnum_pad = self.lib.impdar_kirch_plan_tnum_pad(self.h)
         self.kernel = KERNEL_NAMES[self.lib.impdar_kirch_plan_kernel(self.h)]
+        self.window = ('slide', 'quad')[self.lib.impdar_kirch_plan_window(self.h)]     # of kirch_quad_kernel's tiles
         # position noise of the profile in units of dx; the float64 table-driven kernels meet max(1e-12, 0.1 xnoise)
         self.xnoise = float(self.lib.impdar_kirch_plan_xnoise(self.h))
 

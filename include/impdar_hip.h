@@ -160,6 +160,15 @@ int impdar_kirch_plan_kernel(const impdar_kirch_plan *plan);
  *   gang : adjacent tiles of a chunk that go to one XCD together, 1, 2 or 4; 0 the library's choice
  * Anything else is IMPDAR_ERR_ARG and changes nothing. */
 int impdar_kirch_queue_policy(int order, int gang);
+/* The output window of the float32 ring kernel's tiles (far field), for every plan created after the call (process-wide, like
+ * the queue policy above).
+ *   window: 0 the library's choice, 1 the sliding window, 2 the quad-aligned window where the plan's ring holds its three
+ *           further traces of moveout (elsewhere the plan keeps the sliding one)
+ * The two differ by float32 rounding in the three columns left of every tile start (two partial sums added there) and in no
+ * other bit.  Anything else is IMPDAR_ERR_ARG and changes nothing. */
+int impdar_kirch_window_policy(int window);
+/* which one the plan's kernel runs: 0 sliding, 1 quad-aligned */
+int impdar_kirch_plan_window(const impdar_kirch_plan *plan);
 int impdar_kirch_prep(impdar_kirch_plan *plan, const void *d_data, int ld, int jlo, int nloc);
 int impdar_kirch_allgather(impdar_kirch_plan *plan);
 /* Halo form of the exchange ("grouped ncclSend/ncclRecv of halos when H < shard"): this rank sends
