@@ -1350,6 +1350,81 @@ def main():
                                        "written once for the flatten" % passes},
                           "cpu_baseline": cb}), flush=True)
 
+    if 'load' not in args.skip:
+        # instrument file to resident float32 radargram: pulseEKKO-1.0-shaped records (128-byte trace header, int16 samples; the mean
+        # of the first 100 samples taken off) and RAMAC-shaped ones (int16, kept as they are).  Per call with spreads: the host route
+        # (decode_host, widen, to_device) against the device route (the file's bytes up as they are, decoded in HBM); the decode
+        # kernels alone (the context's kernel timer, bytes already resident) against HBM on the compulsory bytes -- the records read
+        # once, the result written once -- and against a device copy of the same bytes in this run
+        import ctypes
+        from impdar_amd import rawload
+        snum, tnum = (int(v) for v in args.chain.split('x'))
+        ctx, lib = _hip.context(), _hip.load()
+
+        def lspread(fn, reps=5):
+            fn()
+            ts = []
+            for _ in range(reps):
+                a = time.perf_counter()
+                fn()
+                lib.impdar_ctx_sync(ctx)
+                ts.append((time.perf_counter() - a) * 1e3)
+            return {"median": float(np.median(ts)), "min": min(ts), "max": max(ts), "reps": reps}
+
+        def lcopy_ms(nbytes):
+            half = (nbytes // 2 + 7) // 8 * 8                          # a copy reads and writes: half the bytes each way
+            a = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            b = _hip.DeviceArray(ctx, (half // 8, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, half)
+            ms = lspread(lambda: lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(half // 8)), reps=7)
+            a.free()
+            b.free()
+            return ms
+
+        def load_line(label, layout, out_dtype):
+            raw = np.random.default_rng(12).integers(0, 256, layout.stride * layout.tnum, dtype=np.uint8)
+            out_dtype = np.dtype(out_dtype) if out_dtype is not None else rawload.native_dtype(layout)
+
+            def host_route():
+                d = _hip.DeviceArray.from_host(ctx, rawload.decode_host(raw, layout).astype(out_dtype, copy=False))
+                d.free()
+
+            def device_route():
+                rawload.decode_dev(raw, layout, out_dtype, ctx=ctx).free()
+
+            host_ms, dev_ms = lspread(host_route, reps=3), lspread(device_route)
+            d_raw = _hip.DeviceArray.from_host(ctx, raw)
+            kernel = []
+            for _ in range(8):
+                d = rawload.decode_dev(d_raw, layout, out_dtype)
+                ms = ctypes.c_float()
+                _hip.check(lib.impdar_ctx_last_kernel_ms(ctx, ctypes.byref(ms)), 'impdar_ctx_last_kernel_ms')
+                kernel.append(ms.value)
+                d.free()
+            d_raw.free()
+            kernel = sorted(kernel[1:])
+            kernel_ms = {"min": kernel[0], "median": kernel[len(kernel) // 2], "max": kernel[-1]}
+            el = rawload.IN_DTYPES[layout.in_kind].itemsize
+            nbytes = layout.snum * layout.tnum * (el + out_dtype.itemsize)
+            copy = lcopy_ms(nbytes)
+            print(json.dumps({"path": "load %d x %d int16 records%s" % (snum, tnum, label),
+                              "config": "%d MB of file to %d MB of resident %s, record of %d bytes with %d of header" %
+                                        (raw.nbytes >> 20, (layout.snum * layout.tnum * out_dtype.itemsize) >> 20, out_dtype.name,
+                                         layout.stride, layout.head),
+                              "host_decode_widen_upload_ms": host_ms, "raw_upload_device_decode_ms": dev_ms,
+                              "device_ms": kernel_ms["median"], "device_ms_spread": kernel_ms,
+                              "compulsory_bytes": nbytes, "copy_same_bytes_ms": copy,
+                              "kernel_events_over_copy_host_clock": kernel_ms["median"] / copy["median"],
+                              "roofline": {"bound": "hbm", "achieved": nbytes / kernel_ms["median"] / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                           "frac": nbytes / kernel_ms["median"] / 1e6 / 8000.0,
+                                           "note": "the decode kernels alone (for pulseEKKO the trace means, then the transposing pass) "
+                                                   "from events on the stream, the file's bytes already resident; the copy of equal bytes "
+                                                   "and the two routes per call on the host clock around a device synchronise, the file's "
+                                                   "bytes in pageable host memory"}}), flush=True)
+
+        load_line("", rawload.pe_layout(snum, tnum, True), np.float32)
+        load_line(", kept int16 (RAMAC-shaped)", rawload.ramac_layout(snum, tnum), None)
+
 
 if __name__ == '__main__':
     main()

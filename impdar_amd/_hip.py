@@ -33,6 +33,7 @@ _dp = C.POINTER(C.c_double)
 _i = C.c_int
 _d = C.c_double
 _ip = C.POINTER(C.c_int)
+_ll = C.c_longlong
 
 # name -> (restype, argtypes); must list every symbol of include/impdar_hip.h
 SIGNATURES = {
@@ -135,6 +136,9 @@ SIGNATURES = {
     'impdar_apres_decode': (_i, [_p, _p, _i, C.c_longlong, _d, _dp]),
     'impdar_apres_decode_dev': (_i, [_p, _p, _i, C.c_longlong, _d, _p]),
     'impdar_apres_decode_pieces_dev': (_i, [_p, _p, _i, C.c_longlong, _d, _p, C.c_longlong]),
+    'impdar_rawload_plan': (_i, [_ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, C.POINTER(_ll)]),
+    'impdar_rawload_dev': (_i, [_p, _p, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _p]),
+    'impdar_rawload': (_i, [_p, _p, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _p]),
     'impdar_auto_pick': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_auto_pick_dev': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_pick_guided': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _dp, _ip]),

@@ -44,6 +44,7 @@ from ._RadarDataSpectra import horizontal_spectrum as _horizontal_spectrum, spec
 from ._RadarDataSpectra import vertical_spectrum as _vertical_spectrum
 from ._RadarDataDisplay import flattened as _flattened, percentiles as _percentiles, window as _window
 from ... import resident as _resident
+from ._resident import data_dtype as _resident_dtype, data_shape as _resident_shape
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
 
@@ -144,12 +145,13 @@ class RadarData(object):
         for attr in self.attrs_guaranteed + ['fn']:
             if not hasattr(self, attr):
                 raise ImpdarError('{:s} is missing. It appears that this is an ill-defined RadarData object'.format(attr))
-            if getattr(self, attr) is None:
+            if getattr(self, attr) is None and not (attr == 'data' and getattr(self, '_dev', None) is not None):
                 raise ImpdarError('{:s} is None. It appears that this is an ill-defined RadarData object'.format(attr))
         for attr in self.attrs_optional:
             if not hasattr(self, attr):
                 raise ImpdarError('{:s} is missing. It appears that this is an ill-defined RadarData object'.format(attr))
-        if (self.data.shape != (self.snum, self.tnum)) and (self.elev is None):
+        # (a radargram that was decoded in HBM has no host array: the resident shape is checked)
+        if (tuple(_resident_shape(self)) != (self.snum, self.tnum)) and (self.elev is None):
             raise ImpdarError('The data shape does not match the snum and tnum values!!!')
         for attr in ['lat', 'long', 'pressure', 'trig', 'elev', 'dist', 'x_coord', 'y_coord', 'decday']:
             val = getattr(self, attr, None)
@@ -165,7 +167,7 @@ class RadarData(object):
             elif val.shape[0] != self.tnum:
                 raise ImpdarError('{:s} needs length tnum {:d}'.format(attr, self.tnum))
         if getattr(self, 'data_dtype', None) is None:
-            self.data_dtype = self.data.dtype
+            self.data_dtype = _resident_dtype(self)
 
     def save(self, fn):
         """Write a StoDeep/ImpDAR ``.mat``; ``data`` is cast back to the dtype

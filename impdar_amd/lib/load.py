@@ -1,7 +1,8 @@
 """Loader for the one file type on the migration CLI path: ImpDAR/StoDeep
 ``.mat`` (reference ``src/impdar/lib/load/__init__.py:28,79-80``).  The
-reference's other 14 instrument readers are out of scope; convert with the
-reference's ``impdar load`` first."""
+instrument formats (GSSI, pulseEKKO, RAMAC, Tek) come in through
+``impdar_amd.lib.loaders`` and this package's ``impdar load``, which writes the
+``*_raw.mat`` files read here."""
 from .RadarData import RadarData
 
 FILETYPE_OPTIONS = ['mat']
@@ -12,5 +13,5 @@ def load(filetype, fns_in, channel=1, *args, **kwargs):
         fns_in = [fns_in]
     if filetype != 'mat':
         raise ValueError('Only ImpDAR .mat files can be loaded here (got %s); '
-                         'convert other formats with the reference\'s `impdar load`' % filetype)
+                         'convert other formats with `impdar load` (python -m impdar_amd.bin.impdarexec load)' % filetype)
     return [RadarData(fn) for fn in fns_in]

@@ -661,6 +661,44 @@ int impdar_apres_decode_dev(impdar_ctx *ctx, const void *counts_host, int kind, 
 int impdar_apres_decode_pieces_dev(impdar_ctx *ctx, const void *counts_host, int kind, long long n, double divisor,
                                    void *d_volts, long long piece_counts);
 
+/* ---- instrument files decoded in HBM (csrc/rawload.hip, csrc/rawload_route.h) ----
+ * A raw buffer of `nbytes` bytes -- a GSSI .DZT, pulseEKKO .DT1, RAMAC .rd3 or
+ * Tek .DAT file as it is on disk -- holds `tnum` little-endian records: record
+ * t starts at byte base + t * stride, its `snum` samples of `in_kind` at byte
+ * `head` of it (unsigned counts are the same bits as signed: I16 / I32).  With
+ * v[s, t] = sample s of record t, the native result of `op` is
+ *   NONE       v;
+ *   GSSI_TOP   rows 0 and 1 take row 2's values (load_gssi.py:210-211); I16, I32;
+ *   TEK_BIAS   v - 512 in int16, wrapping (load_tek.py:73-74); I16;
+ *   PE_DEMEAN  v minus np.nanmean of the trace's first min(100, snum) samples
+ *              (load_pulse_ekko.py:238-239), bit for bit: the mean in NumPy's
+ *              summation order in float64, the difference in float64, stored
+ *              as NumPy stores it into int16 (truncated through int32, low 16
+ *              bits) or float32 (to nearest even); I16, F32.
+ * out_kind NATIVE keeps int16 / int32 / float32, F32 and F64 convert the native
+ * value as astype does.  out: (snum, tnum) row-major of that type in device
+ * memory, aligned to its element.
+ * impdar_rawload_plan: the check alone, *out_bytes = snum * tnum * sizeof(out);
+ * it needs no context and no device.  IMPDAR_ERR_ARG: snum or tnum < 1, a
+ * negative size, head + snum * elem > stride, base + (tnum - 1) * stride +
+ * head + snum * elem > nbytes, GSSI_TOP with snum < 3, any product that
+ * overflows 64 bits.  IMPDAR_ERR_UNSUPPORTED: an op / kind pair not listed.
+ * No kernel runs on a descriptor the plan rejects.
+ * impdar_rawload_dev: raw bytes already in HBM (any byte alignment); enqueues on
+ * the compute stream and returns.  impdar_rawload: host bytes, uploaded as they
+ * are into scratch the context keeps, decoded by the same kernels; returns
+ * when the bytes have left the host and the result is complete.
+ * impdar_ctx_last_kernel_ms after either gives the decode kernels alone. */
+enum { IMPDAR_RAW_I16 = 0, IMPDAR_RAW_I32 = 1, IMPDAR_RAW_F32 = 2 };
+enum { IMPDAR_RAW_NONE = 0, IMPDAR_RAW_GSSI_TOP = 1, IMPDAR_RAW_TEK_BIAS = 2, IMPDAR_RAW_PE_DEMEAN = 3 };
+enum { IMPDAR_RAW_OUT_NATIVE = 0, IMPDAR_RAW_OUT_F32 = 1, IMPDAR_RAW_OUT_F64 = 2 };
+int impdar_rawload_plan(long long nbytes, long long base, long long stride, long long head, int snum, int tnum, int in_kind,
+                        int op, int out_kind, long long *out_bytes);
+int impdar_rawload_dev(impdar_ctx *ctx, const void *d_raw, long long nbytes, long long base, long long stride, long long head,
+                       int snum, int tnum, int in_kind, int op, int out_kind, void *d_out);
+int impdar_rawload(impdar_ctx *ctx, const void *raw_host, long long nbytes, long long base, long long stride, long long head,
+                   int snum, int tnum, int in_kind, int op, int out_kind, void *d_out);
+
 /* ---- what a plot reads from the radargram (csrc/display.hip) ----
  * data: (snum, tnum) float32 / float64, row-major; a window is rows [y0, y1),
  * traces [x0, x1) of it, 0 <= y0 <= y1 <= snum, 0 <= x0 <= x1 <= tnum.
