@@ -236,21 +236,26 @@ __global__ __launch_bounds__(WN_BLOCK) void wn_hsum_kernel(const T *__restrict__
                     s2 = V2[ro + j];
                     sc = (double)Vc[ro + j];
                 }
-                // padded columns: m zeros each, that is m * (0 - p) and m * p**2 (float32: fl32(0 * 0) = 0)
+                // padded columns: z = m zeros each.  They move the mean by -z p / N.  The fp64 variance is taken about
+                // the mean of the pivots, p over the N - z in-array elements and 0 over the z padded ones: that adds
+                // z (N - z) p**2 / N**2 + 2 z p s1 / N**2 to the variance about p of the in-array part.  Entering the
+                // zeros as z (0 - p) and z p**2 like any other element is the same number, but cancels to nothing once
+                // the window is much larger than the image (float32: fl32(0 * 0) = 0 adds nothing to s2).
                 const int npc = (lo_h - j > 0 ? lo_h - j : 0) + (j + hi_h - (tnum - 1) > 0 ? j + hi_h - (tnum - 1) : 0);
-                if (npc) {
-                    const double z = (double)npc * (double)m;
-                    s1 -= z * p;
-                    if (sizeof(T) == 8) s2 += z * (p * p);
-                }
+                const double z = (double)npc * (double)m;
                 double mean, var;
                 if (sc > 0.0) {
                     mean = __builtin_nan("");
                     var = __builtin_nan("");
                 } else {
-                    const double e1 = s1 / N;
-                    mean = p + e1;
-                    var = sizeof(T) == 8 ? s2 / N - e1 * e1 : s2 / N - mean * mean;
+                    const double eu = s1 / N;
+                    mean = p + (npc ? (s1 - z * p) / N : eu);
+                    if (sizeof(T) == 8) {
+                        var = s2 / N - eu * eu;
+                        if (npc) var += z * (p * (2.0 * s1 + p * (N - z))) / (N * N);
+                    } else {
+                        var = s2 / N - mean * mean;
+                    }
                 }
                 if (MODE == 0) {
                     acc += var;
