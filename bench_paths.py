@@ -297,6 +297,81 @@ def main():
                          "roofline": {"bound": "hbm", "achieved": algo / t / 1e6, "peak": 8000.0, "unit": "GB/s", "frac": algo / t / 1e6 / 8000.0}}
         rec["power_of_two_record_ns_per_sample"] = 0.27e6 / 4096 ** 2         # config 2: 0.27 ms at 4096 x 4096
         print(json.dumps(rec), flush=True)
+    if 'vscan' not in args.skip:
+        # The Stolt velocity scan at config 2, resident: 32 velocities in one impdar_stolt_scan_dev call against what a user does
+        # without it -- 32 impdar_stolt_dev calls, each image downloaded and reduced to the same three sums per row in NumPy.
+        # Device times from the HIP events of each call (the scan's stages from its own events: metrics line); bytes of the back
+        # half per velocity on the traces-first route, E = 4: the stretch writes a spectrum (E snum tnum; the shared spectrum it
+        # reads is counted as cache traffic, not HBM), the inverse C2C and the transpose read and write it, the C2R reads it and
+        # writes the image, the reduction reads the image: 8 E snum tnum.
+        import ctypes
+        n, nv = args.stolt, 32
+        ctx, lib = _hip.context(), _hip.load()
+        geo = synth.geometry(n, n)
+        xs = np.random.default_rng(0).standard_normal((n, n)).astype(np.float32)
+        vels = np.ascontiguousarray(1.68e8 * np.linspace(0.7, 1.3, nv))
+        kx_keep, p_kx = _hip.as_dp(2. * np.pi * np.fft.fftfreq(n, d=float(np.mean(geo['trace_int']))))
+        ws_keep, p_ws = _hip.as_dp(2. * np.pi * np.fft.rfftfreq(n, d=geo['dt']))
+        d_x = _hip.DeviceArray.from_host(ctx, xs)
+        d_o = _hip.DeviceArray(ctx, (n, n), np.float32)
+        sums = np.empty((nv, n, 3))
+        buf = ctypes.create_string_buffer(1024)
+
+        def metrics():
+            _hip.check(lib.impdar_ctx_last_metrics(ctx, buf, len(buf)), 'metrics')
+            return json.loads(buf.value.decode())
+
+        def scan():
+            _hip.check(lib.impdar_stolt_scan_dev(ctx, d_x.ptr, _hip.F32, n, n, p_kx, p_ws, _hip.as_dp(vels)[1], nv, 100., 1000., 0, n, 0,
+                                                 _hip.as_dp(sums)[1], -1, None), 'impdar_stolt_scan_dev')
+            return metrics()
+
+        def single(v):
+            _hip.check(lib.impdar_stolt_dev(ctx, d_x.ptr, _hip.F32, n, n, p_kx, p_ws, float(v), 100., 1000., d_o.ptr), 'impdar_stolt_dev')
+            return metrics()['device_ms']
+
+        for _ in range(2):                                   # warm-up: code objects, buffers
+            scan()
+            single(vels[0])
+        recs, singles, loops, loop_dev = [], [], [], []
+        for _ in range(max(5, args.reps)):                   # the two forms alternated in this process
+            recs.append(scan())
+            singles.append(single(vels[nv // 2]))
+        for _ in range(2):
+            t0 = time.perf_counter()
+            dev, by_hand = 0., np.empty((nv, n, 3))
+            for b, v in enumerate(vels):
+                dev += single(v)
+                img = d_o.to_host().astype(np.float64)
+                x2 = img * img
+                by_hand[b, :, 0], by_hand[b, :, 1], by_hand[b, :, 2] = np.abs(img).sum(axis=1), x2.sum(axis=1), (x2 * x2).sum(axis=1)
+            loops.append((time.perf_counter() - t0) * 1e3)
+            loop_dev.append(dev)
+        t0 = time.perf_counter()
+        scan()
+        scan_wall = (time.perf_counter() - t0) * 1e3
+        d_x.free()
+        d_o.free()
+        ms = [r['device_ms'] for r in recs]
+        t = float(np.median(ms))
+        med = lambda key: float(np.median([r[key] for r in recs]))
+        back = med('stretch_ms') + med('inverse_ms') + med('focus_ms')
+        algo = 8 * 4 * n * n * nv
+        print(json.dumps({"path": "vscan %d x %d float32, %d velocities" % (n, n, nv), "config": "%dx%d float32, resident" % (n, n),
+                          "kernel": recs[-1]['kernel'], "B": recs[-1]['B'], "nv": nv,
+                          "device_ms": t, "device_ms_spread": max(ms) - min(ms), "device_ms_all": ms, "device_ms_per_velocity": t / nv,
+                          "host_ms_one_call": scan_wall,
+                          "split_ms": {"front": t - back, "stretch": med('stretch_ms'), "inverse_passes": med('inverse_ms'),
+                                       "reduction": med('focus_ms')},
+                          "single_call_device_ms": float(np.median(singles)), "single_call_device_ms_all": singles,
+                          "algorithmic_bytes_back_half": algo,
+                          "roofline": {"bound": "hbm", "achieved": algo / back / 1e6, "peak": 8000.0, "unit": "GB/s", "frac": algo / back / 1e6 / 8000.0,
+                                       "note": "bytes of the back half (8 E snum tnum per velocity, the shared spectrum's reads not counted) over "
+                                               "the time of the stretch, the inverse passes and the reduction"},
+                          "by_hand": {"what": "%d impdar_stolt_dev calls, each followed by a download and NumPy sums" % nv,
+                                      "host_ms": min(loops), "host_ms_all": loops, "device_ms_of_the_calls": float(np.median(loop_dev))},
+                          "max_rel_diff_sums_vs_by_hand": float(np.max(np.abs(sums - by_hand) / by_hand)),
+                          "finite": bool(np.isfinite(sums).all())}), flush=True)
     if 'phsh' not in args.skip:
         n = args.phsh
         geo = synth.geometry(n, n)

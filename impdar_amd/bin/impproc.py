@@ -4,6 +4,9 @@
 MI355X engine, and ``autopick``, an extension: ``impproc autopick files --snums S ... --tnums T ... [--freq F] [--pol +-1]
 [--picknums N ...]`` picks one layer per seed (the reference's ``picklib.auto_pick``, which its GUI drives) and
 writes ``<name>_picked.mat``; the files come before the seed lists, which take every number that follows them.
+``impproc vscan VMIN VMAX NV [--htaper --vtaper --traces T0 T1 --samples S0 S1 --gates G --migrate] files``, another
+extension, scans the focus of the Stolt image over NV velocities (``RadarData.velocity_scan``), prints and saves it
+(``<name>_vscan.mat``) and, with ``--migrate``, migrates at the best one (``<name>_migrated.mat``).
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
@@ -160,6 +163,24 @@ def _get_args():
                                  help='Numbers of the new picks (default: continue after the largest present)')
     _add_def_args(parser_autopick)
 
+    parser_vscan = subparsers.add_parser('vscan', help='(extension) Stolt velocity scan: focus of the migrated image '
+                                                       'at NV velocities from VMIN to VMAX')
+    parser_vscan.set_defaults(func=vscan, name='vscan')
+    parser_vscan.add_argument('vmin', type=float, help='Lowest velocity of the scan (m/s)')
+    parser_vscan.add_argument('vmax', type=float, help='Highest velocity of the scan (m/s)')
+    parser_vscan.add_argument('nv', type=int, help='Number of velocities, evenly spaced from vmin to vmax')
+    parser_vscan.add_argument('--htaper', type=int, default=100, help='Number of samples for horizontal taper')
+    parser_vscan.add_argument('--vtaper', type=int, default=1000, help='Number of samples for vertical taper')
+    parser_vscan.add_argument('--traces', type=int, nargs=2, default=None, metavar=('T0', 'T1'),
+                              help='Measure the focus over traces T0 <= j < T1 (default: all)')
+    parser_vscan.add_argument('--samples', type=int, nargs=2, default=None, metavar=('S0', 'S1'),
+                              help='Measure the focus over samples S0 <= k < S1 (default: all)')
+    parser_vscan.add_argument('--gates', type=int, default=None,
+                              help='Split the sample range into this many depth gates, one best velocity each')
+    parser_vscan.add_argument('--migrate', action='store_true',
+                              help='Then migrate (stolt) at the best velocity and save <name>_migrated.mat')
+    _add_def_args(parser_vscan)
+
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
@@ -187,6 +208,11 @@ def main():
         parser.parse_args(['-h'])
 
     radar_data = load(args.ftype, args.fns)
+    if args.name == 'vscan':
+        # (its result is a table of focus values, not a radargram: it names and writes its own files)
+        for dat, fn in zip(radar_data, args.fns):
+            vscan(dat, fn=fn, nfiles=len(radar_data), **vars(args))
+        return
     if args.name == 'interp':
         interp(radar_data, **vars(args))
     else:
@@ -292,6 +318,44 @@ def agc(dat, window=50, scale_factor=50, **kwargs):
 def autopick(dat, snums=(), tnums=(), picknums=None, freq=None, pol=None, **kwargs):
     """(extension) Pick one layer per seed on the device and keep the picks for ``save``."""
     dat.pick_layers(snums, tnums, picknums=picknums, freq=freq, pol=pol)
+
+
+def _out_name(fn, o, nfiles, name):
+    """``main``'s output naming for one input file."""
+    if o is not None and nfiles == 1 and o[-1] != '/':
+        return o
+    bn = os.path.splitext(fn)[0]
+    if o is not None:
+        bn = os.path.join(o, os.path.split(bn)[1])
+    if bn[-4:] == '_raw':
+        bn = bn[:-4]
+    return bn + '_{:s}.mat'.format(name)
+
+
+def vscan(dat, vmin=1.5e8, vmax=1.9e8, nv=9, htaper=100, vtaper=1000, traces=None, samples=None, gates=None,
+          migrate=False, fn='vscan_raw.mat', o=None, nfiles=1, **kwargs):
+    """(extension) Stolt velocity scan: one line per velocity, the best one, ``<name>_vscan.mat`` with the velocities,
+    the three sums per row, the varimax and the best velocity; ``migrate``: then the ordinary Stolt migration at it."""
+    import numpy as np
+    from scipy.io import savemat
+    vels = np.linspace(vmin, vmax, nv)
+    scan = dat.velocity_scan(vels, htaper=htaper, vtaper=vtaper, traces=traces)
+    focus = scan.varimax(samples=samples)
+    best_i, best_vel = scan.best(samples=samples)
+    for v, f in zip(vels, focus):
+        print('vel %.6e m/s  varimax %.6g' % (v, f))
+    print('best velocity %.6e m/s (index %d)' % (best_vel, best_i))
+    out = {'vels': vels, 'l1': scan.l1, 'l2': scan.l2, 'l4': scan.l4, 'varimax': focus, 'best_vel': best_vel,
+           'traces': np.array(scan.traces)}
+    if gates is not None:
+        out['varimax_gates'] = scan.varimax(samples=samples, gates=gates)
+        out['best_vel_gates'] = scan.best(samples=samples, gates=gates)[1]
+        print('best velocity per gate: ' + ' '.join('%.6e' % v for v in out['best_vel_gates']))
+    savemat(_out_name(fn, o, nfiles, 'vscan'), out)
+    if migrate:
+        dat.migrate('stolt', vel=best_vel, htaper=htaper, vtaper=vtaper)
+        # (-o names the scan's file; the image goes beside the input, or into the folder -o names)
+        dat.save(_out_name(fn, o if o is not None and (nfiles > 1 or o[-1] == '/') else None, nfiles, 'migrated'))
 
 
 def interp(dats, spacing, gps_fn=None, offset=0.0, minmove=1.0e-2, extrapolate=False, **kwargs):

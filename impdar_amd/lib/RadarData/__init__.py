@@ -44,6 +44,7 @@ from ._RadarDataSpectra import horizontal_spectrum as _horizontal_spectrum, spec
 from ._RadarDataSpectra import vertical_spectrum as _vertical_spectrum
 from ._RadarDataDisplay import flattened as _flattened, percentiles as _percentiles, window as _window
 from ... import resident as _resident
+from ...velscan import stolt_velocity_scan as _velocity_scan
 from ._resident import data_dtype as _resident_dtype, data_shape as _resident_shape
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -83,6 +84,7 @@ class RadarData(object):
     percentiles = _percentiles
     window = _window
     flattened = _flattened
+    velocity_scan = _velocity_scan
     to_device = _resident.to_device
     from_device = _resident.from_device
 

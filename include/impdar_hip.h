@@ -207,6 +207,23 @@ int impdar_stolt(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnu
 int impdar_stolt_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
                      const double *kx, const double *ws, double vel, double htaper,
                      double vtaper, void *d_out);
+/* Velocity scan: the Stolt image of the same radargram at each of vels[0 .. nv), none of them downloaded -- the taper and
+ * the forward transforms run once, the stretch and the inverse transforms in batches of velocities (max_batch > 0 caps the
+ * batch; 0: as many as fit the library's budget), and every image is reduced on the device to three focus sums per output
+ * row over the traces t0 <= j < t1: sums[v][k] = { sum |x|, sum x^2, sum x^4 }, float64, [nv][2*(snum/2)][3] on the host.
+ * The additions have a fixed order (no atomics): the same call gives the same bits, whatever max_batch.  Every image is
+ * bit for bit what impdar_stolt_dev gives at that velocity; keep >= 0 copies the image of vels[keep] into d_keep
+ * (2*(snum/2) x tnum of dtype), keep = -1: no image (d_keep may be NULL).  d_data is not modified.  ERR_ARG unless
+ * nv >= 1, every velocity positive and finite, 0 <= t0 < t1 <= tnum and -1 <= keep < nv. */
+int impdar_stolt_scan_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
+                          const double *kx, const double *ws, const double *vels, int nv,
+                          double htaper, double vtaper, int t0, int t1, int max_batch,
+                          double *sums, int keep, void *d_keep);
+/* host-buffer form: data is uploaded once; keep_out (host) receives the image of vels[keep] when keep >= 0 */
+int impdar_stolt_scan(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum,
+                      const double *kx, const double *ws, const double *vels, int nv,
+                      double htaper, double vtaper, int t0, int t1, int max_batch,
+                      double *sums, int keep, void *keep_out);
 
 /* ---- the library's own batched power-of-two row transforms (csrc/own_fft.h) ----
  * What the Stolt / phase-shift calls of power-of-two sizes run their transforms on (rocFFT compiles the kernels of
