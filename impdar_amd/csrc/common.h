@@ -168,6 +168,27 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// The two device arrays of a host entry point's call (impdar_stolt, impdar_stolt_scan, impdar_phaseshift), from the cache of freed
+// ones (api.hip: no hipMalloc / hipFree per call).  The call uploads into din, runs, downloads from dout; the arrays go back
+// when it returns, after a synchronisation: nothing in flight may still touch them.
+struct CallArrays {
+    impdar_ctx *ctx;
+    void *din = nullptr, *dout = nullptr;
+    // outb = 0: the call has no second array
+    int alloc(size_t inb, size_t outb)
+    {
+        const int rc = impdar_devcache_alloc(ctx->device, inb, &din);
+        return rc || !outb ? rc : impdar_devcache_alloc(ctx->device, outb, &dout);
+    }
+    ~CallArrays()
+    {
+        if (!din) return;                                 // (the call ended before it had one)
+        (void)hipStreamSynchronize(ctx->stream);
+        impdar_devcache_free(din);
+        impdar_devcache_free(dout);
+    }
+};
+
 // The small host tables of a step (gains, windows, row indices): `blk` blocks packed at 16-byte-rounded offsets of
 // one device buffer, so a table of doubles stays aligned whatever precedes it.
 struct TableBlock {

@@ -1,4 +1,4 @@
-// Small RAII wrapper over rocFFT plans (used by stolt.hip, phaseshift.hip and ffd.hip).
+// Small RAII wrapper over rocFFT plans (used by stolt.hip, phaseshift.hip and ffd.hip); what it declares is defined in fft.hip.
 #pragma once
 #include <functional>
 #include <string>

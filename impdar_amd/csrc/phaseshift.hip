@@ -904,26 +904,14 @@ extern "C" int impdar_phaseshift(impdar_ctx *ctx, const void *data, int dtype, i
                                  const double *kx, const double *ws, double dt, const double *tt_us, double vconst,
                                  const double *vmig, int vmig_len, double htaper, double vtaper, void *out)
 {
-    // (the two device arrays of the call come from the cache of freed ones, api.hip: no hipMalloc / hipFree per call)
-    struct Arrays {
-        impdar_ctx *ctx;
-        void *din = nullptr, *dout = nullptr;
-        ~Arrays()
-        {
-            if (!din) return;                                 // (the call ended at its argument checks)
-            (void)hipStreamSynchronize(ctx->stream);          // (nothing in flight may still touch them)
-            impdar_devcache_free(din);
-            impdar_devcache_free(dout);
-        }
-    } a{ctx};
+    CallArrays a{ctx};
     const size_t bytes = (size_t)snum * tnum * impdar_dtype_size(dtype);
     int rc = ps_enter(ctx, data, out, dtype, snum, tnum, nt, kx, ws, dt, tt_us, vconst, vmig, vmig_len, htaper, vtaper, false, 0, -1,
                       [&](const void **d_in, void **d_out) -> int {
         impdar_trace("impdar_phaseshift: enter (%d x %d, nt %d)", snum, tnum, nt);
         impdar_ctx_pinned_prefetch(ctx, std::min(bytes, IMPDAR_STAGE_RING_BYTES));      // the download's staging ring, pinned while the call works
-        int rc = impdar_devcache_alloc(ctx->device, bytes, &a.din);
+        const int rc = a.alloc(bytes, bytes);
         if (rc) return rc;
-        if ((rc = impdar_devcache_alloc(ctx->device, bytes, &a.dout))) return rc;
         IMPDAR_HIP_CHECK(hipMemcpyAsync(a.din, data, bytes, hipMemcpyHostToDevice, ctx->stream));
         impdar_trace("impdar_phaseshift: upload enqueued");
         *d_in = a.din;

@@ -1,5 +1,6 @@
-"""Every header that the phase-shift units (csrc/phaseshift.hip, csrc/ffd.hip) or the Kirchhoff units (csrc/kirchhoff.hip,
-kirch_ring32.hip, kirch_ring64.hip, kirch_oneshot.hip, kirch_gen.hip) include from csrc/ (transitively) compiles as the only include of a
+"""Every header that the phase-shift units (csrc/phaseshift.hip, csrc/ffd.hip), the Kirchhoff units (csrc/kirchhoff.hip,
+kirch_ring32.hip, kirch_ring64.hip, kirch_oneshot.hip, kirch_gen.hip) or the Stolt and transform units (csrc/stolt.hip, csrc/fft.hip)
+include from csrc/ (transitively) compiles as the only include of a
 translation unit: each names what it uses, none relies on the place or the order in which a source happens to include it.
 Syntax only (host and device pass), no GPU."""
 import os
@@ -27,7 +28,8 @@ def _local_headers(path, seen):
 
 def headers():
     seen = set()
-    for src in ('phaseshift.hip', 'ffd.hip', 'kirchhoff.hip', 'kirch_ring32.hip', 'kirch_ring64.hip', 'kirch_oneshot.hip', 'kirch_gen.hip'):
+    for src in ('phaseshift.hip', 'ffd.hip', 'kirchhoff.hip', 'kirch_ring32.hip', 'kirch_ring64.hip', 'kirch_oneshot.hip', 'kirch_gen.hip',
+                'stolt.hip', 'fft.hip'):
         _local_headers(os.path.join(CSRC, src), seen)
     return sorted(seen)
 
@@ -35,7 +37,8 @@ def headers():
 def test_the_split_headers_are_among_them():
     assert {'ps_layout.h', 'ps_common.h', 'ps_direct.h', 'ps_plan.h', 'ps_mfma.h', 'ps_smooth.h', 'ps_nufft.h', 'ps_series.h',
             'ps_runs.h', 'ps_route.h', 'ps_path_plan.h', 'ps_series_plan.h', 'fft.h', 'own_fft.h', 'common.h',
-            'kirch_prep.h', 'kirch_exact.h', 'kirch_ring.h', 'kirch_plan.h', 'kirch_route.h'} <= set(headers())
+            'kirch_prep.h', 'kirch_exact.h', 'kirch_ring.h', 'kirch_plan.h', 'kirch_route.h',
+            'stolt_route.h', 'stolt_kernels.h'} <= set(headers())
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason='hipcc not installed')

@@ -10,8 +10,8 @@ import pytest
 from conftest import ROOT
 
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-SOURCES = ['api.hip', 'download.hip', 'comm.hip', 'kirchhoff.hip', 'kirch_ring32.hip', 'kirch_ring64.hip', 'kirch_oneshot.hip', 'kirch_gen.hip', 'stolt.hip',
-           'phaseshift.hip', 'preproc.hip']
+SOURCES = ['api.hip', 'download.hip', 'comm.hip', 'kirchhoff.hip', 'kirch_ring32.hip', 'kirch_ring64.hip', 'kirch_oneshot.hip', 'kirch_gen.hip', 'fft.hip',
+           'stolt.hip', 'phaseshift.hip', 'preproc.hip']
 
 
 def _gpu_present():

@@ -1,4 +1,4 @@
-"""The seven-pass form of the Stolt path on power-of-two sizes (csrc/stolt.hip, round 6) restated in NumPy (CPU): the transform over the
+"""The seven-pass form of the Stolt path on power-of-two sizes (csrc/stolt.hip, its stretch in csrc/stolt_kernels.h; round 6) restated in NumPy (CPU): the transform over the
 TRACES first, the wavenumbers k >= 0 with ALL frequencies, the stretch along each row for both signs of the frequency -- the negative
 half by the same interpolation, with the same weights, between the mirrored knots of the same row -- and a real inverse transform over the
 traces at the end.  Held to the oracle's restatement of mig_python.py:126-208 (rfft2 / irfft2: the frequencies w >= 0 of all

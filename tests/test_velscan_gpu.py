@@ -1,4 +1,4 @@
-"""The Stolt velocity scan on the device (csrc/stolt.hip: impdar_stolt_scan[_dev]) at the smallest shapes that reach every route:
+"""The Stolt velocity scan on the device (csrc/stolt.hip: impdar_stolt_scan[_dev]; its kernels: csrc/stolt_kernels.h) at the smallest shapes that reach every route:
 
   traces first, power of two (tnum = 64 is the gate)        64 x 64, 128 x 64      float32, float64
   [w][kx], power of two (tnum < 64)                         64 x 32                float32, float64
