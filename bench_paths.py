@@ -10,7 +10,7 @@ filters (hbp, lp, hp; float64, as constant_space hands them on) at the same size
 winavg_hfilt beside a device-to-device copy of equal bytes, and Stolt at the headline radargram's shape (4096 samples x 10000
 traces, no power of two: the library's own mixed-radix row transforms against rocFFT's plans, steady state and the first call
 of a fresh process), and ApRES range conversion and stacking at an unattended deployment's size (40 bursts x 20 chirps x 40001
-samples, float64),
+samples, float64), and the time-offset search of kinematic GPS control (10000 traces, 100000 fixes, the reference's five passes),
 each through the product path on one MI355X.
 Prints one JSON line per path.  Host wall time includes H2D/D2H of the
 radargram (the entry points take host buffers).  Each line carries a
@@ -1499,6 +1499,85 @@ def main():
 
         load_line("", rawload.pe_layout(snum, tnum, True), np.float32)
         load_line(", kept int16 (RAMAC-shaped)", rawload.ramac_layout(snum, tnum), None)
+
+    if 'gps' not in args.skip:
+        # the time-offset search of kinematic GPS control: 10000 traces at 1 s inside a record of 100000 fixes, the reference's five
+        # passes from offset 0 (5001 candidates over +-0.1 days, then 4 x 1001 around the running offset).  Per pass: the whole call
+        # on the host clock (upload of the track and the traces, kernel, download of cc) and the kernel alone from events; the same
+        # arithmetic in SciPy / NumPy (tests/gps_ref.py, the reference's lines) on one core for a sample of candidates, scaled
+        import ctypes
+        import os
+        from impdar_amd import gpstrack
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+        import gps_ref
+        tnum, ngps = 10000, 100000
+        ctx, lib = _hip.context(), _hip.load()
+        rng = np.random.default_rng(17)
+        s_trace = np.arange(tnum, dtype=np.float64)
+        s_gps = np.sort(rng.uniform(-0.12 * gps_ref.DAY, 0.12 * gps_ref.DAY + tnum, ngps))
+        t, gps_t = gps_ref.DECIDED_T0 + s_trace / gps_ref.DAY, gps_ref.DECIDED_T0 + s_gps / gps_ref.DAY
+        rlat = gps_ref.track_lat(s_trace - 2.5) + 2e-6 * rng.standard_normal(tnum)
+        rlon = gps_ref.track_lon(s_trace - 2.5) + 2e-6 * rng.standard_normal(tnum)
+        glat, glon = gps_ref.track_lat(s_gps), gps_ref.track_lon(s_gps)
+
+        def one_pass(offset):
+            sv = np.linspace(-0.1 * abs(offset), 0.1 * abs(offset), 1001) if offset != 0.0 else np.linspace(-0.1, 0.1, 5001)
+            a = time.perf_counter()
+            cc, nout = gpstrack.cc_search(gps_t, glat, glon, t, rlat, rlon, offset, sv, False)
+            wall = (time.perf_counter() - a) * 1e3
+            ms = ctypes.c_float()
+            _hip.check(lib.impdar_ctx_last_kernel_ms(ctx, ctypes.byref(ms)), 'impdar_ctx_last_kernel_ms')
+            return sv, cc, nout, wall, ms.value
+
+        def five_passes():
+            offset, walls, kernels = 0.0, [], []
+            for _ in range(5):
+                sv, cc, nout, wall, k = one_pass(offset)
+                if np.any(nout):
+                    raise ValueError('the GPS record does not span the search window')
+                offset += sv[np.argmax(cc)]
+                walls.append(wall)
+                kernels.append(k)
+            return offset, walls, kernels
+
+        five_passes()
+        runs = [five_passes() for _ in range(max(args.reps, 5))]
+        walls, kernels = np.array([r[1] for r in runs]), np.array([r[2] for r in runs])
+
+        def stat(v):
+            return {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)), "reps": int(len(v))}
+
+        upload = []
+        in_bytes = 8 * (3 * ngps + 3 * tnum + 5001)
+        d = _hip.DeviceArray(ctx, (in_bytes // 8, 1), np.float64)
+        h = np.zeros(in_bytes // 8)
+        for _ in range(6):
+            a = time.perf_counter()
+            _hip.check(lib.impdar_dev_upload(ctx, d.ptr, h.ctypes.data_as(ctypes.c_void_p), in_bytes), 'impdar_dev_upload')
+            upload.append((time.perf_counter() - a) * 1e3)
+        d.free()
+        upload_ms = float(np.median(upload[1:]))
+        out = {"path": "gps offset search 10000 traces x 100000 fixes, 5001 + 4 x 1001 offsets",
+               "config": "float64, np.interp form (no extrapolation), one workgroup of 256 threads per candidate, two passes over the "
+                         "traces per candidate, one bisection of the fixes per trace and pass",
+               "final_offset_s": runs[0][0] * gps_ref.DAY,
+               "device_ms_per_pass": [stat(kernels[:, p]) for p in range(5)], "device_ms_five_passes": stat(kernels.sum(axis=1)),
+               "call_ms_per_pass": [stat(walls[:, p]) for p in range(5)], "call_ms_five_passes": stat(walls.sum(axis=1)),
+               "upload_ms_one_call": upload_ms, "upload_bytes_one_call": in_bytes,
+               "upload_share_of_five_calls": 5 * upload_ms / float(np.median(walls.sum(axis=1))),
+               "note": "device_ms: the search kernel alone from events on the stream; call_ms: cc_search on the host clock, every "
+                       "call uploading the track and the traces again and waiting for cc; upload_ms_one_call: a synchronous copy of a "
+                       "call's input bytes from pageable memory, timed by itself"}
+        if not args.no_cpu:
+            sample = np.linspace(-0.1, 0.1, 5001)[::500]
+            a = time.perf_counter()
+            gps_ref.cc_f64(gps_t, glat, glon, t, rlat, rlon, 0.0, sample, False)
+            per = (time.perf_counter() - a) / len(sample)
+            out["cpu_baseline"] = {"what": "the reference's interp1d + np.corrcoef lines (tests/gps_ref.cc_f64), one core, timed on %d "
+                                           "candidates and scaled to 5001 + 4 x 1001" % len(sample),
+                                   "ms_per_candidate": per * 1e3, "five_passes_s": per * (5001 + 4 * 1001),
+                                   "speedup_over_device_calls": per * (5001 + 4 * 1001) * 1e3 / float(np.median(walls.sum(axis=1)))}
+        print(json.dumps(out), flush=True)
 
 
 if __name__ == '__main__':

@@ -1,6 +1,6 @@
 #! /usr/bin/env python
 """``impproc migrate`` (and the steps usually run around it, ``vbp``, ``hfilt``, ``ahfilt``, ``denoise``,
-``interp``, ``hbp``, ``lp``, ``crop``, ``nmo``, ``elev``, ``rev``, ``hcrop``, ``restack``, ``rgain`` and ``agc``) on the
+``interp``, ``geolocate``, ``hbp``, ``lp``, ``crop``, ``nmo``, ``elev``, ``rev``, ``hcrop``, ``restack``, ``rgain`` and ``agc``) on the
 MI355X engine, and ``autopick``, an extension: ``impproc autopick files --snums S ... --tnums T ... [--freq F] [--pol +-1]
 [--picknums N ...]`` picks one layer per seed (the reference's ``picklib.auto_pick``, which its GUI drives) and
 writes ``<name>_picked.mat``; the files come before the seed lists, which take every number that follows them.
@@ -10,19 +10,22 @@ extension, scans the focus of the Stolt image over NV velocities (``RadarData.ve
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
-denoise ``:275-293``, ``main`` ``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig``
+geolocate ``:253-272``, ``geolocate`` ``:494-500``, denoise ``:275-293``, ``main`` ``:378-415``, ``hfilt`` ``:418-420``, ``ahfilt`` ``:423-425``, ``mig``
 ``:508-519``, ``vbp`` ``:438-440``, ``hbp`` ``:443-445``, ``lp`` ``:448-450``, ``interp`` ``:483-491``,
 ``denoise`` ``:503-505``; crop parser ``:152-171``, nmo ``:193-220``, elev ``:71-75``, ``elev`` ``:433-435``,
 ``crop`` ``:453-455``, ``nmo`` ``:463-465``; rev parser ``:57-61``, restack ``:78-87``, rgain ``:90-99``, agc
 ``:102-111``, hcrop ``:174-190``, ``rev`` ``:428-430``, ``hcrop`` ``:458-460``, ``restack`` ``:468-470``, ``rgain``
 ``:473-475``, ``agc`` ``:478-480``): same options, types and defaults, same output naming
-(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|denoise|cropped|nmo|elev|rev|hcropped|restacked|rgain|agc>.mat``, ``-o`` file or
+(``<name minus _raw>_<migrated|hfilted|ahfilt|bandpassed|hbp|lp|interp|geolocate|denoise|cropped|nmo|elev|rev|hcropped|restacked|rgain|agc>.mat``, ``-o`` file or
 folder).  As in the reference, ``impproc ahfilt WIN`` parses ``WIN`` but filters with the function's default
 window of 1000 traces.  ``impproc denoise V H`` accepts ``--filt weiner|wiener|median`` (default ``weiner``, the reference's
 spelling, which runs the Wiener filter; the reference's own default fails in its ``RadarData.denoise``).
 As in the reference, ``impproc nmo --const_firn_offset X`` parses ``X`` and does not forward it.
 As in the reference, ``impproc agc`` has no option for the scaling factor and gains with the function's default of 50.
-The reference's other processing sub-commands (``cat``, ``geolocate`` and the rest) are out of scope.
+``impproc geolocate FILE [--extrapolate] [--guess]`` attaches a precision GPS track (``gpslib.interp``); with ``--guess``
+the clock offset between radar and GPS is searched on the MI355X.  ``impproc interp --gps_fn`` stays refused: run
+``geolocate`` first, then ``interp`` on its output.
+The reference's other processing sub-commands (``cat`` and the rest) are out of scope.
 
     python -m impdar_amd.bin.impproc migrate --mtype kirch line1_raw.mat
 """
@@ -31,6 +34,7 @@ import os
 import sys
 
 from ..lib.load import load, FILETYPE_OPTIONS
+from ..lib.gpslib import interp as interpdeep
 
 
 def _get_args():
@@ -185,12 +189,21 @@ def _get_args():
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
     parser_interp.add_argument('--gps_fn', type=str, default=None,
-                               help='File with precision GPS (kinematic GPS control is not part of this engine; '
+                               help='File with precision GPS (not accepted here: run `impproc geolocate` first; '
                                     'only the default, the GPS already in the file, is accepted)')
     parser_interp.add_argument('--offset', type=float, default=0.0, help='Offset from GPS time to radar time')
     parser_interp.add_argument('--minmove', type=float, default=1.0e-2, help='Minimum movement to not be stationary')
     parser_interp.add_argument('--extrapolate', action='store_true', help='Extrapolate GPS data beyond bounds')
     _add_def_args(parser_interp)
+
+    parser_geolocate = subparsers.add_parser('geolocate', help='GPS control')
+    parser_geolocate.set_defaults(func=geolocate, name='geolocate')
+    parser_geolocate.add_argument('gps_fn', type=str,
+                                  help='CSV or mat file containing the GPS information. .csv and .txt files are '
+                                       'assumed to be csv, .mat are mat.')
+    parser_geolocate.add_argument('--extrapolate', action='store_true', help='Extrapolate GPS data beyond bounds')
+    parser_geolocate.add_argument('--guess', action='store_true', help='Guess at offset')
+    _add_def_args(parser_geolocate)
     return parser
 
 
@@ -213,8 +226,8 @@ def main():
         for dat, fn in zip(radar_data, args.fns):
             vscan(dat, fn=fn, nfiles=len(radar_data), **vars(args))
         return
-    if args.name == 'interp':
-        interp(radar_data, **vars(args))
+    if args.name in ('interp', 'geolocate'):
+        args.func(radar_data, **vars(args))
     else:
         for dat in radar_data:
             args.func(dat, **vars(args))
@@ -359,11 +372,18 @@ def vscan(dat, vmin=1.5e8, vmax=1.9e8, nv=9, htaper=100, vtaper=1000, traces=Non
 
 
 def interp(dats, spacing, gps_fn=None, offset=0.0, minmove=1.0e-2, extrapolate=False, **kwargs):
-    """Move data to constant spacing (the reference's ``gpslib.interp`` without external GPS control)."""
+    """Move data to constant spacing (the reference's ``gpslib.interp`` without a GPS file: ``impproc geolocate`` attaches
+    one)."""
     if gps_fn is not None:
-        raise NotImplementedError('kinematic GPS control (--gps_fn) is not part of the MI355X migration engine')
+        raise NotImplementedError('impproc interp does not take --gps_fn: run `impproc geolocate` with the file first, '
+                                  'then `impproc interp` on its output')
     for dat in dats:
         dat.constant_space(spacing, min_movement=minmove)
+
+
+def geolocate(dats, gps_fn, extrapolate=False, guess=False, **kwargs):
+    """Attach precision GPS."""
+    interpdeep(dats, spacing=None, fn=gps_fn, extrapolate=extrapolate, guess_offset=guess)
 
 
 if __name__ == '__main__':

@@ -171,6 +171,22 @@ class RadarData(object):
         if getattr(self, 'data_dtype', None) is None:
             self.data_dtype = _resident_dtype(self)
 
+    def get_projected_coords(self, t_srs=None):
+        """``x_coord``, ``y_coord`` and ``dist`` (km) from ``lat`` / ``long`` (the reference's ``RadarData/__init__.py:333-354``):
+        through ``t_srs`` (a string GDAL accepts, e.g. EPSG:3031), else the object's own ``t_srs``, else the UTM zone of the
+        mean position.  Needs GDAL, as in the reference."""
+        from .. import gpslib
+        if t_srs is not None:
+            transform, self.t_srs = gpslib.get_conversion(t_srs=t_srs)
+        elif self.t_srs is not None:
+            transform, _ = gpslib.get_conversion(t_srs=self.t_srs)
+        else:
+            transform, self.t_srs = gpslib.get_utm_conversion(np.nanmean(self.lat), np.nanmean(self.long))
+        pts = np.array(transform(np.vstack((self.long, self.lat)).transpose()))
+        self.x_coord, self.y_coord = pts[:, 0], pts[:, 1]
+        self.dist = np.zeros((len(self.y_coord), ))
+        self.dist[1:] = np.cumsum(np.sqrt(np.diff(self.x_coord) ** 2.0 + np.diff(self.y_coord) ** 2.0)) / 1000.0
+
     def save(self, fn):
         """Write a StoDeep/ImpDAR ``.mat``; ``data`` is cast back to the dtype
         it was loaded with (NaN-aware for integer files)."""

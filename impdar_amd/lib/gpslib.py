@@ -5,7 +5,13 @@ the results equal the reference's bit for bit.
 
 Without GDAL (``osgeo`` / ``osr``) ``conversions_enabled`` is False, as in the reference: projected coordinates are then
 the reference's spherical guess (``y = 110000 lat``, ``x = 110000 lon |cos lat|``) and the conversion helpers raise its
-``ImportError``.  ``kinematic_gps_control`` and ``interp`` are not part of this package.
+``ImportError``.
+
+``kinematic_gps_control`` (``:348-464``), ``kinematic_gps_mat``, ``kinematic_gps_csv`` and ``interp`` (``:467-595``) attach a
+precision GPS track to the traces.  Their time-offset search (``guess_offset``: 5 passes over 5001 or 1001 candidate
+offsets, each a re-interpolation of the whole track and two correlations) runs on the MI355X
+(``impdar_amd.gpstrack.cc_search``); everything else, the final interpolation included, is the reference's own host
+NumPy / SciPy calls.
 """
 import numpy as np
 from scipy.interpolate import interp1d
@@ -223,3 +229,144 @@ class RadarGPS(nmea_info):
         if conversions_enabled:
             self.get_utm()
         self.get_dist()
+
+
+# a list here collects (search_vals, cc_coeffs, chosen index) of every pass of the offset search, for tests and benchmarks
+_search_log = None
+
+
+def _gaps_to_nan(decday_interp, decday):
+    """``old_gps_gaps``: the trace times farther than a second from every fix become NaN (the reference's loop over
+    ``np.min(abs(dday - decday))``, through a sorted copy: the nearest fix is one of the two neighbours, so the distance
+    is the same float)."""
+    if len(decday) == 0 or np.any(np.isnan(decday)):
+        return                                       # (np.min of nothing raises there; a NaN fix makes every minimum NaN)
+    fixes = np.sort(decday)
+    right = np.searchsorted(fixes, decday_interp).clip(0, len(fixes) - 1)
+    left = (right - 1).clip(0, len(fixes) - 1)
+    nearest = np.minimum(np.abs(decday_interp - fixes[left]), np.abs(decday_interp - fixes[right]))
+    decday_interp[nearest > 1. / (24 * 3600.)] = np.nan
+
+
+def kinematic_gps_control(dats, lat, lon, elev, decday, offset=0.0, extrapolate=False, guess_offset=True,
+                          old_gps_gaps=False):
+    """New, better GPS data for ``lat``, ``long`` and ``elev`` of ``dats`` (one RadarData or a list), interpolated at the
+    traces' ``decday`` (the reference's ``gpslib.py:348-464``, same arguments and defaults).
+
+    ``offset`` translates the GPS times onto the radar's.  ``extrapolate`` fills traces outside the GPS record by
+    extrapolation instead of raising -- use with caution.  ``guess_offset`` searches the offset: 5 passes, each over
+    ``np.linspace(-0.1 |o|, 0.1 |o|, 1001)`` around the running offset ``o`` (``np.linspace(-0.1, 0.1, 5001)`` days when
+    it is zero), keeping the candidate whose interpolated track correlates best with the radar's own positions.  The
+    candidates of a pass are scored in one launch on the GPU, on the GPS arrays sorted once by a stable argsort of
+    ``decday`` (the reference re-sorts the shifted times for every candidate: fixes whose shifted times coincide only
+    after rounding are outside what is held to the reference).  A candidate that leaves a trace outside the GPS record
+    raises ``ValueError`` without ``extrapolate``, as the reference does at the first such candidate.
+    ``old_gps_gaps`` keeps the radar's own position wherever no fix lies within a second of the trace."""
+    fill_value = 'extrapolate' if extrapolate else np.nan
+    if type(dats) not in [list, tuple]:
+        dats = [dats]
+    for in_dat in [lat, lon, elev]:
+        if len(decday) != len(in_dat):
+            raise IndexError('lat, lon, elev, and decday must be the same len')
+    offsets = [offset for i in dats]
+    if guess_offset:
+        from .. import gpstrack
+        print('CC search')
+        order = np.argsort(decday, kind='stable')
+        gps_t, gps_lat, gps_lon = np.asarray(decday)[order], np.asarray(lat)[order], (lon % 360)[order]
+        for j, dat in enumerate(dats):
+            decday_interp = dat.decday.copy()
+            if old_gps_gaps:
+                _gaps_to_nan(decday_interp, decday)
+                dat.lat[dat.lat == 0.] = np.nan
+                dat.long[dat.long == 0.] = np.nan
+                if np.all(np.isnan(decday_interp)):
+                    raise ValueError("Too much time offset")
+            for i in range(5):
+                if (min(lon % 360) - max(dat.long % 360)) > 0. or (min(dat.long % 360) - max(lon % 360)) > 0.:
+                    raise ValueError('No overlap in longitudes')
+                if offsets[j] != 0.0:
+                    search_vals = np.linspace(-0.1 * abs(offsets[j]), 0.1 * abs(offsets[j]), 1001)
+                else:
+                    search_vals = np.linspace(-0.1, 0.1, 5001)
+                cc_coeffs, outside = gpstrack.cc_search(gps_t, gps_lat, gps_lon, decday_interp, dat.lat, dat.long % 360,
+                                                        offsets[j], search_vals, extrapolate)
+                if not extrapolate and np.any(outside > 0):
+                    first = int(np.argmax(outside > 0))
+                    raise ValueError('{:d} trace times are outside the GPS record at the candidate offset {:f}: the '
+                                     'interpolation range does not cover the search window'.format(
+                                         int(outside[first]), offsets[j] + search_vals[first]))
+                best = np.argmax(cc_coeffs)
+                if _search_log is not None:
+                    _search_log.append((search_vals, cc_coeffs, int(best)))
+                offsets[j] += search_vals[best]
+                print('Maximum correlation at offset: {:f}'.format(offsets[j]))
+
+    for j, dat in enumerate(dats):
+        decday_interp = dat.decday.copy()
+        lat_interpolator = interp1d(decday + offsets[j], lat, kind='linear', fill_value=fill_value)
+        long_interpolator = interp1d(decday + offsets[j], lon % 360, kind='linear', fill_value=fill_value)
+        elev_interpolator = interp1d(decday + offsets[j], elev, kind='linear', fill_value=fill_value)
+        if old_gps_gaps:
+            # (again: otherwise the traces off the record are out of bounds)
+            _gaps_to_nan(decday_interp, decday)
+            lat_interp = lat_interpolator(decday_interp)
+            long_interp = long_interpolator(decday_interp)
+            elev_interp = elev_interpolator(decday_interp)
+            gaps = np.isnan(decday_interp)
+            lat_interp[gaps] = dat.lat[gaps]
+            long_interp[gaps] = dat.long[gaps]
+            elev_interp[gaps] = dat.elev[gaps]
+            dat.lat = lat_interp
+            dat.long = long_interp % 360
+            dat.elev = elev_interp
+        else:
+            dat.lat = lat_interpolator(decday_interp)
+            dat.long = long_interpolator(decday_interp)
+            dat.elev = elev_interpolator(decday_interp)
+        if conversions_enabled:
+            dat.get_projected_coords()
+
+
+def kinematic_gps_mat(dats, mat_fn, offset=0.0, extrapolate=False, guess_offset=False, old_gps_gaps=False):
+    """:func:`kinematic_gps_control` with ``lat``, ``long``, ``elev`` and ``decday`` of a matlab file."""
+    from scipy.io import loadmat
+    mat = loadmat(mat_fn)
+    for val in ['lat', 'long', 'elev', 'decday']:
+        if val not in mat:
+            raise ValueError('{:s} needs to be contained in matlab input file'.format(val))
+    kinematic_gps_control(dats, mat['lat'].flatten(), mat['long'].flatten(), mat['elev'].flatten(),
+                          mat['decday'].flatten(), offset=offset, extrapolate=extrapolate, guess_offset=guess_offset,
+                          old_gps_gaps=old_gps_gaps)
+
+
+def kinematic_gps_csv(dats, csv_fn, offset=0, names='decday,long,lat,elev', extrapolate=False, guess_offset=False,
+                      old_gps_gaps=False, **genfromtxt_flags):
+    """:func:`kinematic_gps_control` with the columns of a csv file read by ``numpy.genfromtxt``: ``names`` (a
+    comma-separated string, a list, or True to read them from the file) must contain 'decday', 'long', 'lat' and
+    'elev'; further keywords go to ``genfromtxt``."""
+    data = np.genfromtxt(csv_fn, names=names, **genfromtxt_flags)
+    kinematic_gps_control(dats, data['lat'].flatten(), data['long'].flatten(), data['elev'].flatten(),
+                          data['decday'].flatten(), offset=offset, extrapolate=extrapolate, guess_offset=guess_offset,
+                          old_gps_gaps=old_gps_gaps)
+
+
+def interp(dats, spacing=None, fn=None, fn_type=None, offset=0.0, min_movement=1.0e-2, genfromtxt_kwargs={},
+           extrapolate=False, guess_offset=False, **kwargs):
+    """Kinematic GPS control from ``fn`` (a mat or csv file with lat, long, elev and decday; ``fn_type`` 'mat' or 'csv',
+    else by extension; None: no control), then every radargram to constant ``spacing`` in metres (None: none).  A file
+    without ``dist`` first takes its positions from its own GPS.  ``min_movement`` culls stationary traces."""
+    if fn is not None:
+        if fn_type == 'mat' or ((fn_type is None) and (fn[-4:] == '.mat')):
+            kinematic_gps_mat(dats, fn, offset=offset, extrapolate=extrapolate, guess_offset=guess_offset)
+        elif fn_type == 'csv' or (fn_type is None and fn[-4:] in ['.csv', '.txt']):
+            kinematic_gps_csv(dats, fn, offset=offset, extrapolate=extrapolate, guess_offset=guess_offset,
+                              **genfromtxt_kwargs)
+        else:
+            raise ValueError('Cannot identify fn filetype, must be mat or csv')
+    if spacing is not None:
+        for dat in dats:
+            if dat.dist is None:
+                kinematic_gps_control(dat, dat.lat, dat.long, dat.elev, dat.decday, extrapolate=extrapolate,
+                                      guess_offset=False)
+            dat.constant_space(spacing, min_movement=min_movement)

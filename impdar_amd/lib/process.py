@@ -61,8 +61,8 @@ def process(RadarDataList, interp=None, vbp=None, ahfilt=None, denoise=None, mig
         except (ValueError, TypeError, IndexError):
             raise ValueError('interp must be a target spacing (float) then a gps filename')
         if interp[1] is not None:
-            raise NotImplementedError('kinematic GPS control (a gps filename for interp) is not part of the '
-                                      'MI355X migration engine')
+            raise NotImplementedError('process() does not take a gps filename for interp: attach the track with '
+                                      'gpslib.interp / `impproc geolocate` first')
     if ahfilt is False or (isinstance(ahfilt, (int, np.integer)) and ahfilt == 0):
         ahfilt = None                 # the reference's `if ahfilt:`
     if ahfilt is not None:

@@ -716,6 +716,40 @@ int impdar_rawload_dev(impdar_ctx *ctx, const void *d_raw, long long nbytes, lon
 int impdar_rawload(impdar_ctx *ctx, const void *raw_host, long long nbytes, long long base, long long stride, long long head,
                    int snum, int tnum, int in_kind, int op, int out_kind, void *d_out);
 
+/* ---- the time-offset search of kinematic GPS control (csrc/gpstrack.hip, csrc/gps_route.h) ----
+ * gpslib.py:420-427 of the reference for `ncand` candidate offsets at once.  All
+ * arrays are HOST float64.  gps_t (non-decreasing, no NaN), gps_lat, gps_lon:
+ * the `ngps` fixes; t, lat, lon: the `tnum` traces' decimal day, radar latitude
+ * and radar longitude % 360.  For candidate c the fixes' times are
+ *   x[k] = (gps_t[k] + search[c]) + base        (float64, in that order)
+ * and the track is interpolated to every t[j] as SciPy's interp1d(kind='linear')
+ * does it, bit for bit:
+ *   extrapolate == 0  np.interp: bracket x[j] <= t < x[j+1]; y[j] where t == x[j]
+ *     or j is the last fix, else slope (t - x[j]) + y[j] with NumPy's NaN
+ *     fallback from the other knot.  A non-NaN t outside [x[0], x[ngps-1]] counts
+ *     into nout[c] and takes no part in the sums (the reference raises there);
+ *   extrapolate == 1  interp1d._call_linear: idx = searchsorted(x, t, 'left')
+ *     clipped to [1, ngps-1], ((y_hi - y_lo) / (x_hi - x_lo)) (t - x_lo) + y_lo;
+ *     nout[c] = 0.
+ * Duplicate x give what IEEE gives.  cc[c] = r(lat_i, lat) + r(lon_i, lon), r
+ * the Pearson correlation over the pairs where neither value is NaN (latitude and
+ * longitude masked separately): means first, then sum dx dy / sqrt(sum dx^2
+ * sum dy^2), clipped to [-1, 1]; fewer than 2 pairs or a zero variance: NaN.
+ * float64 sums whose order depends on the trace index alone, no atomics: two calls
+ * return the same bits.  probe = c >= 0 also writes candidate c's interpolated
+ * latitude and longitude (tnum each, NaN where the trace was left out).
+ * IMPDAR_ERR_ARG before any device work: ngps < 2, tnum < 1, ncand < 1, extrapolate
+ * not 0 or 1, a decreasing or NaN gps_t, probe >= ncand, sizes whose products
+ * overflow 64 bits or more candidates than a launch has workgroups (2^31 - 1).
+ * impdar_gps_cc_plan: the checks on the sizes alone, *scratch_bytes = the device
+ * bytes of the call; no context, no device.
+ * impdar_ctx_last_kernel_ms after impdar_gps_cc gives the search kernel alone. */
+int impdar_gps_cc_plan(long long ngps, long long tnum, long long ncand, int extrapolate, long long *scratch_bytes);
+int impdar_gps_cc(impdar_ctx *ctx, const double *gps_t, const double *gps_lat, const double *gps_lon, long long ngps,
+                  const double *t, const double *lat, const double *lon, long long tnum, double base, const double *search,
+                  long long ncand, int extrapolate, double *cc, long long *nout, long long probe, double *probe_lat,
+                  double *probe_lon);
+
 /* ---- what a plot reads from the radargram (csrc/display.hip) ----
  * data: (snum, tnum) float32 / float64, row-major; a window is rows [y0, y1),
  * traces [x0, x1) of it, 0 <= y0 <= y1 <= snum, 0 <= x0 <= x1 <= tnum.
