@@ -1579,6 +1579,81 @@ def main():
                                    "speedup_over_device_calls": per * (5001 + 4 * 1001) * 1e3 / float(np.median(walls.sum(axis=1)))}
         print(json.dumps(out), flush=True)
 
+    if 'atten' not in args.skip:
+        # the window search of attenuation method 3: the pick of the decided fixtures (tests/analysis_ref.recipe) at 10000
+        # traces, 30 rates, win_init = win_step = 100.  The kernel alone from events for the default target, for Nh_target 0 and
+        # for Nh_target -1 (every window of every trace is visited: the worst case), the public call on the host clock, and the reference's loop
+        # restated in NumPy (tests/analysis_ref.search) on one core at a reduced trace count, scaled
+        import ctypes
+        import os
+        from impdar_amd import attsearch
+        from impdar_amd.lib.analysis import attenuation
+        # the one-core yardstick is the tests' restatement of the reference's loop (tests/analysis_ref.py), as for the GPS line:
+        # one text of it in the repository, held to the reference's fixtures by tests/test_analysis_cpu.py
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+        import analysis_ref
+        tnum, ns = 10000, np.arange(30.)
+        ctx, lib = _hip.context(), _hip.load()
+        z_m, power = analysis_ref.recipe(tnum, 21)
+        z, pc = analysis_ref.prepared(z_m, power)
+
+        def kernel(nh_target):
+            out = attsearch.search_dev(attsearch.INDEX, z, pc, ns, 0.1, nh_target, 100, 100, first=50, ncent=tnum - 100)
+            ms = ctypes.c_float()
+            _hip.check(lib.impdar_ctx_last_kernel_ms(ctx, ctypes.byref(ms)), 'impdar_ctx_last_kernel_ms')
+            return out, ms.value
+
+        def stat(v):
+            return {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)), "reps": int(len(v))}
+
+        class Bag(object):
+            pass
+
+        dat, dat.picks = Bag(), Bag()
+        dat.tnum, dat.picks.z, dat.picks.corrected_power = tnum, z_m[None, :], power[None, :]
+        kernel(1.)
+        reps = max(args.reps, 5)
+        default, zero, worst, walls = [kernel(1.) for _ in range(reps)], [kernel(0.) for _ in range(reps)], [kernel(-1.) for _ in range(reps)], []
+        for _ in range(reps):
+            a = time.perf_counter()
+            rates, widths = attenuation.attenuation_method3(dat, 0)
+            walls.append((time.perf_counter() - a) * 1e3)
+        windows = lambda win: float(np.sum((win - 100.) / 100.))            # (the width after the last increment counts them)
+        visits = lambda win: float(np.sum(50. * ((win - 100.) / 100.) * ((win - 100.) / 100. + 1.)))
+        out = {"path": "attenuation window search 10000 traces, 30 rates",
+               "config": "method 3, float64, win_init = win_step = 100, Cw 0.1; one workgroup of 256 threads per trace, a thread per "
+                         "rate and eighth of the window, the window staged through LDS in tiles of 1024 pairs, the reference's passes",
+               "device_ms": stat([k for _, k in default]), "device_ms_target_0": stat([k for _, k in zero]),
+               "device_ms_every_window": stat([k for _, k in worst]),
+               "call_ms": stat(walls),
+               "windows_visited": windows(default[0][0][1]), "windows_visited_target_0": windows(zero[0][0][1]),
+               "windows_visited_every_window": windows(worst[0][0][1]),
+               "element_visits": visits(default[0][0][1]), "element_visits_target_0": visits(zero[0][0][1]),
+               "element_visits_every_window": visits(worst[0][0][1]),
+               "stopped_before_the_edge": float(np.mean((widths[50:tnum - 50] // 2 <= np.arange(50, tnum - 50)) &
+                                                        (widths[50:tnum - 50] // 2 <= tnum - np.arange(50, tnum - 50)))),
+               "note": "device_ms: the search kernel alone from events on the stream, Nh_target 1 (default), 0 (a walk still ends "
+                       "where a single rate lies below Cw) and -1 (every window of every trace: the worst case); call_ms: attenuation_method3 on the host clock (dB, NaN removal, upload, kernel, download, the "
+                       "loop over the outcomes); element_visits: window elements summed over the windows visited, each of them "
+                       "read once per rate"}
+        if not args.no_cpu:
+            small = 1000
+            zs, ps = analysis_ref.prepared(*analysis_ref.recipe(small, 21))
+            a = time.perf_counter()
+            analysis_ref.search(analysis_ref.INDEX, zs, ps, ns, 0.1, 1., 100, 100, range(50, small - 50), count=small)
+            sec = time.perf_counter() - a
+            ws = np.array([analysis_ref.walk(analysis_ref.INDEX, zs, ps, ns, 0.1, 1., 100, 100, tr)['win'] for tr in range(50, small - 50, 30)])
+            per_visit = sec / (visits(ws) * (small - 100) / len(ws))
+            out["cpu_baseline"] = {"what": "the reference's loop restated in NumPy (tests/analysis_ref.search: Python's sum over the "
+                                           "window, three passes per rate), one core, timed at %d traces; extrapolated to 10000 traces by "
+                                           "the element visits of the device run" % small,
+                                   "s_at_%d_traces" % small: sec,
+                                   "s_extrapolated": per_visit * out["element_visits"],
+                                   "s_extrapolated_target_0": per_visit * out["element_visits_target_0"],
+                                   "s_extrapolated_every_window": per_visit * out["element_visits_every_window"],
+                                   "speedup_over_call_extrapolated": per_visit * out["element_visits"] * 1e3 / float(np.median(walls))}
+        print(json.dumps(out), flush=True)
+
 
 if __name__ == '__main__':
     main()

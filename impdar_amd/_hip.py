@@ -143,6 +143,9 @@ SIGNATURES = {
     'impdar_rawload': (_i, [_p, _p, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _p]),
     'impdar_gps_cc_plan': (_i, [_ll, _ll, _ll, _i, C.POINTER(_ll)]),
     'impdar_gps_cc': (_i, [_p, _dp, _dp, _dp, _ll, _dp, _dp, _dp, _ll, _d, _dp, _ll, _i, _dp, C.POINTER(_ll), _ll, _dp, _dp]),
+    'impdar_att_search_plan': (_i, [_i, _ll, _ll, _ll, _d, _d, _ll, _ll, C.POINTER(_ll)]),
+    'impdar_att_search': (_i, [_p, _i, _dp, _dp, _ll, _dp, _ll, _ll, _dp, _ll, _ll, _d, _d, _d, _d, C.POINTER(_ll), _dp, _ip, _ll, _dp, _ll,
+                               C.POINTER(_ll)]),
     'impdar_auto_pick': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_auto_pick_dev': (_i, [_p, _p, _i, _i, _i, _i, _ip, _ip, _i, _i, _i, _i, _dp, _ip]),
     'impdar_pick_guided': (_i, [_p, _p, _i, _i, _i, _i, _i, _ip, _i, _i, _i, _i, _dp, _ip]),

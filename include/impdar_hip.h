@@ -750,6 +750,54 @@ int impdar_gps_cc(impdar_ctx *ctx, const double *gps_t, const double *gps_lat, c
                   long long ncand, int extrapolate, double *cc, long long *nout, long long probe, double *probe_lat,
                   double *probe_lon);
 
+/* ---- the window search of the attenuation methods 3 and 6b (csrc/attsearch.hip, csrc/att_route.h) ----
+ * analysis/attenuation.py of the reference: attenuation_method3 (flavour 0, index
+ * windows) and attenuation_method6b (flavour 1, depth windows) for `ncent` centres
+ * in one launch.  All arrays are HOST; float64 throughout.  z, pc: the `n` NaN-free
+ * (depth in km, 10 log10 corrected power) pairs -- of one pick in trace order
+ * (flavour 0), or of the pooled picks sorted by z, non-decreasing (flavour 1).  ns:
+ * the `nn` candidate rates, ns[j0] == 0.  A centre walks nested windows:
+ *   flavour 0  centre b is trace tr = first + b; the window of width `win` is
+ *     [tr - win/2, tr + win/2) (integer division), visited while win/2 <= tr and
+ *     win/2 <= n - tr; then win += win_step.  win_init >= 2, win_step >= 1, both
+ *     integers handed over as doubles;
+ *   flavour 1  centre b is the depth d = centres[b]; the window is the contiguous
+ *     range with |z - d| < win/2 evaluated in float64, visited while
+ *     d - win/2 >= z[0] and d + win/2 <= z[n-1]; then win += win_step, a repeated
+ *     float64 addition.
+ * At each window, for every rate N = ns[j]: pa = pc + 2 z N and
+ *   C[j] = |sum (z - mean z)(pa - mean pa) / (sqrt(sum (z - mean z)^2) sqrt(sum (pa - mean pa)^2))|;
+ * Cm = min C; if Cm < cw and C[j0] > cw then Nh = max ns[C < cw] - min ns[C < cw]
+ * (halved for flavour 1).  The walk ends when Nh <= nh_target (Nh starts at
+ * nh_target + 1) or the next window leaves the record.  Per centre:
+ *   code 0  idx = the j of the minimum of the last window visited;
+ *   code 1  no window was visited (idx = -1);
+ *   code 2  that minimum is attained by more than one rate (idx = the first);
+ *   code 3  a window was empty or held a C that is NaN or Inf: the walk stopped
+ *           there and the caller decides (NumPy's comparison rules are not restated);
+ *   win = the width after the last increment (win_init for code 1).
+ * The sums have a fixed order per window, no atomics: two calls return the same
+ * bits.  probe = b >= 0 also writes the C rows of every window centre b visited
+ * to probe_c (row-major, nn per row, at most probe_cap rows) and their number to
+ * *probe_rows (which may exceed probe_cap).
+ * IMPDAR_ERR_ARG before any device work: n, nn or ncent < 1, a flavour other than
+ * 0 / 1, win_init < 2 or win_step < 1 or a fraction (flavour 0), a width or step
+ * that is not positive and finite (flavour 1), j0 outside [0, nn), first < 0,
+ * a decreasing, NaN or infinite z (flavour 1), a flavour 1 walk that could not end
+ * -- win_step so small that 2 (z[n-1] - z[0]) + win_step / 2 == 2 (z[n-1] - z[0]), or
+ * (z[n-1] - z[0]) / win_step above 2^20 --, probe >= ncent or probe_cap < 1 with a probe,
+ * sizes whose products overflow 64 bits, more centres than a launch has
+ * workgroups (2^31 - 1).
+ * impdar_att_search_plan: the checks on the sizes alone, *scratch_bytes = the
+ * device bytes of the call; no context, no device.
+ * impdar_ctx_last_kernel_ms after impdar_att_search gives the search kernel alone. */
+int impdar_att_search_plan(int flavour, long long n, long long nn, long long ncent, double win_init, double win_step,
+                           long long probe, long long probe_cap, long long *scratch_bytes);
+int impdar_att_search(impdar_ctx *ctx, int flavour, const double *z, const double *pc, long long n, const double *ns,
+                      long long nn, long long j0, const double *centres, long long first, long long ncent, double win_init,
+                      double win_step, double cw, double nh_target, long long *idx, double *win, int *code,
+                      long long probe, double *probe_c, long long probe_cap, long long *probe_rows);
+
 /* ---- what a plot reads from the radargram (csrc/display.hip) ----
  * data: (snum, tnum) float32 / float64, row-major; a window is rows [y0, y1),
  * traces [x0, x1) of it, 0 <= y0 <= y1 <= snum, 0 <= x0 <= x1 <= tnum.
