@@ -297,6 +297,68 @@ def main():
                          "roofline": {"bound": "hbm", "achieved": algo / t / 1e6, "peak": 8000.0, "unit": "GB/s", "frac": algo / t / 1e6 / 8000.0}}
         rec["power_of_two_record_ns_per_sample"] = 0.27e6 / 4096 ** 2         # config 2: 0.27 ms at 4096 x 4096
         print(json.dumps(rec), flush=True)
+    if 'fk' not in args.skip:
+        # The f-k fan filter, resident, at config 2 and at the headline radargram's shape, against impdar_stolt_dev at the same
+        # size in the same run (the same passes with the stretch in the middle), the calls alternated after warm-up; device
+        # times from the HIP events of each call, the fan kernel alone from the pair around it (metrics line: kernel_ms); its
+        # bytes are one read and one write of the half spectrum; NumPy fft2 / ifft2 with a ready weight on one core.
+        import ctypes
+        from impdar_amd import fk as fklib
+        ctx, lib = _hip.context(), _hip.load()
+        buf = ctypes.create_string_buffer(1024)
+
+        def last():
+            _hip.check(lib.impdar_ctx_last_metrics(ctx, buf, len(buf)), 'metrics')
+            return json.loads(buf.value.decode())
+        for snum, tnum in ((args.stolt, args.stolt), FIELD):
+            geo = synth.geometry(snum, tnum)
+            xf = rng.standard_normal((snum, tnum)).astype(np.float32)
+            d_x = _hip.DeviceArray.from_host(ctx, xf)
+            d_o = _hip.DeviceArray(ctx, (snum, tnum), np.float32)
+            kx = 2. * np.pi * np.fft.fftfreq(tnum, d=float(np.mean(geo['trace_int'])))
+            ws = 2. * np.pi * np.fft.rfftfreq(snum, d=geo['dt'])
+            v0 = float(np.mean(geo['trace_int'])) / geo['dt']
+            fan = fklib.check_fan((snum, tnum), va_lo=0.8 * v0, va_hi=5.0 * v0, taper=0.2)
+
+            def call(which):
+                if which == 'fk':
+                    fklib.fan_dev(d_x, kx, ws, fan, out=d_o)
+                else:
+                    _hip.check(lib.impdar_stolt_dev(ctx, d_x.ptr, _hip.F32, snum, tnum, _hip.as_dp(kx)[1], _hip.as_dp(ws)[1], 1.68e8, 100., 1000.,
+                                                    d_o.ptr), 'impdar_stolt_dev')
+                return last()
+            ms, kms, kernels = {'fk': [], 'stolt': []}, [], {}
+            for which in ('fk', 'stolt'):
+                for _ in range(2):
+                    kernels[which] = call(which)['kernel']
+            finite = bool(np.isfinite(d_o.to_host()).all())
+            for _ in range(max(10, args.reps)):
+                for which in ('fk', 'stolt'):
+                    m = call(which)
+                    ms[which].append(m['device_ms'])
+                    if which == 'fk':
+                        kms.append(m['kernel_ms'])
+            d_x.free()
+            d_o.free()
+            on_rows = 'fk_fan_rows' in kernels['fk']
+            half = (tnum // 2 + 1) * snum if on_rows else (snum // 2 + 1) * tnum
+            fan_bytes = 2 * half * 8
+            cb = None
+            if not args.no_cpu:
+                M = np.ones((snum, tnum), dtype=np.float32)
+                t0 = time.perf_counter()
+                np.fft.ifft2(M * np.fft.fft2(xf)).real
+                cb = {"seconds": time.perf_counter() - t0, "kind": "numpy", "cores": 1, "sample": "numpy.fft fft2 / ifft2, weight ready, one process"}
+            t, tk, ts = float(np.median(ms['fk'])), float(np.median(kms)), float(np.median(ms['stolt']))
+            print(json.dumps({"path": "fk fan %d x %d float32" % (snum, tnum), "config": "%dx%d float32, resident" % (snum, tnum),
+                              "kernel": kernels['fk'], "finite": finite, "device_ms": t, "device_ms_spread": max(ms['fk']) - min(ms['fk']),
+                              "device_ms_all": ms['fk'],
+                              "fan_kernel": {"ms": tk, "ms_spread": max(kms) - min(kms), "bytes": fan_bytes,
+                                             "roofline": {"bound": "hbm", "achieved": fan_bytes / tk / 1e6, "peak": 8000.0, "unit": "GB/s",
+                                                          "frac": fan_bytes / tk / 1e6 / 8000.0}},
+                              "stolt_same_run": {"kernel": kernels['stolt'], "device_ms": ts, "device_ms_spread": max(ms['stolt']) - min(ms['stolt']),
+                                                 "device_ms_all": ms['stolt']},
+                              "fk_over_stolt": t / ts, "cpu_baseline": cb}), flush=True)
     if 'vscan' not in args.skip:
         # The Stolt velocity scan at config 2, resident: 32 velocities in one impdar_stolt_scan_dev call against what a user does
         # without it -- 32 impdar_stolt_dev calls, each image downloaded and reduced to the same three sums per row in NumPy.

@@ -74,7 +74,11 @@ SIGNATURES = {
     'impdar_stolt_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _d, _d, _d, _p]),
     'impdar_stolt_scan_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _dp, _i, _d, _d, _i, _i, _i, _dp, _i, _p]),
     'impdar_stolt_scan': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _dp, _i, _d, _d, _i, _i, _i, _dp, _i, _p]),
-    'impdar_fft_rows_dev': (_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
+    'impdar_fk_fan': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _d, _d, _d, _i, _i, _p]),
+    'impdar_fk_fan_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _d, _d, _d, _i, _i, _p]),
+    'impdar_fk_power': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _dp]),
+    'impdar_fk_power_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _p]),
+    'impdar_fft_rows_dev':(_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_fft_rows_any_dev': (_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_phaseshift': (_i, [_p, _p, _i, _i, _i, _i, _dp, _dp, _d, _dp, _d, _dp, _i, _d, _d, _p]),
     'impdar_phaseshift_dev': (_i, [_p, _p, _i, _i, _i, _i, _dp, _dp, _d, _dp, _d, _dp, _i, _d, _d, _p]),

@@ -1,7 +1,7 @@
 #! /usr/bin/env python
 # -*- coding: utf-8 -*-
 """``impplot``: ``rg``, ``traces``, ``power``, ``ft``, ``hft`` and ``spectrogram``, with the reference's option names
-(``src/impdar/bin/impplot.py``).  What reads the whole radargram -- colour limits, the flattened image, the spectra -- is
+(``src/impdar/bin/impplot.py``), and ``fk``, an extension: the f-k power spectrum in dB.  What reads the whole radargram -- colour limits, the flattened image, the spectra -- is
 computed on the MI355X (``impdar_amd/lib/plot.py``).
 
     python -m impdar_amd.bin.impplot rg [-s] [-o OUT] [--o_fmt png] [-dpi 300] [-xd] [-yd | -dualy] [-picks] [-clims LO HI]
@@ -11,6 +11,7 @@ computed on the MI355X (``impdar_amd/lib/plot.py``).
     python -m impdar_amd.bin.impplot ft ... files
     python -m impdar_amd.bin.impplot hft ... files
     python -m impdar_amd.bin.impplot spectrogram files FREQ_LOWER FREQ_UPPER [-window W] [-scaling spectrum|density]
+    python -m impdar_amd.bin.impplot fk ... files
 """
 import argparse
 import sys
@@ -36,6 +37,7 @@ def _get_args():
     power.add_argument('layer', type=int, help='Layer upon which to plot the power')
     _add_parser(subparsers, 'ft', 'Plot the power spectrum in the vertical', plot_ft)
     _add_parser(subparsers, 'hft', 'Plot the power spectrum in the horizontal', plot_hft)
+    _add_parser(subparsers, 'fk', '(extension) Plot the f-k power spectrum', plot_fk)
     spec = _add_parser(subparsers, 'spectrogram', 'Plot spectrogram for all traces', plot_spectrogram)
     spec.add_argument('freq_lower', type=float, help='Lower frequency bound')
     spec.add_argument('freq_upper', type=float, help='Upper frequency bound')
@@ -93,6 +95,12 @@ def plot_hft(fns=None, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat', **kw
     """Plot the power spectrum along the traces: where a horizontal filter belongs."""
     from ..lib import plot
     plot.plot(fns, s=s, o=o, ftype=o_fmt, dpi=dpi, filetype=in_fmt, hft=True)
+
+
+def plot_fk(fns=None, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat', **kwargs):
+    """(extension) Plot the f-k power spectrum: where the fan of ``impproc fk`` is chosen."""
+    from ..lib import plot
+    plot.plot(fns, s=s, o=o, ftype=o_fmt, dpi=dpi, filetype=in_fmt, fk=True)
 
 
 def plot_spectrogram(fns=None, freq_lower=None, freq_upper=None, window=None, scaling='spectrum', s=False, o=None,

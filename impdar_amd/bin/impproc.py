@@ -7,6 +7,8 @@ writes ``<name>_picked.mat``; the files come before the seed lists, which take e
 ``impproc vscan VMIN VMAX NV [--htaper --vtaper --traces T0 T1 --samples S0 S1 --gates G --migrate] files``, another
 extension, scans the focus of the Stolt image over NV velocities (``RadarData.velocity_scan``), prints and saves it
 (``<name>_vscan.mat``) and, with ``--migrate``, migrates at the best one (``<name>_migrated.mat``).
+``impproc fk [--va_lo V] [--va_hi V] [--taper T] [--mode pass|reject] [--dip both|down_right|down_left] files``, a third
+extension, is the f-k fan (dip) filter (``RadarData.fk_filter``) and writes ``<name>_fk.mat``.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
@@ -185,6 +187,19 @@ def _get_args():
                               help='Then migrate (stolt) at the best velocity and save <name>_migrated.mat')
     _add_def_args(parser_vscan)
 
+    parser_fk = subparsers.add_parser('fk', help='(extension) f-k fan (dip) filter: keep or remove the events whose '
+                                                 'apparent velocity lies between --va_lo and --va_hi')
+    parser_fk.set_defaults(func=fk, name='fk')
+    parser_fk.add_argument('--va_lo', type=float, default=None, help='Lowest apparent velocity of the fan (m/s along the profile)')
+    parser_fk.add_argument('--va_hi', type=float, default=None, help='Highest apparent velocity of the fan (m/s along the profile)')
+    parser_fk.add_argument('--taper', type=float, default=0.1,
+                           help='Relative half-width of the cosine taper in slowness around either edge, in [0, 1) (default 0.1)')
+    parser_fk.add_argument('--mode', type=str, default='pass', choices=['pass', 'reject'], help='Keep the fan or remove it')
+    parser_fk.add_argument('--dip', type=str, default='both', choices=['both', 'down_right', 'down_left'],
+                           help='Filter events that dip either way, or only those whose arrival time grows (down_right) or '
+                                'shrinks (down_left) with distance')
+    _add_def_args(parser_fk)
+
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
@@ -331,6 +346,11 @@ def agc(dat, window=50, scale_factor=50, **kwargs):
 def autopick(dat, snums=(), tnums=(), picknums=None, freq=None, pol=None, **kwargs):
     """(extension) Pick one layer per seed on the device and keep the picks for ``save``."""
     dat.pick_layers(snums, tnums, picknums=picknums, freq=freq, pol=pol)
+
+
+def fk(dat, va_lo=None, va_hi=None, taper=0.1, mode='pass', dip='both', **kwargs):
+    """(extension) f-k fan filter."""
+    dat.fk_filter(va_lo=va_lo, va_hi=va_hi, taper=taper, mode=mode, dip=dip)
 
 
 def _out_name(fn, o, nfiles, name):

@@ -22,7 +22,9 @@ spectra behind the reference's ``plot_ft``, ``plot_hft`` and
 ``plot_spectrogram``: ``vertical_spectrum``, ``horizontal_spectrum`` and
 ``spectrogram`` (``_RadarDataSpectra.py``; drawn by ``lib/plot.py``), and what
 its ``plot_radargram`` and ``plot_traces`` read: ``percentiles``, ``window``
-and ``flattened`` (``_RadarDataDisplay.py``).  Everything else in the
+and ``flattened`` (``_RadarDataDisplay.py``), and two extensions on the Stolt
+transforms: ``velocity_scan`` (``velscan.py``) and the f-k fan filter with its
+spectrum, ``fk_filter`` and ``fk_spectrum`` (``fk.py``).  Everything else in the
 reference's class (moving picks with the data, GPS, the ApRES plots) is out
 of scope.
 """
@@ -45,6 +47,7 @@ from ._RadarDataSpectra import vertical_spectrum as _vertical_spectrum
 from ._RadarDataDisplay import flattened as _flattened, percentiles as _percentiles, window as _window
 from ... import resident as _resident
 from ...velscan import stolt_velocity_scan as _velocity_scan
+from ...fk import fk_filter as _fk_filter, fk_spectrum as _fk_spectrum
 from ._resident import data_dtype as _resident_dtype, data_shape as _resident_shape
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -85,6 +88,8 @@ class RadarData(object):
     window = _window
     flattened = _flattened
     velocity_scan = _velocity_scan
+    fk_filter = _fk_filter
+    fk_spectrum = _fk_spectrum
     to_device = _resident.to_device
     from_device = _resident.from_device
 

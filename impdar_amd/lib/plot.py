@@ -36,7 +36,7 @@ def plot(fns, tr=None, s=False, ftype='png', dpi=300, xd=False, yd=False, dualy=
          hft=False, clims=None, cmap=None, flatten_layer=None, *args, **kwargs):
     """Load every file of ``fns`` and draw one kind of plot of each: the traces ``tr``, the power of pick ``power`` (all
     files on one axis), the vertical spectrum (``ft``), the horizontal spectrum (``hft``), the spectrogram (``spectra``,
-    the pair of frequency limits in MHz) or, when none of these is asked for, the radargram -- against the distance
+    the pair of frequency limits in MHz), the f-k spectrum (keyword ``fk``, an extension) or, when none of these is asked for, the radargram -- against the distance
     (``xd``), the depth (``yd``) or both time and depth (``dualy``), with picks in ``pick_colors``, colour limits
     ``clims``, colour map ``cmap`` (None: grey) and layer ``flatten_layer`` made flat.  Save next to the input with
     extension ``ftype`` (``s``) or show."""
@@ -61,6 +61,8 @@ def plot(fns, tr=None, s=False, ftype='png', dpi=300, xd=False, yd=False, dualy=
         figs = [plot_hft(dat) for dat in radar_data]
     elif spectra:
         figs = [plot_spectrogram(dat, spectra, window=window, scaling=scaling) for dat in radar_data]
+    elif kwargs.get('fk', False):
+        figs = [plot_fk(dat) for dat in radar_data]
     else:
         figs = [plot_radargram(dat, xdat=xdat, ydat=ydat, x_range=None, pick_colors=pick_colors, clims=clims, cmap=cmap,
                                flatten_layer=flatten_layer) for dat in radar_data]
@@ -400,4 +402,24 @@ def plot_spectrogram(dat, freq_limit=None, window=None, scaling='spectrum', fig=
     ax.set_xlabel('Trace Number')
     ax.set_ylabel('Frequency (MHz)')
     ax.set_title('PSD(tnum, f)')
+    return fig, ax
+
+
+def plot_fk(dat, fig=None, ax=None):
+    """(extension) Image of the f-k power spectrum in dB below its maximum, ``10 log10(P / max P)``: wavenumber in cycles
+    per metre against frequency in MHz -- where the fan of ``fk_filter`` is chosen."""
+    import matplotlib.pyplot as plt
+    freq_mhz, k_per_m, power = dat.fk_spectrum()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        db = 10.0 * np.log10(power / np.max(power))
+    fig, ax = _axes(fig, ax, (10, 7))
+    dk = (k_per_m[-1] - k_per_m[0]) / (len(k_per_m) - 1)
+    df = (freq_mhz[-1] - freq_mhz[0]) / (len(freq_mhz) - 1)
+    im = ax.imshow(db, origin='lower', aspect='auto', interpolation='nearest',
+                   extent=[k_per_m[0] - dk / 2.0, k_per_m[-1] + dk / 2.0, freq_mhz[0] - df / 2.0, freq_mhz[-1] + df / 2.0])
+    cbar = plt.colorbar(im, shrink=0.9, orientation='vertical', pad=0.03, ax=ax)
+    cbar.set_label('Power (dB below the maximum)')
+    ax.set_xlabel('Wavenumber (1/m)')
+    ax.set_ylabel('Frequency (MHz)')
+    ax.set_title('P(k, f)')
     return fig, ax

@@ -225,6 +225,33 @@ int impdar_stolt_scan(impdar_ctx *ctx, const void *data, int dtype, int snum, in
                       double htaper, double vtaper, int t0, int t1, int max_batch,
                       double *sums, int keep, void *keep_out);
 
+/* ---- f-k fan (dip) filter and f-k spectrum (csrc/fk.hip; an extension) ----------
+ * On the transforms and the cached plan of impdar_stolt (IMPDAR_STOLT_FFT chooses the route as there; a chain
+ * fk -> stolt at one size plans once), with both tapers off.  kx: tnum wavenumbers in numpy.fft.fftfreq order; ws: the
+ * snum/2 + 1 frequencies of numpy.fft.rfftfreq (the negative ones are their mirror).  snum, tnum >= 2, odd sizes included.
+ * impdar_fk_fan: out = Re ifft2(M * fft2(data)), (snum, tnum) of dtype (d_out may be d_data), M real, per element:
+ *   slowness p = 0 where |kx| == 0, else +inf where |w| == 0, else |kx| / |w|;
+ *   E(p; pc, taper) = 1 for p <= pc (1 - taper) (tested first), 0 for p >= pc (1 + taper), a raised cosine between;
+ *   W = E(p; 1/va_lo, taper) * (1 - E(p; 1/va_hi, taper)), a factor 1 for an edge that is NaN: apparent velocities
+ *   va_lo <= |w| / |kx| <= va_hi pass;  dip 0: both sides, 1 (down_right: arrival time grows with distance) keeps
+ *   w kx < 0, 2 (down_left) w kx > 0 -- elements with w kx == 0 or on a Nyquist row / column belong to both -- off the
+ *   side W = 0;  mode 0 (pass): M = W, 1 (reject): M = 1 - W.  The weight is evaluated in float64 for both dtypes.
+ *   ERR_ARG, before any device work: both edges NaN; an edge not finite and positive; taper outside [0, 1);
+ *   (1/va_hi) (1 + taper) > (1/va_lo) (1 - taper); snum < 2 or tnum < 2; another dtype, mode or dip.
+ * impdar_fk_power: out[j][i] = |fft2(data)[j][i]|^2 for the snum/2 + 1 rows w >= 0, the columns in fftshift order,
+ *   not normalised: (snum/2 + 1, tnum) float64 whatever dtype (the transforms run in dtype).
+ * Metrics: "kernel_ms" is the fan (or power) kernel alone; "planned": 1 when this call made plans or buffers. */
+int impdar_fk_fan(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum,
+                  const double *kx, const double *ws, double va_lo, double va_hi, double taper,
+                  int mode, int dip, void *out);
+int impdar_fk_fan_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
+                      const double *kx, const double *ws, double va_lo, double va_hi, double taper,
+                      int mode, int dip, void *d_out);
+int impdar_fk_power(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum,
+                    const double *kx, const double *ws, double *out);
+int impdar_fk_power_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
+                        const double *kx, const double *ws, void *d_out);
+
 /* ---- the library's own batched power-of-two row transforms (csrc/own_fft.h) ----
  * What the Stolt / phase-shift calls of power-of-two sizes run their transforms on (rocFFT compiles the kernels of
  * lengths above 1024 at run time: 0.25-3 s per plan, profiles/r05_first_call.txt).  numpy.fft conventions
