@@ -359,6 +359,90 @@ def main():
                               "stolt_same_run": {"kernel": kernels['stolt'], "device_ms": ts, "device_ms_spread": max(ms['stolt']) - min(ms['stolt']),
                                                  "device_ms_all": ms['stolt']},
                               "fk_over_stolt": t / ts, "cpu_baseline": cb}), flush=True)
+    if 'decon' not in args.skip:
+        # Predictive deconvolution at the headline radargram's shape, resident, out of place: oplen 32 and 256 at gap 8, design
+        # 'mean', and the autocorrelogram of 65 lags, the calls alternated after warm-up with a device copy of the radargram's
+        # bytes between them as the yardstick of the run; device and stage times from the HIP events of each call (metrics
+        # line).  Floors: (|lags| + oplen) fmas per sample against the float64 vector peak, three passes against HBM.
+        import ctypes
+        from impdar_amd import decon as dclib
+        ctx, lib = _hip.context(), _hip.load()
+        buf = ctypes.create_string_buffer(1024)
+        snum, tnum = FIELD
+        xf = rng.standard_normal((snum, tnum)).astype(np.float32)
+        d_x = _hip.DeviceArray.from_host(ctx, xf)
+        d_o = _hip.DeviceArray(ctx, (snum, tnum), np.float32)
+        PEAK_F64, PEAK_HBM = 78.6e12, 8.0e12
+        confs = {'oplen32': dict(oplen=32, gap=8, design='each'), 'oplen256': dict(oplen=256, gap=8, design='each'),
+                 'mean': dict(oplen=32, gap=8, design='mean'), 'acorr': dict(maxlag=64)}
+
+        def call(name):
+            c = confs[name]
+            if name == 'acorr':
+                dclib.acorr_dev(d_x, dclib.check_acorr((snum, tnum), c['maxlag']))
+            else:
+                dclib.decon_dev(d_x, dclib.check_decon((snum, tnum), c['oplen'], c['gap'], 0.1, None, c['design']), out=d_o)
+            _hip.check(lib.impdar_ctx_last_metrics(ctx, buf, len(buf)), 'metrics')
+            return json.loads(buf.value.decode())
+
+        def copy_ms():
+            # a device copy that moves the three passes' bytes (1.5 radargrams read, 1.5 written): ten enqueued back to back
+            # per sample, the host clock around them and one synchronise, so that the launches hide behind the copies
+            n64 = snum * tnum * 3 // 4
+            a, b = _hip.DeviceArray(ctx, (n64, 1), np.float64), _hip.DeviceArray(ctx, (n64, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, n64 * 8)
+            out = []
+            for _ in range(12):
+                lib.impdar_ctx_sync(ctx)
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(n64))
+                lib.impdar_ctx_sync(ctx)
+                out.append((time.perf_counter() - t0) * 100.0)
+            a.free()
+            b.free()
+            return out[2:]
+        ms = {k: [] for k in confs}
+        stages = {k: {'acorr_ms': [], 'solve_ms': [], 'apply_ms': []} for k in confs}
+        kernels = {}
+        for k in confs:
+            for _ in range(2):
+                kernels[k] = call(k)['kernel']
+        finite = bool(np.isfinite(d_o.to_host()).all())
+        for _ in range(max(10, args.reps)):
+            for k in confs:
+                m = call(k)
+                ms[k].append(m['device_ms'])
+                for s in stages[k]:
+                    if s in m:
+                        stages[k][s].append(m[s])
+        cp = copy_ms()
+        d_x.free()
+        d_o.free()
+        cb = None
+        if not args.no_cpu:
+            import os
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+            import decon_ref
+            t0 = time.perf_counter()
+            decon_ref.decon(xf[:, :100], 32, 8, 0.1, None, 'each', 'ref')
+            el = time.perf_counter() - t0
+            cb = {"seconds": el * tnum / 100.0, "kind": "numpy", "cores": 1,
+                  "sample": "NumPy / SciPy restatement (tests/decon_ref.py, ref) of oplen 32, gap 8 on 100 traces: %.3f s, extrapolated by trace count" % el}
+        for k, c in confs.items():
+            t = float(np.median(ms[k]))
+            nl = c['maxlag'] + 1 if k == 'acorr' else len(set(range(c['oplen'])) | set(range(c['gap'], c['gap'] + c['oplen'])))
+            fmas = snum * tnum * (nl + (0 if k == 'acorr' else c['oplen']))
+            nbytes = snum * tnum * 4 * (1 if k == 'acorr' else 3)
+            rec = {"path": "decon 4096 x 10000 float32" if k == 'oplen32' else "decon 4096 x 10000 float32, %s" % k,
+                   "config": "%dx%d float32, resident, %s" % (snum, tnum, ', '.join('%s=%s' % kv for kv in sorted(c.items()))),
+                   "kernel": kernels[k], "finite": finite, "device_ms": t, "device_ms_spread": max(ms[k]) - min(ms[k]), "device_ms_all": ms[k],
+                   "stages": {s: {"ms": float(np.median(v)), "ms_spread": max(v) - min(v)} for s, v in stages[k].items() if v},
+                   "fmas": fmas, "fma_floor_ms": 2 * fmas / PEAK_F64 * 1e3, "bytes": nbytes, "hbm_floor_ms": nbytes / 6.3e12 * 1e3,
+                   "frac_f64_vector_peak": 2 * fmas / (t * 1e-3) / PEAK_F64, "frac_hbm_peak": nbytes / (t * 1e-3) / PEAK_HBM,
+                   "copy_same_run": {"ms": float(np.median(cp)), "ms_spread": max(cp) - min(cp), "bytes": 3 * snum * tnum * 4},
+                   "cpu_baseline": cb if k == 'oplen32' else None}
+            print(json.dumps(rec), flush=True)
     if 'vscan' not in args.skip:
         # The Stolt velocity scan at config 2, resident: 32 velocities in one impdar_stolt_scan_dev call against what a user does
         # without it -- 32 impdar_stolt_dev calls, each image downloaded and reduced to the same three sums per row in NumPy.

@@ -78,6 +78,10 @@ SIGNATURES = {
     'impdar_fk_fan_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _d, _d, _d, _i, _i, _p]),
     'impdar_fk_power': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _dp]),
     'impdar_fk_power_dev': (_i, [_p, _p, _i, _i, _i, _dp, _dp, _p]),
+    'impdar_decon': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _dp]),
+    'impdar_decon_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _p]),
+    'impdar_acorr': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _dp]),
+    'impdar_acorr_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'impdar_fft_rows_dev':(_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_fft_rows_any_dev': (_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_phaseshift': (_i, [_p, _p, _i, _i, _i, _i, _dp, _dp, _d, _dp, _d, _dp, _i, _d, _d, _p]),

@@ -1,7 +1,7 @@
 #! /usr/bin/env python
 # -*- coding: utf-8 -*-
 """``impplot``: ``rg``, ``traces``, ``power``, ``ft``, ``hft`` and ``spectrogram``, with the reference's option names
-(``src/impdar/bin/impplot.py``), and ``fk``, an extension: the f-k power spectrum in dB.  What reads the whole radargram -- colour limits, the flattened image, the spectra -- is
+(``src/impdar/bin/impplot.py``), and two extensions: ``fk``, the f-k power spectrum in dB, and ``acorr``, the autocorrelogram.  What reads the whole radargram -- colour limits, the flattened image, the spectra -- is
 computed on the MI355X (``impdar_amd/lib/plot.py``).
 
     python -m impdar_amd.bin.impplot rg [-s] [-o OUT] [--o_fmt png] [-dpi 300] [-xd] [-yd | -dualy] [-picks] [-clims LO HI]
@@ -12,6 +12,7 @@ computed on the MI355X (``impdar_amd/lib/plot.py``).
     python -m impdar_amd.bin.impplot hft ... files
     python -m impdar_amd.bin.impplot spectrogram files FREQ_LOWER FREQ_UPPER [-window W] [-scaling spectrum|density]
     python -m impdar_amd.bin.impplot fk ... files
+    python -m impdar_amd.bin.impplot acorr [--maxlag L] ... files
 """
 import argparse
 import sys
@@ -38,6 +39,8 @@ def _get_args():
     _add_parser(subparsers, 'ft', 'Plot the power spectrum in the vertical', plot_ft)
     _add_parser(subparsers, 'hft', 'Plot the power spectrum in the horizontal', plot_hft)
     _add_parser(subparsers, 'fk', '(extension) Plot the f-k power spectrum', plot_fk)
+    acorr = _add_parser(subparsers, 'acorr', '(extension) Plot the autocorrelation of every trace', plot_acorr)
+    acorr.add_argument('--maxlag', type=int, default=None, help='Largest lag in samples (default: a quarter of the trace, at most 256)')
     spec = _add_parser(subparsers, 'spectrogram', 'Plot spectrogram for all traces', plot_spectrogram)
     spec.add_argument('freq_lower', type=float, help='Lower frequency bound')
     spec.add_argument('freq_upper', type=float, help='Upper frequency bound')
@@ -101,6 +104,12 @@ def plot_fk(fns=None, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat', **kwa
     """(extension) Plot the f-k power spectrum: where the fan of ``impproc fk`` is chosen."""
     from ..lib import plot
     plot.plot(fns, s=s, o=o, ftype=o_fmt, dpi=dpi, filetype=in_fmt, fk=True)
+
+
+def plot_acorr(fns=None, maxlag=None, s=False, o=None, o_fmt='png', dpi=300, in_fmt='mat', **kwargs):
+    """(extension) Plot the autocorrelogram: where ``--gap`` and ``--oplen`` of ``impproc decon`` are chosen."""
+    from ..lib import plot
+    return plot.plot(fns, s=s, o=o, ftype=o_fmt, dpi=dpi, filetype=in_fmt, acorr=True, maxlag=maxlag)
 
 
 def plot_spectrogram(fns=None, freq_lower=None, freq_upper=None, window=None, scaling='spectrum', s=False, o=None,

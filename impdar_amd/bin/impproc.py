@@ -9,6 +9,8 @@ extension, scans the focus of the Stolt image over NV velocities (``RadarData.ve
 (``<name>_vscan.mat``) and, with ``--migrate``, migrates at the best one (``<name>_migrated.mat``).
 ``impproc fk [--va_lo V] [--va_hi V] [--taper T] [--mode pass|reject] [--dip both|down_right|down_left] files``, a third
 extension, is the f-k fan (dip) filter (``RadarData.fk_filter``) and writes ``<name>_fk.mat``.
+``impproc decon --oplen N [--gap G] [--prewhiten P] [--window S0 S1] [--design each|mean] files``, a fourth, is predictive
+deconvolution (``RadarData.predictive_decon``) and writes ``<name>_decon.mat``.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
@@ -200,6 +202,18 @@ def _get_args():
                                 'shrinks (down_left) with distance')
     _add_def_args(parser_fk)
 
+    parser_decon = subparsers.add_parser('decon', help='(extension) predictive (gapped) deconvolution of every trace: '
+                                                       'shortens the wavelet, removes ringing and short-period multiples')
+    parser_decon.set_defaults(func=decon, name='decon')
+    parser_decon.add_argument('--oplen', type=int, required=True, help='Length of the prediction operator in samples (1 .. 256)')
+    parser_decon.add_argument('--gap', type=int, default=1, help='Prediction distance in samples (default 1: spiking deconvolution)')
+    parser_decon.add_argument('--prewhiten', type=float, default=0.1, help='Per cent of the zero lag added to it (default 0.1)')
+    parser_decon.add_argument('--window', type=int, nargs=2, default=None, metavar=('S0', 'S1'),
+                              help='Samples [S0, S1) the operator is designed on (default: the whole trace)')
+    parser_decon.add_argument('--design', type=str, default='each', choices=['each', 'mean'],
+                              help='An operator per trace, or one from the autocorrelations summed over the traces')
+    _add_def_args(parser_decon)
+
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
@@ -351,6 +365,11 @@ def autopick(dat, snums=(), tnums=(), picknums=None, freq=None, pol=None, **kwar
 def fk(dat, va_lo=None, va_hi=None, taper=0.1, mode='pass', dip='both', **kwargs):
     """(extension) f-k fan filter."""
     dat.fk_filter(va_lo=va_lo, va_hi=va_hi, taper=taper, mode=mode, dip=dip)
+
+
+def decon(dat, oplen=None, gap=1, prewhiten=0.1, window=None, design='each', **kwargs):
+    """(extension) predictive deconvolution."""
+    dat.predictive_decon(oplen, gap=gap, prewhiten=prewhiten, window=None if window is None else tuple(window), design=design)
 
 
 def _out_name(fn, o, nfiles, name):

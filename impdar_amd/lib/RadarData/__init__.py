@@ -24,7 +24,9 @@ spectra behind the reference's ``plot_ft``, ``plot_hft`` and
 its ``plot_radargram`` and ``plot_traces`` read: ``percentiles``, ``window``
 and ``flattened`` (``_RadarDataDisplay.py``), and two extensions on the Stolt
 transforms: ``velocity_scan`` (``velscan.py``) and the f-k fan filter with its
-spectrum, ``fk_filter`` and ``fk_spectrum`` (``fk.py``).  Everything else in the
+spectrum, ``fk_filter`` and ``fk_spectrum`` (``fk.py``), and a third along the
+traces: ``predictive_decon``, ``decon_operators`` and ``autocorrelation``
+(``decon.py``).  Everything else in the
 reference's class (moving picks with the data, GPS, the ApRES plots) is out
 of scope.
 """
@@ -48,6 +50,7 @@ from ._RadarDataDisplay import flattened as _flattened, percentiles as _percenti
 from ... import resident as _resident
 from ...velscan import stolt_velocity_scan as _velocity_scan
 from ...fk import fk_filter as _fk_filter, fk_spectrum as _fk_spectrum
+from ...decon import autocorrelation as _autocorrelation, decon_operators as _decon_operators, predictive_decon as _predictive_decon
 from ._resident import data_dtype as _resident_dtype, data_shape as _resident_shape
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -90,6 +93,9 @@ class RadarData(object):
     velocity_scan = _velocity_scan
     fk_filter = _fk_filter
     fk_spectrum = _fk_spectrum
+    predictive_decon = _predictive_decon
+    decon_operators = _decon_operators
+    autocorrelation = _autocorrelation
     to_device = _resident.to_device
     from_device = _resident.from_device
 

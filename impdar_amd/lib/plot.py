@@ -36,7 +36,8 @@ def plot(fns, tr=None, s=False, ftype='png', dpi=300, xd=False, yd=False, dualy=
          hft=False, clims=None, cmap=None, flatten_layer=None, *args, **kwargs):
     """Load every file of ``fns`` and draw one kind of plot of each: the traces ``tr``, the power of pick ``power`` (all
     files on one axis), the vertical spectrum (``ft``), the horizontal spectrum (``hft``), the spectrogram (``spectra``,
-    the pair of frequency limits in MHz), the f-k spectrum (keyword ``fk``, an extension) or, when none of these is asked for, the radargram -- against the distance
+    the pair of frequency limits in MHz), the f-k spectrum (keyword ``fk``, an extension), the autocorrelogram (keywords
+    ``acorr`` and ``maxlag``, an extension) or, when none of these is asked for, the radargram -- against the distance
     (``xd``), the depth (``yd``) or both time and depth (``dualy``), with picks in ``pick_colors``, colour limits
     ``clims``, colour map ``cmap`` (None: grey) and layer ``flatten_layer`` made flat.  Save next to the input with
     extension ``ftype`` (``s``) or show."""
@@ -63,6 +64,8 @@ def plot(fns, tr=None, s=False, ftype='png', dpi=300, xd=False, yd=False, dualy=
         figs = [plot_spectrogram(dat, spectra, window=window, scaling=scaling) for dat in radar_data]
     elif kwargs.get('fk', False):
         figs = [plot_fk(dat) for dat in radar_data]
+    elif kwargs.get('acorr', False):
+        figs = [plot_acorr(dat, maxlag=kwargs.get('maxlag', None)) for dat in radar_data]
     else:
         figs = [plot_radargram(dat, xdat=xdat, ydat=ydat, x_range=None, pick_colors=pick_colors, clims=clims, cmap=cmap,
                                flatten_layer=flatten_layer) for dat in radar_data]
@@ -422,4 +425,24 @@ def plot_fk(dat, fig=None, ax=None):
     ax.set_xlabel('Wavenumber (1/m)')
     ax.set_ylabel('Frequency (MHz)')
     ax.set_title('P(k, f)')
+    return fig, ax
+
+
+def plot_acorr(dat, maxlag=None, fig=None, ax=None):
+    """(extension) Image of the normalised autocorrelation of every trace, lag time in nanoseconds against trace number
+    -- where ``gap`` and ``oplen`` of ``predictive_decon`` are chosen: ringing and multiples are the bands below the zero
+    lag.  ``maxlag`` in samples (None: a quarter of the trace, at most 256)."""
+    import matplotlib.pyplot as plt
+    if maxlag is None:
+        maxlag = max(min(int(dat.snum) // 4, 256), 1) if dat.snum > 1 else 0
+    lag_s, A = dat.autocorrelation(maxlag)
+    fig, ax = _axes(fig, ax, (10, 7))
+    dl = float(dat.dt) * 1.0e9
+    im = ax.imshow(A, origin='upper', aspect='auto', interpolation='nearest', vmin=-1.0, vmax=1.0, cmap='RdBu_r',
+                   extent=[0.5, A.shape[1] + 0.5, lag_s[-1] * 1.0e9 + dl / 2.0, -dl / 2.0])
+    cbar = plt.colorbar(im, shrink=0.9, orientation='vertical', pad=0.03, ax=ax)
+    cbar.set_label('Autocorrelation / zero lag')
+    ax.set_xlabel('Trace number')
+    ax.set_ylabel('Lag (ns)')
+    ax.set_title('A(lag, tnum)')
     return fig, ax

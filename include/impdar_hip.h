@@ -252,6 +252,32 @@ int impdar_fk_power(impdar_ctx *ctx, const void *data, int dtype, int snum, int 
 int impdar_fk_power_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum,
                         const double *kx, const double *ws, void *d_out);
 
+/* ---- predictive (gapped, Wiener-Levinson) deconvolution and the autocorrelogram (csrc/decon.hip; an extension) ----
+ * The contract is csrc/decon_core.h; all arithmetic is float64 for both dtypes.  Per trace (column) x, over the design
+ * window [s0, s1): r[l] = sum_k x[k] x[k + l]; the symmetric Toeplitz system c[|m - i|] a[i] = r[gap + m], m < oplen, with
+ * c[0] = r[0] (1 + prewhiten / 100), by Levinson recursion; y[k] = x[k] - sum_i a[i] x[k - gap - i] over the whole trace
+ * (samples before its start are zero), rounded to dtype.  gap = 1: spiking deconvolution.
+ * design 0 (each): every trace its own operator; 1 (mean): one operator from the lags summed over the live traces, in a
+ *   fixed order.  A trace whose r[0] is not finite or not > 0, or whose recursion loses a finite positive error power, is
+ *   dead: it passes unchanged (NaN positions included) and its operator is zero.
+ * impdar_decon: out is (snum, tnum) of dtype (d_out may be d_data: the result is the out-of-place one bit for bit);
+ *   op: null, or (oplen, tnum) float64, the operator applied to every trace (a device array in the _dev form).
+ * impdar_acorr: out[l][j] = r_j[l], l = 0 .. maxlag: (maxlag + 1, tnum) float64; normalize != 0 divides by r_j[0], a
+ *   dead trace's column is NaN.
+ * ERR_ARG, before any device work, with the reason of csrc/decon_route.h: oplen outside 1 .. 256; gap < 1; a window that
+ *   is not 0 <= s0 < s1 <= snum; gap + oplen > s1 - s0; maxlag < 0 or >= s1 - s0; prewhiten negative or not finite;
+ *   another design or dtype.
+ * Metrics: "device_ms" and the stages "acorr_ms", "solve_ms", "apply_ms" (impdar_acorr: "acorr_ms"); the _dev forms
+ *   return with the stream drained. */
+int impdar_decon(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int s0, int s1,
+                 int oplen, int gap, double prewhiten, int design, void *out, double *op);
+int impdar_decon_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int s0, int s1,
+                     int oplen, int gap, double prewhiten, int design, void *d_out, double *d_op);
+int impdar_acorr(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int s0, int s1,
+                 int maxlag, int normalize, double *out);
+int impdar_acorr_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int s0, int s1,
+                     int maxlag, int normalize, double *d_out);
+
 /* ---- the library's own batched power-of-two row transforms (csrc/own_fft.h) ----
  * What the Stolt / phase-shift calls of power-of-two sizes run their transforms on (rocFFT compiles the kernels of
  * lengths above 1024 at run time: 0.25-3 s per plan, profiles/r05_first_call.txt).  numpy.fft conventions
