@@ -443,6 +443,78 @@ def main():
                    "copy_same_run": {"ms": float(np.median(cp)), "ms_spread": max(cp) - min(cp), "bytes": 3 * snum * tnum * 4},
                    "cpu_baseline": cb if k == 'oplen32' else None}
             print(json.dumps(rec), flush=True)
+    if 'attr' not in args.skip:
+        # Complex-trace attributes at the headline radargram's shape, resident, out of place: envelope, phase, frequency and the
+        # frequency smoothed over 9 samples, the calls alternated after warm-up, device times from the HIP events of each call
+        # (metrics line).  The compulsory bytes are one read and one write of the radargram; a device copy of the same bytes in
+        # the same run is the yardstick.  CPU: scipy.signal.hilbert and NumPy on one core (tests/attr_ref.py, ref) on 100 traces.
+        import ctypes
+        from impdar_amd import attributes as atlib
+        ctx, lib = _hip.context(), _hip.load()
+        buf = ctypes.create_string_buffer(1024)
+        snum, tnum = FIELD
+        dt_s = 2.5e-9
+        xf = rng.standard_normal((snum, tnum)).astype(np.float32)
+        d_x = _hip.DeviceArray.from_host(ctx, xf)
+        d_o = _hip.DeviceArray(ctx, (snum, tnum), np.float32)
+        confs = {'envelope': ('envelope', 1), 'phase': ('phase', 1), 'frequency': ('frequency', 1), 'frequency smooth 9': ('frequency', 9)}
+
+        def call(name):
+            kind, smooth = confs[name]
+            atlib.attr_dev(d_x, atlib.check_attr((snum, tnum), kind, smooth, dt_s), out=d_o)
+            _hip.check(lib.impdar_ctx_last_metrics(ctx, buf, len(buf)), 'metrics')
+            return json.loads(buf.value.decode())
+
+        def copy_ms():
+            # a device copy that reads one radargram and writes one: ten enqueued back to back per sample, the host clock around
+            # them and one synchronise, so that the launches hide behind the copies
+            n64 = snum * tnum // 2
+            a, b = _hip.DeviceArray(ctx, (n64, 1), np.float64), _hip.DeviceArray(ctx, (n64, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, n64 * 8)
+            out = []
+            for _ in range(12):
+                lib.impdar_ctx_sync(ctx)
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(n64))
+                lib.impdar_ctx_sync(ctx)
+                out.append((time.perf_counter() - t0) * 100.0)
+            a.free()
+            b.free()
+            return out[2:]
+        ms = {k: [] for k in confs}
+        kernels, finite = {}, {}
+        for k in confs:
+            for _ in range(2):
+                kernels[k] = call(k)['kernel']
+            finite[k] = bool(np.isfinite(d_o.to_host()).all())
+        for _ in range(max(10, args.reps)):
+            for k in confs:
+                ms[k].append(call(k)['device_ms'])
+        cp = copy_ms()
+        d_x.free()
+        d_o.free()
+        cbs = {k: None for k in confs}
+        if not args.no_cpu:
+            import os
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+            import attr_ref
+            attr_ref.attr_ref(xf[:64, :2], 'envelope')          # (SciPy's import is not part of the figure)
+            for k, (kind, smooth) in confs.items():
+                t0 = time.perf_counter()
+                attr_ref.attr_ref(xf[:, :100], kind, smooth, dt_s)
+                el = time.perf_counter() - t0
+                cbs[k] = {"seconds": el * tnum / 100.0, "kind": "numpy", "cores": 1,
+                          "sample": "scipy.signal.hilbert + NumPy (tests/attr_ref.py, ref) on 100 traces: %.3f s, extrapolated by trace count" % el}
+        nbytes = 2 * snum * tnum * 4
+        for k in confs:
+            t = float(np.median(ms[k]))
+            print(json.dumps({"path": "attributes 4096 x 10000 float32, %s" % k,
+                              "config": "%dx%d float32, resident, out of place, kind=%s, smooth=%d" % ((snum, tnum) + confs[k]),
+                              "kernel": kernels[k], "finite": finite[k], "device_ms": t, "device_ms_spread": max(ms[k]) - min(ms[k]),
+                              "device_ms_all": ms[k], "bytes": nbytes, "frac_hbm_peak": nbytes / (t * 1e-3) / 8.0e12,
+                              "copy_same_run": {"ms": float(np.median(cp)), "ms_spread": max(cp) - min(cp), "bytes": nbytes},
+                              "cpu_baseline": cbs[k]}), flush=True)
     if 'vscan' not in args.skip:
         # The Stolt velocity scan at config 2, resident: 32 velocities in one impdar_stolt_scan_dev call against what a user does
         # without it -- 32 impdar_stolt_dev calls, each image downloaded and reduced to the same three sums per row in NumPy.

@@ -82,6 +82,9 @@ SIGNATURES = {
     'impdar_decon_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _d, _i, _p, _p]),
     'impdar_acorr': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _dp]),
     'impdar_acorr_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    'impdar_attr': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
+    'impdar_attr_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
+    'impdar_attr_route_probe': (_i, [_i, _i, _i, _i, _ip]),
     'impdar_fft_rows_dev':(_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_fft_rows_any_dev': (_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_phaseshift': (_i, [_p, _p, _i, _i, _i, _i, _dp, _dp, _d, _dp, _d, _dp, _i, _d, _d, _p]),

@@ -11,6 +11,9 @@ extension, scans the focus of the Stolt image over NV velocities (``RadarData.ve
 extension, is the f-k fan (dip) filter (``RadarData.fk_filter``) and writes ``<name>_fk.mat``.
 ``impproc decon --oplen N [--gap G] [--prewhiten P] [--window S0 S1] [--design each|mean] files``, a fourth, is predictive
 deconvolution (``RadarData.predictive_decon``) and writes ``<name>_decon.mat``.
+``impproc attr --kind envelope|phase|frequency [--smooth W] files``, a fifth, replaces every trace by a complex-trace
+attribute (``RadarData.envelope``, ``instantaneous_phase``, ``instantaneous_frequency``) and writes ``<name>_env.mat``,
+``<name>_phase.mat`` or ``<name>_ifreq.mat``.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
@@ -39,6 +42,9 @@ import sys
 
 from ..lib.load import load, FILETYPE_OPTIONS
 from ..lib.gpslib import interp as interpdeep
+
+
+ATTR_NAMES = {'envelope': 'env', 'phase': 'phase', 'frequency': 'ifreq'}      # `impproc attr --kind`: the output's suffix
 
 
 def _get_args():
@@ -214,6 +220,14 @@ def _get_args():
                               help='An operator per trace, or one from the autocorrelations summed over the traces')
     _add_def_args(parser_decon)
 
+    parser_attr = subparsers.add_parser('attr', help='(extension) complex-trace attribute of every trace: envelope '
+                                                     '(reflection strength), instantaneous phase or frequency')
+    parser_attr.set_defaults(func=attr, name='attr')
+    parser_attr.add_argument('--kind', type=str, required=True, choices=sorted(ATTR_NAMES), help='The attribute that replaces the data')
+    parser_attr.add_argument('--smooth', type=int, default=1,
+                             help='Frequency only: mean over so many samples (odd, 1 .. 255) weighted by the squared envelope (default 1: none)')
+    _add_def_args(parser_attr)
+
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
@@ -249,6 +263,8 @@ def main():
     if not hasattr(args, 'func'):
         parser.parse_args(['-h'])
 
+    if args.name == 'attr':
+        args.name = ATTR_NAMES[args.kind]
     radar_data = load(args.ftype, args.fns)
     if args.name == 'vscan':
         # (its result is a table of focus values, not a radargram: it names and writes its own files)
@@ -370,6 +386,18 @@ def fk(dat, va_lo=None, va_hi=None, taper=0.1, mode='pass', dip='both', **kwargs
 def decon(dat, oplen=None, gap=1, prewhiten=0.1, window=None, design='each', **kwargs):
     """(extension) predictive deconvolution."""
     dat.predictive_decon(oplen, gap=gap, prewhiten=prewhiten, window=None if window is None else tuple(window), design=design)
+
+
+def attr(dat, kind=None, smooth=1, **kwargs):
+    """(extension) complex-trace attribute."""
+    if kind == 'frequency':
+        dat.instantaneous_frequency(smooth=smooth)
+    elif smooth != 1:
+        raise ValueError('--smooth goes with --kind frequency alone')
+    elif kind == 'phase':
+        dat.instantaneous_phase()
+    else:
+        dat.envelope()
 
 
 def _out_name(fn, o, nfiles, name):

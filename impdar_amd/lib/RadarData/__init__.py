@@ -26,7 +26,9 @@ and ``flattened`` (``_RadarDataDisplay.py``), and two extensions on the Stolt
 transforms: ``velocity_scan`` (``velscan.py``) and the f-k fan filter with its
 spectrum, ``fk_filter`` and ``fk_spectrum`` (``fk.py``), and a third along the
 traces: ``predictive_decon``, ``decon_operators`` and ``autocorrelation``
-(``decon.py``).  Everything else in the
+(``decon.py``), and a fourth, the complex-trace attributes ``envelope``,
+``instantaneous_phase``, ``instantaneous_frequency``, ``complex_attribute``
+and ``analytic_signal`` (``attributes.py``).  Everything else in the
 reference's class (moving picks with the data, GPS, the ApRES plots) is out
 of scope.
 """
@@ -51,6 +53,8 @@ from ... import resident as _resident
 from ...velscan import stolt_velocity_scan as _velocity_scan
 from ...fk import fk_filter as _fk_filter, fk_spectrum as _fk_spectrum
 from ...decon import autocorrelation as _autocorrelation, decon_operators as _decon_operators, predictive_decon as _predictive_decon
+from ...attributes import analytic_signal as _analytic_signal, complex_attribute as _complex_attribute, envelope as _envelope
+from ...attributes import instantaneous_frequency as _instantaneous_frequency, instantaneous_phase as _instantaneous_phase
 from ._resident import data_dtype as _resident_dtype, data_shape as _resident_shape
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -96,6 +100,11 @@ class RadarData(object):
     predictive_decon = _predictive_decon
     decon_operators = _decon_operators
     autocorrelation = _autocorrelation
+    envelope = _envelope
+    instantaneous_phase = _instantaneous_phase
+    instantaneous_frequency = _instantaneous_frequency
+    complex_attribute = _complex_attribute
+    analytic_signal = _analytic_signal
     to_device = _resident.to_device
     from_device = _resident.from_device
 

@@ -278,6 +278,29 @@ int impdar_acorr(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnu
 int impdar_acorr_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int s0, int s1,
                      int maxlag, int normalize, double *d_out);
 
+/* ---- complex-trace attributes: envelope, instantaneous phase and frequency (csrc/attr.hip; an extension) ----
+ * The contract is csrc/attr_route.h; all arithmetic is float64 for both dtypes.  Per trace (column) x of n = snum samples:
+ * q = irfft(Y, n) with Y[k] = -i rfft(x)[k] for 0 < k < n / 2 (and k = (n - 1) / 2 of an odd n), Y[0] = 0, Y[n / 2] = 0 for
+ * even n -- imag(scipy.signal.hilbert(x)); n <= 2 gives q = 0.  With z = x + i q:
+ *   kind 0 quadrature q;  1 envelope hypot(x, q);  2 phase atan2(q, x) in radians;
+ *   kind 3 frequency f[k] = arg(z[k + 1] conj z[k]) / (2 pi dt) in Hz, f[n - 1] = f[n - 2], 0 for n = 1; with smooth = W > 1
+ *   (odd, at most 255) the mean of f over |j - k| <= (W - 1) / 2, clipped to the trace, weighted by x[j]^2 + q[j]^2 and summed
+ *   with j rising, 0 where the weights sum to 0.  smooth = 1 leaves f as it is; dt is read for kind 3 alone.
+ * out is (snum, tnum) of dtype, rounded once (d_out may be d_data: the result is the out-of-place one bit for bit).  A trace
+ * with a sample that is not finite is NaN throughout, an all-zero trace gives zeros; both are decided by a reduction over
+ * the trace, not by a transform.  No floating-point atomics: two calls give the same bits.
+ * ERR_ARG, before any device work, with the reason of csrc/attr_route.h: an unknown kind; smooth even or outside 1 .. 255;
+ *   smooth > 1 with a kind other than 3; dt not finite or not positive (kind 3); an empty radargram; another dtype.
+ * impdar_attr_route_probe: what csrc/attr_route.h decides for tnum traces of snum samples: out[0] = 0 own power-of-two
+ *   transform, 1 own mixed-radix transform, 2 rocFFT; out[1] threads of the row kernel; out[2] workgroups; out[3] traces
+ *   per workgroup; out[4] bytes of LDS per workgroup; out[5] = 1 when no transform runs (n <= 2).  No device call.
+ * Metrics: "device_ms"; the _dev form enqueues on the context's compute stream. */
+int impdar_attr(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int kind, int smooth,
+                double dt, void *out);
+int impdar_attr_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int kind, int smooth,
+                    double dt, void *d_out);
+int impdar_attr_route_probe(int snum, int tnum, int kind, int smooth, int *out);
+
 /* ---- the library's own batched power-of-two row transforms (csrc/own_fft.h) ----
  * What the Stolt / phase-shift calls of power-of-two sizes run their transforms on (rocFFT compiles the kernels of
  * lengths above 1024 at run time: 0.25-3 s per plan, profiles/r05_first_call.txt).  numpy.fft conventions
