@@ -515,6 +515,92 @@ def main():
                               "device_ms_all": ms[k], "bytes": nbytes, "frac_hbm_peak": nbytes / (t * 1e-3) / 8.0e12,
                               "copy_same_run": {"ms": float(np.median(cp)), "ms_spread": max(cp) - min(cp), "bytes": nbytes},
                               "cpu_baseline": cbs[k]}), flush=True)
+    if 'slope' not in args.skip:
+        # Layer slopes at the headline radargram's shape, resident, out of place: the slope field at sigma = (2, 8), dipsmooth with
+        # half 4 on a given slope, and the two together (no slope given), the calls alternated after warm-up, device times from the
+        # HIP events of each call (metrics line).  Compulsory bytes: the field reads the radargram and writes float64; dipsmooth
+        # reads the radargram and the float64 slope and writes the radargram; the two together read and write the radargram.  A
+        # device copy of the same bytes in the same run is the yardstick.  CPU: np.gradient, scipy.ndimage.gaussian_filter and
+        # NumPy on one core (tests/slope_ref.py, ref) on 100 traces.
+        import ctypes
+        from impdar_amd import slope as sllib
+        ctx, lib = _hip.context(), _hip.load()
+        buf = ctypes.create_string_buffer(1024)
+        snum, tnum = FIELD
+        sigma, half, max_slope = (2.0, 8.0), 4, 4.0
+        xf = rng.standard_normal((snum, tnum)).astype(np.float32)
+        d_x = _hip.DeviceArray.from_host(ctx, xf)
+        d_o = _hip.DeviceArray(ctx, (snum, tnum), np.float32)
+        d_p = _hip.DeviceArray(ctx, (snum, tnum), np.float64)
+        count = snum * tnum
+        confs = {'slope field': 4 * count + 8 * count, 'dipsmooth, slope given': 4 * count + 8 * count + 4 * count,
+                 'dipsmooth, own slope': 4 * count + 4 * count}
+
+        def call(name):
+            if name == 'slope field':
+                sllib.slope_dev(d_x, sllib.check_slope((snum, tnum), 'slope', sigma, max_slope), d_p)
+            elif name == 'dipsmooth, slope given':
+                sllib.dipsmooth_dev(d_x, sllib.check_dipsmooth((snum, tnum), half, sigma, max_slope, d_p), d_p, out=d_o)
+            else:
+                sllib.dipsmooth_dev(d_x, sllib.check_dipsmooth((snum, tnum), half, sigma, max_slope), None, out=d_o)
+            _hip.check(lib.impdar_ctx_last_metrics(ctx, buf, len(buf)), 'metrics')
+            return json.loads(buf.value.decode())
+
+        def copy_ms(nbytes):
+            # a device copy that moves `nbytes` in all: ten enqueued back to back per sample, the host clock around them and one
+            # synchronise, so that the launches hide behind the copies
+            n64 = nbytes // 16
+            a, b = _hip.DeviceArray(ctx, (n64, 1), np.float64), _hip.DeviceArray(ctx, (n64, 1), np.float64)
+            lib.impdar_dev_memset(ctx, a.ptr, 0, n64 * 8)
+            out = []
+            for _ in range(12):
+                lib.impdar_ctx_sync(ctx)
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    lib.impdar_cast_dev(ctx, a.ptr, _hip.F64, b.ptr, _hip.F64, ctypes.c_size_t(n64))
+                lib.impdar_ctx_sync(ctx)
+                out.append((time.perf_counter() - t0) * 100.0)
+            a.free()
+            b.free()
+            return out[2:]
+        ms = {k: [] for k in confs}
+        kernels, finite = {}, {}
+        for k in confs:
+            for _ in range(2):
+                kernels[k] = call(k)['kernel']
+            finite[k] = bool(np.isfinite((d_p if k == 'slope field' else d_o).to_host()).all())
+        for _ in range(max(10, args.reps)):
+            for k in confs:
+                ms[k].append(call(k)['device_ms'])
+        cps = {k: copy_ms(nb) for k, nb in confs.items()}
+        d_x.free()
+        d_o.free()
+        d_p.free()
+        cbs = {k: None for k in confs}
+        if not args.no_cpu:
+            import os
+            sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+            import slope_ref
+            part = xf[:, :100]
+            slope_ref.slope_ref(xf[:64, :8], 'slope', sigma)            # (SciPy's import is not part of the figure)
+            t0 = time.perf_counter()
+            p_cpu = slope_ref.slope_ref(part, 'slope', sigma, max_slope)
+            t_field = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            slope_ref.dipsmooth_ref(part, half, p_cpu)
+            t_mean = time.perf_counter() - t0
+            for k, el in (('slope field', t_field), ('dipsmooth, slope given', t_mean), ('dipsmooth, own slope', t_field + t_mean)):
+                cbs[k] = {"seconds": el * tnum / 100.0, "kind": "numpy", "cores": 1,
+                          "sample": "np.gradient + scipy.ndimage.gaussian_filter + NumPy (tests/slope_ref.py, ref) on 100 traces: %.3f s, "
+                                    "extrapolated by trace count" % el}
+        for k, nbytes in confs.items():
+            t, cp = float(np.median(ms[k])), cps[k]
+            print(json.dumps({"path": "layer slopes 4096 x 10000 float32, %s" % k,
+                              "config": "%dx%d float32, resident, out of place, sigma=(2, 8), half=%d, max_slope=4" % (snum, tnum, half),
+                              "kernel": kernels[k], "finite": finite[k], "device_ms": t, "device_ms_spread": max(ms[k]) - min(ms[k]),
+                              "device_ms_all": ms[k], "bytes": nbytes, "frac_hbm_peak": nbytes / (t * 1e-3) / 8.0e12,
+                              "copy_same_run": {"ms": float(np.median(cp)), "ms_spread": max(cp) - min(cp), "bytes": nbytes},
+                              "times_copy": t / float(np.median(cp)), "cpu_baseline": cbs[k]}), flush=True)
     if 'vscan' not in args.skip:
         # The Stolt velocity scan at config 2, resident: 32 velocities in one impdar_stolt_scan_dev call against what a user does
         # without it -- 32 impdar_stolt_dev calls, each image downloaded and reduced to the same three sums per row in NumPy.

@@ -85,6 +85,11 @@ SIGNATURES = {
     'impdar_attr': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
     'impdar_attr_dev': (_i, [_p, _p, _i, _i, _i, _i, _i, _d, _p]),
     'impdar_attr_route_probe': (_i, [_i, _i, _i, _i, _ip]),
+    'impdar_slope': (_i, [_p, _p, _i, _i, _i, _i, _d, _d, _d, _dp]),
+    'impdar_slope_dev': (_i, [_p, _p, _i, _i, _i, _i, _d, _d, _d, _p]),
+    'impdar_dipsmooth': (_i, [_p, _p, _i, _i, _i, _i, _dp, _d, _d, _d, _p]),
+    'impdar_dipsmooth_dev': (_i, [_p, _p, _i, _i, _i, _i, _p, _d, _d, _d, _p]),
+    'impdar_slope_route_probe': (_i, [_i, _i, _d, _d, _i, _ip]),
     'impdar_fft_rows_dev':(_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_fft_rows_any_dev': (_i, [_p, _i, _i, _i, _i, _p, _p, _d]),
     'impdar_phaseshift': (_i, [_p, _p, _i, _i, _i, _i, _dp, _dp, _d, _dp, _d, _dp, _i, _d, _d, _p]),

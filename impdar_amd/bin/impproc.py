@@ -14,6 +14,10 @@ deconvolution (``RadarData.predictive_decon``) and writes ``<name>_decon.mat``.
 ``impproc attr --kind envelope|phase|frequency [--smooth W] files``, a fifth, replaces every trace by a complex-trace
 attribute (``RadarData.envelope``, ``instantaneous_phase``, ``instantaneous_frequency``) and writes ``<name>_env.mat``,
 ``<name>_phase.mat`` or ``<name>_ifreq.mat``.
+``impproc dipsmooth HALF [--sigma SZ SX] [--max_slope P] files``, a sixth, averages every sample over ``2 HALF + 1`` traces
+along the layers' local slope (``RadarData.dip_smooth``) and writes ``<name>_dipsm.mat``; ``impproc slope --kind
+slope|dip|coherence [--sigma SZ SX] [--max_slope P] files`` replaces the data by that field (``RadarData.layer_slope``) and
+writes ``<name>_slope.mat``, ``<name>_dip.mat`` or ``<name>_coh.mat``, which ``impplot rg`` shows.
 
 Mirrors these sub-commands of the reference's ``src/impdar/bin/impproc.py`` (migrate parser ``:295-343``,
 hfilt ``:30-43``, ahfilt ``:46-54``, vbp ``:113-125``, hbp ``:128-139``, lp ``:141-146``, interp ``:222-251``,
@@ -44,6 +48,7 @@ from ..lib.load import load, FILETYPE_OPTIONS
 from ..lib.gpslib import interp as interpdeep
 
 
+SLOPE_NAMES = {'slope': 'slope', 'dip': 'dip', 'coherence': 'coh'}                # `impproc slope --kind`: the output's suffix
 ATTR_NAMES = {'envelope': 'env', 'phase': 'phase', 'frequency': 'ifreq'}      # `impproc attr --kind`: the output's suffix
 
 
@@ -228,6 +233,23 @@ def _get_args():
                              help='Frequency only: mean over so many samples (odd, 1 .. 255) weighted by the squared envelope (default 1: none)')
     _add_def_args(parser_attr)
 
+    parser_dipsm = subparsers.add_parser('dipsmooth', help='(extension) mean over 2 HALF + 1 traces along the local slope of the layers')
+    parser_dipsm.set_defaults(func=dipsmooth, name='dipsm')
+    parser_dipsm.add_argument('half', type=int, help='Traces on either side of the sample (1 .. 32)')
+    parser_dipsm.add_argument('--sigma', type=float, nargs=2, default=[2.0, 8.0], metavar=('SZ', 'SX'),
+                              help='Gaussian neighbourhood of the slope estimate in samples and in traces (default 2 8)')
+    parser_dipsm.add_argument('--max_slope', type=float, default=4.0, help='Largest slope followed, in samples per trace (default 4)')
+    _add_def_args(parser_dipsm)
+
+    parser_slope = subparsers.add_parser('slope', help='(extension) replace the data by the local slope of the layers, their dip '
+                                                       'or the coherence of the estimate')
+    parser_slope.set_defaults(func=slope, name='slope')
+    parser_slope.add_argument('--kind', type=str, required=True, choices=sorted(SLOPE_NAMES), help='The field that replaces the data')
+    parser_slope.add_argument('--sigma', type=float, nargs=2, default=[2.0, 8.0], metavar=('SZ', 'SX'),
+                              help='Gaussian neighbourhood in samples and in traces (default 2 8)')
+    parser_slope.add_argument('--max_slope', type=float, default=4.0, help='Clamp of the slope, in samples per trace (default 4)')
+    _add_def_args(parser_slope)
+
     parser_interp = subparsers.add_parser('interp', help='Reinterpolate GPS')
     parser_interp.set_defaults(func=interp, name='interp')
     parser_interp.add_argument('spacing', type=float, help='New spacing of radar traces, in meters')
@@ -265,6 +287,8 @@ def main():
 
     if args.name == 'attr':
         args.name = ATTR_NAMES[args.kind]
+    if args.name == 'slope':
+        args.name = SLOPE_NAMES[args.kind]
     radar_data = load(args.ftype, args.fns)
     if args.name == 'vscan':
         # (its result is a table of focus values, not a radargram: it names and writes its own files)
@@ -398,6 +422,19 @@ def attr(dat, kind=None, smooth=1, **kwargs):
         dat.instantaneous_phase()
     else:
         dat.envelope()
+
+
+def dipsmooth(dat, half=None, sigma=(2.0, 8.0), max_slope=4.0, **kwargs):
+    """(extension) mean along the layers."""
+    dat.dip_smooth(half, sigma=tuple(sigma), max_slope=max_slope)
+
+
+def slope(dat, kind=None, sigma=(2.0, 8.0), max_slope=4.0, **kwargs):
+    """(extension) the data replaced by a field of the layers' orientation (float64)."""
+    field = dat.layer_slope(sigma=tuple(sigma), kind=kind, max_slope=max_slope)
+    if getattr(dat, '_dev', None) is not None:
+        dat.from_device()
+    dat.data = field
 
 
 def _out_name(fn, o, nfiles, name):

@@ -13,7 +13,7 @@ LIB = os.path.join(CSRC, 'libimpdar_hip.so')
 SOURCES = ['api.hip', 'download.hip', 'comm.hip', 'kirchhoff.hip', 'kirch_ring32.hip', 'kirch_ring64.hip', 'kirch_oneshot.hip', 'kirch_gen.hip',
            'fft.hip', 'stolt.hip', 'phaseshift.hip', 'ffd.hip', 'preproc.hip', 'hfilt.hip', 'denoise.hip', 'hpass.hip', 'vaxis.hip', 'gain.hip',
            'taxis.hip', 'quadpol.hip', 'apres.hip', 'pick.hip', 'spectrum.hip', 'display.hip', 'rawload.hip', 'gpstrack.hip',
-           'attsearch.hip', 'fk.hip', 'decon.hip', 'attr.hip']
+           'attsearch.hip', 'fk.hip', 'decon.hip', 'attr.hip', 'slope.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-ffp-contract=off',
          '-fno-slp-vectorize', '-Wall', '-Wno-unused-function']
 

@@ -183,6 +183,7 @@ void impdar_gpstrack_forget(impdar_ctx *ctx);      // gpstrack.hip
 void impdar_attsearch_forget(impdar_ctx *ctx);     // attsearch.hip
 void impdar_decon_forget(impdar_ctx *ctx);         // decon.hip
 void impdar_attr_forget(impdar_ctx *ctx);          // attr.hip
+void impdar_slope_forget(impdar_ctx *ctx);         // slope.hip
 
 void impdar_kirch_trim();    // kirch_oneshot.hip
 void impdar_stolt_trim();    // stolt.hip
@@ -224,6 +225,7 @@ extern "C" void impdar_ctx_destroy(impdar_ctx *ctx)
     impdar_attsearch_forget(ctx);
     impdar_decon_forget(ctx);
     impdar_attr_forget(ctx);
+    impdar_slope_forget(ctx);
     impdar_devcache_trim(ctx->device);
     impdar_ctx_pinned_release(ctx);
     if (ctx->ev_produced) (void)hipEventDestroy(ctx->ev_produced);

@@ -217,7 +217,7 @@ template <int N> static int impdar_upload_tables(impdar_ctx *ctx, DevBuf &buf, c
 }
 
 // What a unit of processing steps (preproc.hip, hfilt.hip, denoise.hip, hpass.hip, vaxis.hip, gain.hip, taxis.hip,
-// quadpol.hip, apres.hip, pick.hip, spectrum.hip, display.hip, rawload.hip, gpstrack.hip, attsearch.hip, decon.hip, attr.hip) keeps between calls: its buffers -- `Bufs`, with a release() that frees every one of them -- and the context they
+// quadpol.hip, apres.hip, pick.hip, spectrum.hip, display.hip, rawload.hip, gpstrack.hip, attsearch.hip, decon.hip, attr.hip, slope.hip) keeps between calls: its buffers -- `Bufs`, with a release() that frees every one of them -- and the context they
 // belong to.  One set per process and step: entry points of different contexts / threads take turns, each holding
 // lock() from its argument check to its return (re-entrant because the host-buffer forms call the resident ones).
 template <class Bufs> struct StepScratch : Bufs {

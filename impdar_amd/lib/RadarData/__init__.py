@@ -28,7 +28,9 @@ spectrum, ``fk_filter`` and ``fk_spectrum`` (``fk.py``), and a third along the
 traces: ``predictive_decon``, ``decon_operators`` and ``autocorrelation``
 (``decon.py``), and a fourth, the complex-trace attributes ``envelope``,
 ``instantaneous_phase``, ``instantaneous_frequency``, ``complex_attribute``
-and ``analytic_signal`` (``attributes.py``).  Everything else in the
+and ``analytic_signal`` (``attributes.py``), and a fifth, the layers' local
+slope and the mean along it, ``layer_slope`` and ``dip_smooth``
+(``slope.py``).  Everything else in the
 reference's class (moving picks with the data, GPS, the ApRES plots) is out
 of scope.
 """
@@ -55,6 +57,7 @@ from ...fk import fk_filter as _fk_filter, fk_spectrum as _fk_spectrum
 from ...decon import autocorrelation as _autocorrelation, decon_operators as _decon_operators, predictive_decon as _predictive_decon
 from ...attributes import analytic_signal as _analytic_signal, complex_attribute as _complex_attribute, envelope as _envelope
 from ...attributes import instantaneous_frequency as _instantaneous_frequency, instantaneous_phase as _instantaneous_phase
+from ...slope import dip_smooth as _dip_smooth, layer_slope as _layer_slope
 from ._resident import data_dtype as _resident_dtype, data_shape as _resident_shape
 
 STODEEP_ATTRS = ['data', 'migdata', 'interp_data', 'nmo_data', 'filtdata', 'hfilt_data']
@@ -105,6 +108,8 @@ class RadarData(object):
     instantaneous_frequency = _instantaneous_frequency
     complex_attribute = _complex_attribute
     analytic_signal = _analytic_signal
+    layer_slope = _layer_slope
+    dip_smooth = _dip_smooth
     to_device = _resident.to_device
     from_device = _resident.from_device
 

@@ -301,6 +301,35 @@ int impdar_attr_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, in
                     double dt, void *d_out);
 int impdar_attr_route_probe(int snum, int tnum, int kind, int smooth, int *out);
 
+/* ---- layer slopes: structure-tensor dip field and dip-steered mean (csrc/slope.hip; an extension) ----
+ * The contract is csrc/slope_route.h; all arithmetic is float64 for both dtypes; a sample that is not finite is read as NaN.
+ * impdar_slope: gradients gz, gx in index units (np.gradient), the products gz gz, gz gx, gx gx smoothed by a separable
+ *   Gaussian (sigma_x along the traces, then sigma_z along the samples; radius int(4 sigma + 0.5), clamped indices, sigma 0
+ *   leaves the axis alone) into a, b, c; d = a - c, D = sqrt(d d + 4 b b).  out is a float64 (snum, tnum) field:
+ *   kind 0 slope in samples per trace (-2b / (d + D) where d >= 0, -(D - d) / (2b) where d < 0, 0 where D = 0), clamped to
+ *   +-max_slope;  1 dip atan2(-2b, d) / 2 in radians;  2 coherence D / (a + c) (0 where a + c is not positive);
+ *   3, 4, 5: a, b, c.  A NaN in a, b or c gives NaN in kinds 0 .. 2.
+ * impdar_dipsmooth: every sample becomes the mean over the traces j - half .. j + half inside the radargram of their linear
+ *   interpolation at k + p i clamped to the trace, p the slope at the sample itself -- `slope` (float64, (snum, tnum); a
+ *   device pointer in the _dev form) or, when that is null, kind 0 at (sigma_z, sigma_x, max_slope), which are not read
+ *   otherwise.  A NaN p gives NaN.  out is (snum, tnum) of dtype, rounded once; d_out may be d_data (the same bits).
+ * No floating-point atomics and one fixed order of every sum: two calls give the same bits.
+ * ERR_ARG, before any device work, with the reason of csrc/slope_route.h: an unknown kind; a sigma not finite, negative or
+ *   above 16; max_slope not finite or not positive; half outside 1 .. 32; an empty radargram; another dtype.
+ * impdar_slope_route_probe: what csrc/slope_route.h decides: out[0], out[1] the radii r_z, r_x; out[2 .. 4] threads,
+ *   workgroups and bytes of LDS of the row pass; out[5 .. 7] of the column pass; out[8], out[9] threads and workgroups of
+ *   the gather; out[10] MiB of scratch of an in-place float64 dipsmooth with no slope given (the most).  No device call.
+ * Metrics: "device_ms"; the _dev forms enqueue on the context's compute stream. */
+int impdar_slope(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int kind, double sigma_z,
+                 double sigma_x, double max_slope, double *out_f64);
+int impdar_slope_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int kind, double sigma_z,
+                     double sigma_x, double max_slope, double *d_out_f64);
+int impdar_dipsmooth(impdar_ctx *ctx, const void *data, int dtype, int snum, int tnum, int half,
+                     const double *slope_f64_or_null, double sigma_z, double sigma_x, double max_slope, void *out);
+int impdar_dipsmooth_dev(impdar_ctx *ctx, const void *d_data, int dtype, int snum, int tnum, int half,
+                         const double *d_slope_f64_or_null, double sigma_z, double sigma_x, double max_slope, void *d_out);
+int impdar_slope_route_probe(int snum, int tnum, double sigma_z, double sigma_x, int half, int *out);
+
 /* ---- the library's own batched power-of-two row transforms (csrc/own_fft.h) ----
  * What the Stolt / phase-shift calls of power-of-two sizes run their transforms on (rocFFT compiles the kernels of
  * lengths above 1024 at run time: 0.25-3 s per plan, profiles/r05_first_call.txt).  numpy.fft conventions
